@@ -14,6 +14,10 @@ N GPUs: the q latent GPs are sharded across ranks (latent i -> rank i mod N), to
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # N > 1 outside torch.distributed.run: starts the N ranks itself (self_launch)
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds what takes runs of its own: the
+per-kernel table and roofline (HIP events), the PLMC_SPLIT=0 / 3 runs beside the headline, the CPU oracle baseline and the
+fp64 accuracy checkpoints.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -174,6 +178,21 @@ def cpu_baseline(X, Y, P, n_latents):
                        "untimed latent evaluation: %.1f s; loss %.6f" % (n_latents, n, t, loss))
 
 
+def dump_outputs(path, loss, model):
+    """What a caller of the timed step receives -- the loss, every parameter's gradient and its value after the optimiser step
+    -- as path/<name>.npy in float32 / float64 (a few kB at the default shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        np.save(os.path.join(path, name + ".npy"), (a if a.dtype == torch.float64 else a.float()).numpy())
+
+
 def self_launch(n_ranks):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: run the N ranks as CHILD processes under
     torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1, a free port) and pass on their exit code.  Rank 0's
@@ -202,12 +221,18 @@ def main():
     ap.add_argument("--tasks", type=int, default=16)
     ap.add_argument("--latents", type=int, default=8)
     ap.add_argument("--variant", default="PLMC_fast", choices=["PLMC_fast", "PLMC"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-options", action="store_true", help="skip the runs with PLMC_SPLIT=0 (fp32 MFMA everywhere) and PLMC_SPLIT=3 (three bf16 planes) that are reported beside the headline")
-    ap.add_argument("--pmc", action="store_true", help="measure roofline.traffic live (two rocprofv3 --pmc child runs) "
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel table and roofline, the PLMC_SPLIT=0 / 3 "
+                                                       "runs, the CPU oracle baseline and the fp64 accuracy checkpoints")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the loss, gradients and updated parameters of the last timed "
+                                                          "step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and accuracy checkpoints")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: do not bracket kernels with HIP events")
+    ap.add_argument("--no-options", action="store_true", help="with --full: skip the runs with PLMC_SPLIT=0 (fp32 MFMA everywhere) and PLMC_SPLIT=3 (three bf16 planes) that are reported beside the headline")
+    ap.add_argument("--pmc", action="store_true", help="with --full: measure roofline.traffic live (two rocprofv3 --pmc child runs) "
                                                       "when no profile of this build is committed")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -255,13 +280,13 @@ def main():
                                       kernel_type=plmc.MaternKernel, init_lmc_coeffs=True,
                                       latent_shard=(rank, world) if world > 1 else None, **kw)
     # initial state for the CPU baseline / log-lik check (before moving to the device)
-    cpu_params = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    do_checks = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if do_checks:
         from oracle import bridge
         cpu_params = bridge.oracle_params(model, dtype=dt)                 # raw parameters of the initial model, oracle form
-    with torch.no_grad():
-        cpu_state = (model.covar_module.lengthscale.reshape(q, d).clone(), model.projected_noise().clone(),
-                     model.project_data(Y).clone())
+        with torch.no_grad():
+            cpu_state = (model.covar_module.lengthscale.reshape(q, d).clone(), model.projected_noise().clone(),
+                         model.project_data(Y).clone())
     model = model.to(dev)
     Xd, Yd = X.to(dev), Y.to(dev)
     model.train()
@@ -292,7 +317,6 @@ def main():
     # parameters, latents 0 and q-1 after 5 optimiser steps.  The mixing-matrix / noise-model parameters
     # sit behind d logp / d y~ through the same torch autograd on both sides.
     from projectedlmc import _engine
-    do_checks = rank == 0 and world == 1 and not args.no_cpu_baseline
     checkpoints = []                                    # (label, latent, ell, noise, ytil, lp_gpu, grad_gpu)
 
     def gpu_checkpoint(label, state, latents):
@@ -329,8 +353,8 @@ def main():
     # Inside the timed region only the two MFMA-heavy kernel classes (and the whole sweep) are bracketed by
     # HIP events: a bracket costs ~10 us of stream time, which on the ~200 short chain kernels of a step
     # would distort the very step time being measured.  The full per-kernel table comes from extra untimed
-    # steps afterwards.
-    prof = not args.no_prof
+    # steps afterwards.  A plain run (no --full) brackets nothing.
+    prof = args.full and not args.no_prof
     HEAVY = ("k_trail", "k_trail_head", "k_kinv_grad", "sweep_total")
     if prof:
         _hip.prof_enable(HEAVY)
@@ -341,6 +365,8 @@ def main():
         last = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                 # before any untimed step of --full moves the model on
+        dump_outputs(args.dump_outputs, last, model)
     stats = _hip.prof_collect() if prof else {}
     table, table_steps, iso = {}, 3, {}
     if prof:
@@ -363,7 +389,7 @@ def main():
     split = int(os.environ.get("PLMC_SPLIT", "2"))
     split = split if split in (0, 3) else 2
     options = {}
-    if world == 1 and not args.no_options:
+    if args.full and world == 1 and not args.no_options:
         for alt in (0, 3):
             if alt == split:
                 continue
@@ -472,7 +498,7 @@ def main():
                                  "note": "q n^3 flop per step over the step time, against the fp32 matrix peak %.1f TF (the step may "
                                          "exceed it: its bulk products run on the bf16 matrix cores)" % p32}
         note("%.2f ms/step on %d GPU(s)" % (1e3 * elapsed / args.steps, world))
-        if world == 1 and not args.no_cpu_baseline:
+        if do_checks:
             note("timing the CPU oracle on %d host cores (one full step of the same workload) ..." % host_cores())
             cb = cpu_baseline(X, Y, cpu_params, q)
             res["cpu_baseline"] = cb

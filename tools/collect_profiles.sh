@@ -18,5 +18,5 @@ cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -- python3 $OUT/../bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-prof --no-options > /dev/null 2>&1
 cp $(find $OUT/prof_stats -name "*kernel_stats.csv" | head -1) $OUT/${R}_bench_kernel_stats.csv || exit 1
 rm -rf $OUT/prof_stats
-python3 $OUT/../bench.py --steps 20 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/${R}_bench.log || exit 1
+python3 $OUT/../bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench.json 2> $OUT/${R}_bench.log || exit 1
 echo done
