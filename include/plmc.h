@@ -64,6 +64,13 @@ int64_t     plmc_vd_blocks(int64_t n_pad, int64_t lda);
  * in groups of 8 block rows (it ignores the dev knob PLMC_GRP: one kept buffer per 8 block rows is what this size reserves and
  * what plmc_potrs_aug_kept_f32 walks).  plmc_kinv_grad_vd_f32 accepts either scratch: the sweep records its per-latent stride. */
 int64_t     plmc_vd_blocks_keep(int64_t n_pad, int64_t lda);
+/* Offset, in floats from the start of one latent's Vd slice, of the block of scales a plmc_potrf_ex_f32 / plmc_factorize_ex_f32
+ * sweep leaves there (4-byte elements; either Vd size above; per-latent stride = that latent's Vd blocks x NB^2 floats):
+ *   [0..5]  the power-of-two scales of the split engine's six operand families (SU, SW, RU, RW, SA, RA; all 1 under PLMC_SPLIT=3),
+ *   [6] [7] the largest diagonal entry D of the input and lambda = max(min(eig_lo, smallest diagonal entry), 1e-12 D),
+ *   [104]   the number of planes of the scheme that wrote them (2 or 3), [105] the per-latent Vd stride in NB x NB blocks.
+ * Read-only, for tests and diagnostics; plmc_potrs_aug_kept_f32 rewrites [4] and [5] for its new augmented columns. */
+int64_t     plmc_split_scales_offset(int64_t n_pad, int64_t lda);
 /* Bytes of the `partials` scratch plmc_kinv_grad_* needs for (n_pad, q): per-tile partial sums, and for 4-byte elements the
  * bf16 planes of W (6 q n_pad^2 bytes).  plmc_grad_scratch_bytes = the 4-byte size. */
 int64_t     plmc_grad_scratch_bytes_for(int64_t n_pad, int q, int elem_bytes);
@@ -148,7 +155,7 @@ int plmc_potrf_ex_f64(double *A, int64_t n_pad, int64_t lda, int naug, int64_t s
 
 /* Assembly + factorisation in one call (round 4): plmc_assemble_* followed by plmc_potrf_ex_* on the same buffers, with the
  * assembly overlapped with the sweep -- the sweep writes the rows of its first group of block rows on the caller's stream and
- * queues the other rows (and the scan of the diagonal for the fp16 scales, which needs them) on a helper stream beside that
+ * queues the other rows (and the scan of their diagonal for the fp16 scales; the first group's rows are scanned before its chain) on a helper stream beside that
  * group's chain; nothing reads them before.  The augmented columns must be in place BEFORE the call (plmc_write_rhs_*,
  * plmc_assemble_cross_*).  n_pad = plmc_pad(n).  Same kernels on the same data as the two separate calls: bit-identical results
  * (tests/test_gpu_engine.py).  Replaces, like them: `self.covar_module(x)` + `likelihood(dist)` + the Cholesky inside `log_prob`

@@ -335,14 +335,16 @@ enum { SC_SU = 0, SC_SW = 1, SC_RU = 2, SC_RW = 3, SC_SA = 4, SC_RA = 5, SC_N = 
 // lambda_min is bounded below by the caller's `eig_lo` (the noise variance of a GP covariance) -- and by the smallest
 // diagonal entry, which brings in the identity padding of the rows beyond n (eigenvalue 1, whatever the noise).  SplitB3
 // needs no scales (all 1).  grid (q).
-// Two launches: k_scale_scan (grid (SCAN_PARTS, q): largest / smallest diagonal entry and largest |augmented entry| of a slice
+// Two launches: k_scale_scan (grid (parts, q): largest / smallest diagonal entry and largest |augmented entry| of a slice
 // of the rows, into 3 SCAN_PARTS floats behind the scales) and k_split_scales (grid (q): reduction of the partials + the scales).
+// The scan may be split by rows over several launches with disjoint partial slots (maxima and minima do not depend on the order):
+// rows row0 .. row1 - 1 into slots part0 .. part0 + gridDim.x - 1; a slot whose slice is empty holds the neutral values.
 constexpr int SCAN_PARTS = 32;
-__global__ __launch_bounds__(NTHREADS) void k_scale_scan(const float *__restrict__ A, int64_t n_pad, int64_t lda, int64_t strideA, int naug_pad,
-                                                         float *__restrict__ sc, int64_t sc_stride) {
+__global__ __launch_bounds__(NTHREADS) void k_scale_scan(const float *__restrict__ A, int64_t n_pad, int64_t row0, int64_t row1, int64_t lda,
+                                                         int64_t strideA, int naug_pad, float *__restrict__ sc, int64_t sc_stride, int part0) {
   __shared__ float r0[NTHREADS], r1[NTHREADS], r2[NTHREADS];
-  const int part = blockIdx.x, lat = blockIdx.y;
-  const int64_t rows = (n_pad + SCAN_PARTS - 1) / SCAN_PARTS, i0 = part * rows, i1 = i0 + rows < n_pad ? i0 + rows : n_pad;
+  const int part = part0 + (int)blockIdx.x, lat = blockIdx.y;
+  const int64_t rows = (row1 - row0 + gridDim.x - 1) / gridDim.x, i0 = row0 + blockIdx.x * rows, i1 = i0 + rows < row1 ? i0 + rows : row1;
   float d = 0.0f, dm = 3.0e38f, am = 0.0f;
   for (int64_t i = i0 + threadIdx.x; i < i1; i += NTHREADS) {
     const float v = A[(int64_t)lat * strideA + i * lda + i];
@@ -962,7 +964,7 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // rest panel -- other sweeps in flight on the device -- read half-overwritten planes)
   const int64_t vgp_elems = b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB);
   unsigned short *const VgP2[2] = {bf3 ? Praw + pl_buf : nullptr, bf3 ? Praw + pl_buf + vgp_elems : nullptr};
-  float *const scl = bf3 ? reinterpret_cast<float *>(VgP2[1] + vgp_elems) : nullptr;   // SC_N floats
+  float *const scl = bf3 ? reinterpret_cast<float *>(Vd) + plmc_split_scales_offset(n_pad, lda) : nullptr;   // behind VgP2[1]: one block
   // ... and, with the inverse factor, the full-height planes of W (n_pad columns per plane row) that plmc_kinv_grad_vd_* reads:
   // written by the same epilogues that write the rolling buffer, so the K^-1 kernel needs no split pass over W
   unsigned short *const Wk = (bf3 && with_inverse && vd_wk_blocks(n_pad, lda, (int)sizeof(T)) > 0)
@@ -1132,17 +1134,23 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // tiles of the diagonal-block outputs that k_diag leaves alone (they are read as parts of full 128 x 128 operands)
   hipLaunchKernelGGL(k_zero_diag_out<T>, dim3(m > GMAX ? m : GMAX, q), dim3(NTHREADS), 0, st, Vd, strideV, m, Wg, (int64_t)LDG,
                      strideV, (int64_t)NB * LDG + NB, GMAX, (int64_t)GMAX * NB);    // (+ the chain kernel's counters in the pad column of Wg)
-  auto scales = [&](hipStream_t s) {                      // scales of the operand families (SplitB3: ones), before anything splits
+  // scan of rows row0 .. row1 - 1 into the partial slots part0 .. part0 + parts - 1 (two-plane split only)
+  auto scan = [&](hipStream_t s, int64_t row0, int64_t row1, int part0, int parts) {
     if constexpr (bf3) {
       if (SS::NPL == 2)
-        hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, s, (const float *)A, n_pad, lda, strideA, (int)naug_pad, scl, sc_lat);
-      hipLaunchKernelGGL((k_split_scales<SS>), dim3(q), dim3(64), 0, s, n_pad, eig_lo, scl, sc_lat);
+        hipLaunchKernelGGL(k_scale_scan, dim3(parts, q), dim3(NTHREADS), 0, s, (const float *)A, n_pad, row0, row1, lda, strideA, (int)naug_pad, scl,
+                           sc_lat, part0);
     }
   };
+  auto split_scales = [&](hipStream_t s) {                // scales of the operand families (SplitB3: ones), before anything splits
+    if constexpr (bf3) hipLaunchKernelGGL((k_split_scales<SS>), dim3(q), dim3(64), 0, s, n_pad, eig_lo, scl, sc_lat);
+  };
   // A sweep that also assembles (plmc_factorize_ex_*, `job`) with the look-ahead on: only the first group's own block triangle is written
-  // in front of the chain, everything else -- and the scan of the diagonal for the scales, which needs it -- rides on the helper stream H
-  // beside the first group's chain (the first consumer of either, the transpose + head panel of group 0, waits for them: e_sc).
-  // `fused_la` is settled below, once the look-ahead is known to run.
+  // in front of the chain, everything else rides on the helper stream H beside the first group's chain (the first consumer, the
+  // transpose + head panel of group 0, waits for it: e_sc).  So does the scan for the scales -- but only of the rows below the first
+  // group: chain(0) overwrites the diagonal of the first group's rows (Schur updates, then U_ii) while H runs, so those rows are
+  // scanned on the caller's stream in front of the chain, into slots of their own (the scales are those of the input matrix, as in
+  // the two-call path, whatever the timing).  `fused_la` is settled below, once the look-ahead is known to run.
   auto finish = [&](hipStream_t s) {
     hipLaunchKernelGGL(k_logdet<T>, dim3(q), dim3(NTHREADS), 0, s, (const T *)A, n_pad, lda, strideA, logdet, info,
                        (const T *)(Wg + (int64_t)LDG + (int64_t)GMAX * NB), strideV, q);    // (the chain kernel's abort words: one per launch, at its first latent)
@@ -1274,7 +1282,10 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
     const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, st);
     if (rc != 0) return rc;
   }
-  if (!fused_la) scales(st);
+  if (!fused_la) {
+    scan(st, 0, n_pad, 0, SCAN_PARTS);
+    split_scales(st);
+  }
   if (!la) {
     // one stream: chain -> transpose -> group panel over every column -> trailing update of every row below
     // split engine: which engine a tile goes through must not depend on the schedule -- the same launches as under the look-ahead
@@ -1318,6 +1329,7 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   if (fused_la) {                                                               // the first group's own triangle: all its chain reads
     const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, G0(1), st, G0(1));
     if (rc != 0) return rc;
+    scan(st, 0, (int64_t)G0(1) * NB, 0, SCAN_PARTS / 2);                        // the first group's rows, before chain(0) writes them
   }
   (void)hipEventRecord(e_entry, st);
   (void)hipStreamWaitEvent(C, e_entry, 0);
@@ -1325,7 +1337,10 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   if (fused_la) {
     const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, H, -1, G0(1));            // everything else, beside chain(0)
     if (rc != 0) return rc;
-    scales(H);
+    // (nothing else H queues beside chain(0) touches the first group's triangle: the assembly skips it, k_raw_planes reads the
+    // columns right of it, k_split_scales the partials)
+    scan(H, (int64_t)G0(1) * NB, n_pad, SCAN_PARTS / 2, SCAN_PARTS / 2);         // the other rows
+    split_scales(H);
     (void)hipEventRecord(e_sc, H);
   }
   raw_planes0(H, G0(1));                                                        // (the head panel of the first group waits for it: e_hd)
@@ -1384,13 +1399,8 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
 bool vd_w_planes(const float *Vd, int64_t n_pad, int64_t lda, const unsigned short **wk, int64_t *wk_lat_stride, const float **w_scale,
                  int64_t *w_scale_lat_stride) {
   if (vd_wk_blocks(n_pad, lda, 4) <= 0) return false;
-  const int64_t m = n_pad / NB, strideV = plmc_vd_blocks_for(n_pad, lda, 4) * (int64_t)NB * NB;
-  const float *Wg = Vd + m * NB * NB;
-  const float *Pbulk = Wg + 4 * (int64_t)GMAX * NB * LDG;
-  const int64_t pl_buf = b3_elems<SplitB3>((int64_t)GMAX * NB, lda);
-  const unsigned short *Pl0 = reinterpret_cast<const unsigned short *>(Pbulk + (int64_t)GMAX * NB * lda);
-  const unsigned short *VgP = Pl0 + 3 * pl_buf;
-  const float *scl = reinterpret_cast<const float *>(VgP + 2 * b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB));
+  const int64_t strideV = plmc_vd_blocks_for(n_pad, lda, 4) * (int64_t)NB * NB;
+  const float *scl = Vd + plmc_split_scales_offset(n_pad, lda);
   *wk = reinterpret_cast<const unsigned short *>(scl + (int64_t)NB * NB);
   *wk_lat_stride = strideV * 2;
   *w_scale = scl + SC_SW;                                        // (the scheme tag sits SC_TAG - SC_SW floats behind it)
@@ -1479,13 +1489,14 @@ int potrs_aug_kept(float *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0
   unsigned short *const Pl0 = reinterpret_cast<unsigned short *>(Pbulk + (int64_t)GMAX * NB * lda);
   unsigned short *const Praw = Pl0 + 2 * pl_buf;
   unsigned short *const VgP2[2] = {Praw + pl_buf, Praw + pl_buf + vgp_elems};
-  float *const scl = reinterpret_cast<float *>(VgP2[1] + vgp_elems);
+  float *const scl = Vd + plmc_split_scales_offset(n_pad, lda);        // behind VgP2[1]: one block
   unsigned short *const Wk = reinterpret_cast<unsigned short *>(scl + (int64_t)NB * NB);
   unsigned short *const Uk0 = reinterpret_cast<unsigned short *>(reinterpret_cast<float *>(Wk) + vd_wk_blocks(n_pad, lda, 4) * (int64_t)NB * NB);
   const int64_t pl_lat = strideV * 2, sc_lat = strideV;
   float *const WA = A + wcol0;
   const ColMap<float> cm{0, 0, Tu, 0, 0, n_pad, (float *)nullptr, lda, strideA};
-  hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, st, (const float *)A, n_pad, lda, strideA, (int)naug_pad, scl, sc_lat);
+  hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, st, (const float *)A, n_pad, (int64_t)0, n_pad, lda, strideA, (int)naug_pad,
+                     scl, sc_lat, 0);
   hipLaunchKernelGGL((k_aug_scales<S>), dim3(q), dim3(64), 0, st, n_pad, scl, sc_lat);
   const int G0 = GMAX < m ? GMAX : m;
   hipLaunchKernelGGL((k_raw_planes<S>), dim3(Tu, G0, q), dim3(NTHREADS), 0, st, (const float *)A, lda, strideA, 0, cm, Praw, pl_lat, wcol0, (const float *)scl,
@@ -1569,6 +1580,13 @@ int64_t plmc_vd_blocks(int64_t n_pad, int64_t lda) { return plmc_vd_blocks_for(n
 int64_t plmc_vd_blocks_keep(int64_t n_pad, int64_t lda) {
   const int64_t ldb = (lda + plmc::NB - 1) / plmc::NB, m = n_pad / plmc::NB;
   return plmc_vd_blocks_for(n_pad, lda, 4) + ((m + plmc::GMAX - 1) / plmc::GMAX) * (3 * plmc::GMAX * ldb / 2);
+}
+// where potrf_impl / potrs_aug_kept put `scl` (4-byte elements): behind the m diagonal inverses, the group scratch (Wg, Vg2, Ph),
+// the bulk panel buffer, three plane buffers of 128 GMAX rows (two rolling + raw) and the two plane copies of Vgg
+int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) {
+  using namespace plmc;
+  const int64_t pl_buf = b3_elems<SplitB3>((int64_t)GMAX * NB, lda), vgp_elems = b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB);
+  return (n_pad / NB) * NB * NB + 4 * (int64_t)GMAX * NB * LDG + (int64_t)GMAX * NB * lda + (3 * pl_buf + 2 * vgp_elems) / 2;
 }
 // PLMC_SPLIT picks the arithmetic of the bulk fp32 products: 0 = fp32 MFMA everywhere, 3 = SplitB3, 2 (default) = SplitH2
 // where the caller supplies eigenvalue bounds (plmc_potrf_ex_f32), SplitB3 otherwise.

@@ -56,6 +56,7 @@ _PLAIN = {
     "plmc_vd_blocks": ([_L, _L], _L),
     "plmc_vd_blocks_for": ([_L, _L, _I], _L),
     "plmc_vd_blocks_keep": ([_L, _L], _L),
+    "plmc_split_scales_offset": ([_L, _L], _L),
     "plmc_max_dim": ([], _I),
     "plmc_qr_max": ([], _I),
     "plmc_last_error": ([], _c.c_char_p),

@@ -222,19 +222,31 @@ def test_sweep_is_deterministic_and_schedule_independent(eng, n, q, dtype, split
         eng.free_workspaces()
 
 
-def _schedule_independence_body(eng, n, q, dtype):
+@pytest.mark.parametrize("osc,noise", [((0.6, 0.9), (0.01, 0.2)), (None, (2.0, 6.0))], ids=["diag-below-1", "noise-2-6"])
+def test_sweep_is_schedule_independent_where_the_factor_leaves_the_input_range(eng, osc, noise):
+    """The same bit-identity at n = 8192, q = 8 on the fp32 default split, in the two regimes where the factor's diagonal
+    sqrt(pivot) leaves the range of the input's: outputscale + noise < 1 (sqrt(p) above the largest diagonal entry) and a noise
+    of 2-6 (sqrt(p) below the noise).  The fp16 scales come from the input's diagonal; the fused call (plmc_factorize_ex) once
+    scanned the first group's diagonal beside that group's chain, which rewrites it, so its scales -- and bits -- depended on
+    the timing there (tests/test_gpu_split_scales.py reads the scales themselves)."""
+    _schedule_independence_body(eng, 8192, 8, torch.float32, osc=osc, noise=noise)
+    eng.free_workspaces()
+
+
+def _schedule_independence_body(eng, n, q, dtype, osc=None, noise=(0.05, 0.5)):
     import os
     d = 8
     g = torch.Generator().manual_seed(5)
     X = (2 * torch.rand(n, d, generator=g, dtype=dtype) - 1).to(DEV)
     y = torch.randn(q, n, generator=g, dtype=dtype).to(DEV)
     ell = torch.linspace(0.4, 1.0, q, dtype=dtype)[:, None].expand(q, d).contiguous().to(DEV)
-    noise = torch.linspace(0.05, 0.5, q, dtype=dtype).to(DEV)
+    osc = None if osc is None else torch.linspace(osc[0], osc[1], q, dtype=dtype).to(DEV)
+    noise = torch.linspace(noise[0], noise[1], q, dtype=dtype).to(DEV)
     ws = eng.Workspace(n, q, 1, dtype, torch.device(DEV), True)
     it = torch.int32 if dtype == torch.float32 else torch.int64
 
     def factor():
-        eng.factorize("matern52", X, ell, None, noise, y.reshape(q, 1, n), ws)
+        eng.factorize("matern52", X, ell, osc, noise, y.reshape(q, 1, n), ws)
         torch.cuda.synchronize()
         return ws.A.view(it).clone(), ws.logdet.clone(), ws.info.clone()
 
