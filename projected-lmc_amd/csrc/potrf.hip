@@ -19,26 +19,23 @@
 //      launch instead of 2 G latency-bound ones;
 //   4. the trailing update C -= P^T P of depth 128 G (k_update) runs once per group.
 // Tiles of W are written (not accumulated) the first time they are touched, so W needs no memset.
-// The chain of the NEXT group runs beside the group panel / trailing update of the current one (potrf_impl).
+// The chain of the NEXT group runs beside the group panel / trailing update of the current one (Sweep::lookahead).
+// Host side: Sweep holds one sweep's launches, potrf_impl picks one of its two schedules (one stream / look-ahead on three).  The
+// per-latent scratch `Vd` (group scratch, panel and plane buffers, scales, diagonal K^-1 tiles) is laid out in ONE place,
+// VdLayout (vd_layout.hpp), which the sweep, the substitutions, the gradient and the C-ABI size queries all read.
 #include <stdlib.h>
-#include <vector>
 #include "api_common.hpp"
 #include "covariance.hpp"
 #include "diag_block.hpp"
 #include "bf3_engine.hpp"
 #include "chain_engine.hpp"
+#include "vd_layout.hpp"
 #include "../../include/plmc.h"
 
 namespace plmc {
 
-constexpr int GMAX = 8;                       // largest group (block rows; 16 was measured: 4 groups at n = 8192 pipeline too coarsely, 36.8 -> 38.8 ms at q = 8)
 // slabs of 16 rows the chain kernels keep in flight (tile_mainloop_burst): fp32 all 8 of K = 128, fp64 4 (registers)
 template <typename T> constexpr int CHAIN_BURST = sizeof(T) == 8 ? 4 : 8;
-constexpr int LDG = (GMAX + 1) * NB;          // leading dimension of the group scratch matrices (Wg, Vg, Ph): an odd number of
-                                              // 128-blocks, like lda -- a power-of-two row stride camps on a few L2 channels
-// per-latent scratch behind the m inverse diagonal blocks of Vd: Wg + two Vg (ping-pong), GMAX^2 blocks each
-// + the head panel buffer (GMAX^2 blocks) + the bulk panel buffer (GMAX block rows of lda / NB blocks)
-constexpr int VD_FIXED_BLOCKS = 4 * GMAX * (GMAX + 1);
 
 // Column-tile decoding shared by k_panel / k_update / k_gpanel.  Tiles along grid.x are laid out as
 //   [ U block columns u0 .. u0+nU-1 | aug tiles (Taug) | W block columns w0 .. w0+nW-1 ].
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(NTHREADS, TILE_MIN_WAVES<T>) void k_update(T *A, in
 // That list is a topological order of the dependency graph and a ticket is only ever held by a resident workgroup, so the
 // lowest unfinished operation can always run -- deadlock-free for ANY number of resident pool workgroups, with no assumption on
 // placement or dispatch order -- PROVIDED the q critical workgroups of the launch are resident: they are dispatched first
-// (lowest block indices) and the host keeps q <= CHAIN_QB per launch (potrf_impl) so that they always fit.  Every wait is
+// (lowest block indices) and the host keeps q <= CHAIN_QB per launch (Sweep::chain) so that they always fit.  Every wait is
 // bounded besides (chain_wait).  Dependencies = version counters per tile (`cnt`, per latent: 8 x 8 U tiles, 8 x 8 W tiles): tile
 // U(i,j) is final at version i + 1 (i updates + its panel solve / factorisation), W(i,c) at i - c + 1.  Every tile receives its
 // operations in the order of the launches, each the same K = 128 product: the results are bit-identical to the launch-per-step chain.
@@ -323,8 +320,8 @@ __global__ __launch_bounds__(CH_NT, 2) void k_chain(T *A, int64_t lda, int64_t s
   }
 }
 
-// ---- scales of the split engine's operand families (bf3_engine.hpp).  Per latent eight floats in the Vd scratch:
-enum { SC_SU = 0, SC_SW = 1, SC_RU = 2, SC_RW = 3, SC_SA = 4, SC_RA = 5, SC_N = 8, SC_TAG = 8 + 3 * 32 };   // SC_TAG: behind the scan partials (3 SCAN_PARTS)
+// ---- scales of the split engine's operand families (bf3_engine.hpp).  Per latent eight floats in the scale block of Vd (SC_*,
+// vd_layout.hpp):
 //   SU solved rows, U columns:      |U_kj| <= sqrt(A_jj) <= sqrt(D),  D = largest diagonal entry of the input
 //   SW solved rows, W columns, and the inverse triangle Vgg:   |W_ij| <= ||U^-1||_2 = 1 / sqrt(lambda_min)
 //   RU raw rows (before their panel solve), U columns: entries of Schur complements, <= D
@@ -339,7 +336,6 @@ enum { SC_SU = 0, SC_SW = 1, SC_RU = 2, SC_RW = 3, SC_SA = 4, SC_RA = 5, SC_N = 
 // of the rows, into 3 SCAN_PARTS floats behind the scales) and k_split_scales (grid (q): reduction of the partials + the scales).
 // The scan may be split by rows over several launches with disjoint partial slots (maxima and minima do not depend on the order):
 // rows row0 .. row1 - 1 into slots part0 .. part0 + gridDim.x - 1; a slot whose slice is empty holds the neutral values.
-constexpr int SCAN_PARTS = 32;
 __global__ __launch_bounds__(NTHREADS) void k_scale_scan(const float *__restrict__ A, int64_t n_pad, int64_t row0, int64_t row1, int64_t lda,
                                                          int64_t strideA, int naug_pad, float *__restrict__ sc, int64_t sc_stride, int part0) {
   __shared__ float r0[NTHREADS], r1[NTHREADS], r2[NTHREADS];
@@ -920,94 +916,91 @@ __global__ __launch_bounds__(WTMV_NT) void k_w_diag(const T *__restrict__ W, int
 }
 
 // ----------------------------------------------------------------------------------------------
+// One sweep's launches and the state they share: the problem, the Vd regions (VdLayout), the knob snapshot, the group boundaries
+// and the streams.  Each member queues one piece of work; the two schedules (one_stream, lookahead) put them in order, and the
+// substitutions (potrs_aug_at, potrs_aug_kept) reuse the members whose launches are theirs too.
 // S: split scheme of the bulk fp32 products (bf3_engine.hpp); void = none (fp64, or PLMC_SPLIT=0: MFMA of the element type
-// everywhere).  eig_lo: q lower bounds of the smallest eigenvalue (device), needed by SplitH2 only.
+// everywhere).
 template <typename T, class S>
-int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *Vd, double *logdet, int *info,
-               int with_inverse_arg, int q, const float *eig_lo, void *stream, const AssembleJob *job = nullptr) {
-  constexpr bool bf3 = !std::is_void<S>::value;
-  // with_inverse & 4 (split engine, with the inverse factor): KEEP the planes of the solved rows of every group instead of
-  // rolling over two buffers -- Vd then has plmc_vd_blocks_keep blocks per latent -- so that plmc_potrs_aug_kept_* can later run
-  // its updates on the split engine too (the eval-mode factorisation cache)
-  const bool keep = bf3 && (with_inverse_arg & 4) != 0 && (with_inverse_arg & 3) != 0;
-  const int with_inverse = with_inverse_arg & 3;
-  using SS = typename std::conditional<bf3, S, SplitB3>::type;       // a valid scheme type for the (dead) template arguments when bf3 is off
-  constexpr bool aug_fp32 = false;                                     // (the augmented columns have bounds too: k_split_scales)
-  PLMC_REQUIRE(A && Vd && logdet && info, "null pointer");
-  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && lda % NB == 0 && lda >= n_pad, "n_pad/lda must be multiples of NB");
-  const int64_t naug_pad = plmc_pad(naug);
-  PLMC_REQUIRE(naug >= 0 && n_pad + naug_pad + (with_inverse ? n_pad : 0) <= lda,
-               "lda too small for naug (+ the n_pad columns of the inverse factor)");
-  PLMC_REQUIRE(q > 0 && aligned16(A) && aligned16(Vd), "bad q or unaligned buffer");
-  const hipStream_t st = (hipStream_t)stream;
-  const int m = (int)(n_pad / NB);
-  const int Taug = (int)(naug_pad / NB);
-  const int64_t strideV = (keep ? plmc_vd_blocks_keep(n_pad, lda) : plmc_vd_blocks_for(n_pad, lda, (int)sizeof(T))) * (int64_t)NB * NB; // per latent
-  const int64_t wcol0 = n_pad + naug_pad;
-  const double nb = (double)NB, nb3 = nb * nb * nb, esz = sizeof(T);
-  // group scratch of latent 0 (batch stride strideV): the inverse triangle Wg and two transposed copies (ping-pong:
-  // the group panel of one group may still read its copy while the chain of the next group writes the other)
-  T *const Wg = Vd + (int64_t)m * NB * NB;
-  T *const Vg2[2] = {Wg + (int64_t)GMAX * NB * LDG, Wg + 2 * (int64_t)GMAX * NB * LDG};
-  T *const Ph = Wg + 3 * (int64_t)GMAX * NB * LDG;                      // panel buffer of the head columns (ld LDG)
-  T *const Pbulk = Ph + (int64_t)GMAX * NB * LDG;                       // panel buffer of the other columns (ld lda)
-  T *const Kd = Vd + strideV - (int64_t)m * NB * NB;                    // diagonal tiles of the accumulated K^-1: last m blocks
-  // split engine (fp32): plane buffers behind the bulk panel buffer -- the rolling two-group buffer of the solved panel rows,
-  // the raw rows of the next group, Vgg, and the scales of the operand families.  The offsets are those of the three-plane
-  // scheme whatever the scheme (plmc_vd_blocks_for sizes the scratch for it).
+struct Sweep {
+  static constexpr bool bf3 = !std::is_void<S>::value;
   static_assert(!bf3 || sizeof(T) == 4, "split schemes stand in for fp32 products");
-  const int64_t pl_buf = b3_elems<SplitB3>((int64_t)GMAX * NB, lda);    // 16-bit elements reserved per group of rows
-  unsigned short *const Pl0 = bf3 ? reinterpret_cast<unsigned short *>(Pbulk + (int64_t)GMAX * NB * lda) : nullptr;
-  unsigned short *const Praw = bf3 ? Pl0 + 2 * pl_buf : nullptr;         // raw rows of the group whose panel comes next (one group)
-  // planes of Vgg (128 GMAX x 128 GMAX), ping-pong like Vg2: the rest panel of group gi (helper stream H) may still read its
-  // copy while the chain stream transposes the triangle of group gi + 1 (nothing orders those two; with one copy a delayed
-  // rest panel -- other sweeps in flight on the device -- read half-overwritten planes)
-  const int64_t vgp_elems = b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB);
-  unsigned short *const VgP2[2] = {bf3 ? Praw + pl_buf : nullptr, bf3 ? Praw + pl_buf + vgp_elems : nullptr};
-  float *const scl = bf3 ? reinterpret_cast<float *>(Vd) + plmc_split_scales_offset(n_pad, lda) : nullptr;   // behind VgP2[1]: one block
-  // ... and, with the inverse factor, the full-height planes of W (n_pad columns per plane row) that plmc_kinv_grad_vd_* reads:
-  // written by the same epilogues that write the rolling buffer, so the K^-1 kernel needs no split pass over W
-  unsigned short *const Wk = (bf3 && with_inverse && vd_wk_blocks(n_pad, lda, (int)sizeof(T)) > 0)
-                                 ? reinterpret_cast<unsigned short *>(reinterpret_cast<float *>(scl) + (int64_t)NB * NB) : nullptr;
-  const int64_t pl_lat = strideV * (int64_t)(sizeof(T) / 2);            // latent stride in 16-bit elements
-  const int64_t sc_lat = strideV * (int64_t)sizeof(T) / 4;              // ... in floats
-  // block rows per group (the dev knob PLMC_GRP; as below).  A sweep that KEEPS its planes always works in groups of GMAX:
-  // plmc_vd_blocks_keep reserves one buffer per GMAX block rows and plmc_potrs_aug_kept walks them in groups of GMAX (a
-  // smaller PLMC_GRP would write more buffers than were reserved and hand the cached substitution planes of the wrong rows)
-  const int grp_rows = (!keep && knobs().grp > 0 && knobs().grp < GMAX) ? knobs().grp : GMAX;
-  // (keep: one buffer per group, behind the planes of W)
-  unsigned short *const Uk0 = keep ? reinterpret_cast<unsigned short *>(reinterpret_cast<float *>(Wk) + vd_wk_blocks(n_pad, lda, 4) * (int64_t)NB * NB) : nullptr;
-  auto planes = [&](int g0) -> unsigned short * {                       // buffer of the group that starts at block row g0
-    if (keep) return Uk0 + (int64_t)(g0 / grp_rows) * pl_buf;
-    return bf3 ? Pl0 + (int64_t)((g0 / grp_rows) & 1) * pl_buf : nullptr;
-  };
-  const bool kacc_on = with_inverse == 2;
-  T *const WA = with_inverse ? A + wcol0 : (T *)nullptr;                // inverse-factor columns of the factor buffer
+  static constexpr double nb = NB, nb3 = nb * nb * nb, esz = sizeof(T);
 
-  const Knobs &kn = knobs();                            // dev knobs: read once per process (api.hip)
-  const double hthr = kn.half_tiles;
-  const bool serial = kn.serial;
-  // With one or two latents the chain is the critical path: the bulk kernels then ask for LDS they do not use, which caps
-  // their occupancy -- 16 KB (three workgroups per CU) at q = 2, 20 KB (two per CU: 46 KB of LDS and half the register file
-  // stay free, so a chain workgroup is placed at once instead of waiting for a bulk workgroup to retire) at q = 1.
-  // q = 2: 11.4 -> 11.0 ms/step; q = 1: sweep 5.55 -> 5.30 (16 KB) -> 5.03 ms (20 KB); 26 KB and more lose again (5.36);
-  // with many latents the bulk is the bound and a cap costs 1-2 %.
-  const unsigned bulk_lds = (unsigned)(kn.bulk_lds >= 0 ? kn.bulk_lds : (q == 1 ? 20000 : (q == 2 ? 16000 : 0)));
+  T *A;
+  int64_t n_pad, lda, strideA, naug_pad, wcol0;   // wcol0: first inverse-factor column
+  int q, m, Taug, with_inverse;
+  bool keep;
+  const float *eig_lo = nullptr;                  // q lower bounds of the smallest eigenvalue (device), needed by SplitH2 only
+  double *logdet = nullptr;                       // outputs of finish()
+  int *info = nullptr;
+  // Vd regions of latent 0; the per-latent strides in elements, 16-bit plane elements and floats.  The split engine's regions are
+  // null unless it runs, the full-height planes of W also without the inverse factor, the kept buffers unless `keep`.
+  T *Vd, *Wg, *Vg2[2], *Ph, *Pbulk, *Kd;
+  unsigned short *Pl[2], *Praw, *VgP2[2], *Wk, *Uk;
+  float *scl;
+  int64_t strideV, pl_lat, sc_lat, uk_step;       // uk_step: 16-bit elements per kept buffer
+  T *WA;                                          // inverse-factor columns of the factor buffer (nullptr without them)
+  const Knobs &kn;                                // dev knobs: read once per process (api.hip)
+  double hthr;
+  unsigned bulk_lds;
+  int grp, ng, chain_pool;                        // block rows per group, groups
+  hipStream_t st, C = nullptr, H = nullptr, K = nullptr;
+  hipEvent_t e_entry = nullptr, e_v = nullptr, e_gh = nullptr, e_p = nullptr, e_hd = nullptr, e_tail = nullptr, e_doneC = nullptr,
+             e_doneH = nullptr, e_prev = nullptr, e_doneK = nullptr, e_sc = nullptr;
 
-  auto diag = [&](int r, int g0, hipStream_t s) {
+  Sweep(T *A_, int64_t n_pad_, int64_t lda_, int naug, int64_t wcol0_, int64_t strideA_, T *Vd_, int q_, int with_inverse_, bool keep_,
+        int grp_, unsigned bulk_lds_, hipStream_t st_)
+      : A(A_), n_pad(n_pad_), lda(lda_), strideA(strideA_), naug_pad(plmc_pad(naug)), wcol0(wcol0_), q(q_), m((int)(n_pad_ / NB)),
+        Taug((int)(plmc_pad(naug) / NB)), with_inverse(with_inverse_), keep(keep_), Vd(Vd_), kn(knobs()), hthr(kn.half_tiles),
+        bulk_lds(bulk_lds_), grp(grp_), st(st_) {
+    const VdLayout L(n_pad, lda, (int)sizeof(T), keep);
+    strideV = L.stride();
+    pl_lat = L.stride_u16();
+    sc_lat = L.stride_f32();
+    Wg = L.at<T>(Vd, L.wg);
+    Ph = L.at<T>(Vd, L.ph);
+    Pbulk = L.at<T>(Vd, L.pbulk);
+    Kd = L.at<T>(Vd, L.kd);
+    for (int b = 0; b < 2; ++b) {
+      Vg2[b] = L.at<T>(Vd, L.vg[b]);
+      Pl[b] = bf3 ? L.at<unsigned short>(Vd, L.pl[b]) : nullptr;
+      VgP2[b] = bf3 ? L.at<unsigned short>(Vd, L.vgp[b]) : nullptr;
+    }
+    Praw = bf3 ? L.at<unsigned short>(Vd, L.praw) : nullptr;
+    scl = bf3 ? L.at<float>(Vd, L.scl) : nullptr;
+    Wk = (bf3 && with_inverse) ? L.at<unsigned short>(Vd, L.wk) : nullptr;
+    Uk = keep ? L.at<unsigned short>(Vd, L.uk) : nullptr;
+    uk_step = L.plane_blocks * NB * NB * 2;
+    WA = with_inverse ? A + wcol0 : nullptr;
+    // Group boundaries.  Large groups divide the read-modify-write traffic of the trailing matrix by G and put
+    // G (G + 1) / 2 tile products into every group-panel strip; the chain of a group costs ~3 G small launches.
+    ng = (m + grp - 1) / grp;
+    chain_pool = kn.chain_nw > 0 ? (kn.chain_nw < 200 ? kn.chain_nw : 200) : (q >= 8 ? 80 : (q >= 4 ? 44 : (q >= 2 ? 36 : 31)));   // (PLMC_CHAIN_NW > 80: dev only)
+  }
+
+  int G0(int gi) const { return gi < ng ? gi * grp : m; }   // first block row of group gi (m beyond the last group)
+  // W part of a column map: the group scratch, shifted so that absolute block indices address it
+  ColMap<T> cm_tri(int g0, int u0, int nU, int w0, int nW) const {
+    return ColMap<T>{u0, nU, 0, w0, nW, n_pad, Wg - (int64_t)g0 * NB * LDG - (int64_t)g0 * NB, (int64_t)LDG, strideV};
+  }
+  // ... or the factor buffer's own columns (aug + inverse factor)
+  ColMap<T> cm_buf(int u0, int nU, int taug, int w0, int nW) const { return ColMap<T>{u0, nU, taug, w0, WA ? nW : 0, n_pad, WA, lda, strideA}; }
+  // split engine: plane buffer of the solved rows of the group that starts at block row g0
+  unsigned short *planes(int g0) const { return keep ? Uk + (int64_t)(g0 / grp) * uk_step : Pl[(g0 / grp) & 1]; }
+
+  // tiles of the diagonal-block outputs that k_diag leaves alone (they are read as parts of full 128 x 128 operands), and the chain
+  // kernel's control words in the pad column of Wg
+  void clear() {
+    hipLaunchKernelGGL(k_zero_diag_out<T>, dim3(m > GMAX ? m : GMAX, q), dim3(NTHREADS), 0, st, Vd, strideV, m, Wg, (int64_t)LDG,
+                       strideV, (int64_t)NB * LDG + NB, GMAX, VdLayout::CTR);
+  }
+  void diag(int r, int g0, hipStream_t s) {
     ProfScope ps(PK_DIAG, s, q * (2.0 / 3.0) * nb3, q * 3.0 * nb * nb * esz);
     T *wout = Wg + (int64_t)(r - g0) * NB * LDG + (int64_t)(r - g0) * NB;
     hipLaunchKernelGGL((k_diag<T>), dim3(q), dim3(DIAG_NT), 0, s, A, lda, strideA, r, Vd, strideV, wout, (int64_t)LDG, strideV);
-  };
-  // W part of a column map: the group scratch, shifted so that absolute block indices address it
-  auto cm_tri = [&](int g0, int u0, int nU, int w0, int nW) {
-    return ColMap<T>{u0, nU, 0, w0, nW, n_pad, Wg - (int64_t)g0 * NB * LDG - (int64_t)g0 * NB, (int64_t)LDG, strideV};
-  };
-  // ... or the factor buffer's own columns (aug + inverse factor)
-  auto cm_buf = [&](int u0, int nU, int taug, int w0, int nW) {
-    return ColMap<T>{u0, nU, taug, w0, WA ? nW : 0, n_pad, WA, lda, strideA};
-  };
-  auto panel = [&](int r, const ColMap<T> &cm, hipStream_t s) {
+  }
+  void panel(int r, const ColMap<T> &cm, hipStream_t s) {
     const int nt = cm.nU + cm.Taug + cm.nW;
     if (nt == 0) return;
     // algorithmic: triangular solve of nt*NB columns with a 128 x 128 factor = nb^2 flops per column
@@ -1018,14 +1011,14 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
       hipLaunchKernelGGL((k_panel<T, 2>), dim3(nt, q, 2), dim3(NTHREADS), 0, s, A, lda, strideA, r, cm, Vd, strideV);
     else
       hipLaunchKernelGGL((k_panel<T, 4>), dim3(nt, q, 1), dim3(NTHREADS), 0, s, A, lda, strideA, r, cm, Vd, strideV);
-  };
+  }
   // cls: profiler class of the launch -- PK_TRAIL (the big trailing update), PK_TRAIL_HEAD (look-ahead updates of the next
   // group's rows: `crit` = the triangle on the chain stream, else the other columns on the second helper stream),
   // PK_TRAIL_ROW (rank-128 update inside a group's triangle)
   // raw_end (split engine): block rows below it are the next group's -- this launch is their last update and also writes
   // their planes (Praw) for the next group panel
-  auto update = [&](int ib0, int nrows, int r_lo, int r_hi, const ColMap<T> &cm, hipStream_t s, int cls, int skip_ib = 0,
-                    int skip_jb = 0, bool crit = false, int raw_end = 0) {
+  void update(int ib0, int nrows, int r_lo, int r_hi, const ColMap<T> &cm, hipStream_t s, int cls, int skip_ib = 0, int skip_jb = 0,
+              bool crit = false, int raw_end = 0) {
     const int Cn = cm.nU + cm.Taug + cm.nW;
     if (nrows <= 0 || Cn == 0) return;
     const double depth = (r_hi - r_lo + 1) * nb, nr = (double)nrows;
@@ -1048,129 +1041,78 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
     const double flops = 2.0 * nb * nb * (depth * (tilesU - halfU) + nr * (depth * cm.Taug + depthW));
     const double bytes = (2.0 * (tilesU + nr * (cm.Taug + cm.nW)) - nr * nfirst) * nb * nb * esz;
     ProfScope ps(cls, s, q * flops, q * bytes);
-    // launches with few tiles run on 64-row half tiles: twice the workgroups
     // Split engine: which engine a tile goes through must not depend on the schedule (bit-identical results with and
     // without the look-ahead): every tail / head tile takes the split engine on macro tiles, the next group's triangle
-    // (U1; `crit`) and the chain stay on the fp32 MFMAs -- and so do the augmented columns under SplitH2 (aug_fp32)
-    const bool use_bf3 = bf3 && (cls == PK_TRAIL || cls == PK_TRAIL_HEAD);
-    const unsigned dyn = (cls == PK_TRAIL || (cls == PK_TRAIL_HEAD && !crit)) ? bulk_lds : 0u;
-    auto fp32_launch = [&](const ColMap<T> &c) {
-      const int cn = c.nU + c.Taug + c.nW;
-      if (cn == 0) return;
-      const bool half = !use_bf3 && cls != PK_TRAIL && (double)cn * nrows * q <= hthr;
-      const dim3 grid(cn, half ? 2 * nrows : nrows, q);
-#define PLMC_UPD(ROLE, MT) \
-  hipLaunchKernelGGL((k_update<T, ROLE, MT>), grid, dim3(NTHREADS), dyn, s, A, lda, strideA, ib0, r_lo, r_hi, c, skip_ib, skip_jb)
-      if (cls == PK_TRAIL_ROW) { if (half && q <= 2 && r_hi == r_lo) PLMC_UPD(4, 2); else if (half) PLMC_UPD(1, 2); else PLMC_UPD(1, 4); }
-      else if (cls == PK_TRAIL_HEAD && crit) { if (half) PLMC_UPD(2, 2); else PLMC_UPD(2, 4); }
-      else if (cls == PK_TRAIL_HEAD) { if (half) PLMC_UPD(3, 2); else PLMC_UPD(3, 4); }
-      else PLMC_UPD(0, 4);
-#undef PLMC_UPD
-    };
+    // (U1; `crit`) and the chain stay on the fp32 MFMAs
     if constexpr (bf3) {
-      if (use_bf3) {
-        ColMap<T> cb = cm, ca = cm;
-        if (aug_fp32) { cb.Taug = 0; ca.nU = 0; ca.nW = 0; }
-        const int cnb = cb.nU + cb.Taug + cb.nW;
+      if (cls == PK_TRAIL || cls == PK_TRAIL_HEAD) {
+        const dim3 grid(Cn, (nrows + 1) / 2, q);
         const unsigned short *pl = planes(r_lo);
-        const dim3 gridb(cnb, (nrows + 1) / 2, q);
-        if (cnb > 0) {
-          if (cls == PK_TRAIL)
-            hipLaunchKernelGGL((k_update_bf3<SS, 0>), gridb, dim3(B3_NT), 0, s, A, lda, strideA, ib0, nrows, r_lo, r_hi, cb, skip_ib, skip_jb, pl, pl_lat,
-                               wcol0, Praw, pl_lat, raw_end, (const float *)scl, sc_lat, Wk, pl_lat);
-          else if (crit)
-            hipLaunchKernelGGL((k_update_bf3<SS, 2>), gridb, dim3(B3_NT), 0, s, A, lda, strideA, ib0, nrows, r_lo, r_hi, cb, skip_ib, skip_jb, pl, pl_lat,
-                               wcol0, Praw, pl_lat, raw_end, (const float *)scl, sc_lat, Wk, pl_lat);
-          else
-            hipLaunchKernelGGL((k_update_bf3<SS, 3>), gridb, dim3(B3_NT), 0, s, A, lda, strideA, ib0, nrows, r_lo, r_hi, cb, skip_ib, skip_jb, pl, pl_lat,
-                               wcol0, Praw, pl_lat, raw_end, (const float *)scl, sc_lat, Wk, pl_lat);
-        }
-        if (aug_fp32) fp32_launch(ca);
+#define PLMC_UPD3(ROLE)                                                                                                                    \
+  hipLaunchKernelGGL((k_update_bf3<S, ROLE>), grid, dim3(B3_NT), 0, s, A, lda, strideA, ib0, nrows, r_lo, r_hi, cm, skip_ib, skip_jb, pl, \
+                     pl_lat, wcol0, Praw, pl_lat, raw_end, (const float *)scl, sc_lat, Wk, pl_lat)
+        if (cls == PK_TRAIL) PLMC_UPD3(0);
+        else if (crit) PLMC_UPD3(2);
+        else PLMC_UPD3(3);
+#undef PLMC_UPD3
         return;
       }
     }
-    fp32_launch(cm);
-  };
-  // head != 0: the few columns of the next group (panel buffer Ph), on the chain stream
-  auto gpanel = [&](int g0, int G, const ColMap<T> &cm, const T *Vg, hipStream_t s, int head) {
+    // launches with few tiles run on 64-row half tiles: twice the workgroups
+    const bool half = cls != PK_TRAIL && (double)Cn * nrows * q <= hthr;
+    const unsigned dyn = (cls == PK_TRAIL || (cls == PK_TRAIL_HEAD && !crit)) ? bulk_lds : 0u;
+    const dim3 grid(Cn, half ? 2 * nrows : nrows, q);
+#define PLMC_UPD(ROLE, MT) \
+  hipLaunchKernelGGL((k_update<T, ROLE, MT>), grid, dim3(NTHREADS), dyn, s, A, lda, strideA, ib0, r_lo, r_hi, cm, skip_ib, skip_jb)
+    if (cls == PK_TRAIL_ROW) { if (half && q <= 2 && r_hi == r_lo) PLMC_UPD(4, 2); else if (half) PLMC_UPD(1, 2); else PLMC_UPD(1, 4); }
+    else if (cls == PK_TRAIL_HEAD && crit) { if (half) PLMC_UPD(2, 2); else PLMC_UPD(2, 4); }
+    else if (cls == PK_TRAIL_HEAD) { if (half) PLMC_UPD(3, 2); else PLMC_UPD(3, 4); }
+    else PLMC_UPD(0, 4);
+#undef PLMC_UPD
+  }
+  // group panel of the rows g0 .. g0 + G - 1 with Vgg from Vg2[buf] (split engine: VgP2[buf]); head != 0: the few columns of the
+  // next group (fp32 / fp64 engine: panel buffer Ph), on the chain stream
+  void gpanel(int g0, int G, const ColMap<T> &cm, int buf, hipStream_t s, int head) {
     const int nt = cm.nU + cm.Taug + cm.nW;
     if (nt == 0) return;
     const double prods = G * (G + 1) / 2.0;               // 128-deep tile products per column strip
     ProfScope ps(PK_GPANEL, s, q * (double)nt * prods * 2.0 * nb3, q * (double)nt * (prods + G) * nb * nb * esz);
-    // fp32 / fp64 engine: out of place into a panel buffer + copy
-    auto fp32_panel = [&](const ColMap<T> &c) {
-      const int ct = c.nU + c.Taug + c.nW;
-      if (ct == 0) return;
+    if constexpr (bf3) {                                   // split engine, in place, planes from the epilogue (k_gpanel_bf3)
+      const int nm = (G + 1) / 2;
+      // (round 4: one macro row per workgroup, heaviest first, instead of heavy + light pairs for the rest panel too: 17.86-17.89
+      // against 17.82-17.84 ms/step at q = 8, level at q = 4 -- the pairing stays)
+      hipLaunchKernelGGL((k_gpanel_bf3<S>), dim3(nt, head ? nm : (nm + 1) / 2, q), dim3(B3_NT), 0, s, A, lda, strideA, g0, G, cm,
+                         (const unsigned short *)VgP2[buf], pl_lat, (const unsigned short *)Praw, pl_lat, planes(g0), pl_lat, wcol0,
+                         (const float *)scl, sc_lat, head ? 0 : 1, Wk, pl_lat);
+    } else {                                               // fp32 / fp64 engine: out of place into a panel buffer + copy
       T *Pb = head ? Ph : Pbulk;
       const int64_t ldp = head ? (int64_t)LDG : lda;
       if (head)
-        hipLaunchKernelGGL((k_gpanel_rows<T, 1>), dim3(ct, 2 * G, q), dim3(NTHREADS), 0, s, (const T *)A, lda, strideA, g0, G, c, Vg, (int64_t)LDG,
-                           strideV, Pb, ldp, strideV);
+        hipLaunchKernelGGL((k_gpanel_rows<T, 1>), dim3(nt, 2 * G, q), dim3(NTHREADS), 0, s, (const T *)A, lda, strideA, g0, G, cm,
+                           (const T *)Vg2[buf], (int64_t)LDG, strideV, Pb, ldp, strideV);
       else
-        hipLaunchKernelGGL((k_gpanel_rows<T, 0>), dim3(ct, (G + 1) / 2, q), dim3(NTHREADS), bulk_lds, s, (const T *)A, lda, strideA, g0, G, c, Vg,
-                           (int64_t)LDG, strideV, Pb, ldp, strideV);
-      hipLaunchKernelGGL((k_gpanel_copy<T>), dim3(ct, G, q), dim3(NTHREADS), 0, s, A, lda, strideA, g0, c, (const T *)Pb, ldp, strideV);
-    };
-    if constexpr (bf3) {                                   // split engine, in place, planes from the epilogue (k_gpanel_bf3)
-      ColMap<T> cb = cm, ca = cm;
-      if (aug_fp32) { cb.Taug = 0; ca.nU = 0; ca.nW = 0; }
-      const int nb_ = cb.nU + cb.Taug + cb.nW, nm = (G + 1) / 2;
-      // (round 4: one macro row per workgroup, heaviest first, instead of heavy + light pairs for the rest panel too: 17.86-17.89
-      // against 17.82-17.84 ms/step at q = 8, level at q = 4 -- the pairing stays)
-      if (nb_ > 0)
-        hipLaunchKernelGGL((k_gpanel_bf3<SS>), dim3(nb_, head ? nm : (nm + 1) / 2, q), dim3(B3_NT), 0, s, A, lda, strideA, g0, G, cb,
-                           (const unsigned short *)VgP2[Vg == Vg2[1]], pl_lat, (const unsigned short *)Praw, pl_lat, planes(g0), pl_lat, wcol0,
-                           (const float *)scl, sc_lat, head ? 0 : 1, Wk, pl_lat);
-      if (aug_fp32) fp32_panel(ca);
-      return;
+        hipLaunchKernelGGL((k_gpanel_rows<T, 0>), dim3(nt, (G + 1) / 2, q), dim3(NTHREADS), bulk_lds, s, (const T *)A, lda, strideA, g0, G, cm,
+                           (const T *)Vg2[buf], (int64_t)LDG, strideV, Pb, ldp, strideV);
+      hipLaunchKernelGGL((k_gpanel_copy<T>), dim3(nt, G, q), dim3(NTHREADS), 0, s, A, lda, strideA, g0, cm, (const T *)Pb, ldp, strideV);
     }
-    fp32_panel(cm);
-  };
-
-  // whole-sweep bracket on the caller's stream (the per-kernel records of overlapped kernels add up to
-  // more than the wall time once the look-ahead runs the chain beside the trailing update)
-  const double npd = (double)n_pad;
-  ProfScope whole(PK_SWEEP, st, q * (with_inverse == 2 ? 3.0 : (with_inverse ? 2.0 : 1.0)) * npd * npd * npd / 3.0, 0.0);
-  // tiles of the diagonal-block outputs that k_diag leaves alone (they are read as parts of full 128 x 128 operands)
-  hipLaunchKernelGGL(k_zero_diag_out<T>, dim3(m > GMAX ? m : GMAX, q), dim3(NTHREADS), 0, st, Vd, strideV, m, Wg, (int64_t)LDG,
-                     strideV, (int64_t)NB * LDG + NB, GMAX, (int64_t)GMAX * NB);    // (+ the chain kernel's counters in the pad column of Wg)
+  }
   // scan of rows row0 .. row1 - 1 into the partial slots part0 .. part0 + parts - 1 (two-plane split only)
-  auto scan = [&](hipStream_t s, int64_t row0, int64_t row1, int part0, int parts) {
+  void scan(hipStream_t s, int64_t row0, int64_t row1, int part0, int parts) {
     if constexpr (bf3) {
-      if (SS::NPL == 2)
+      if (S::NPL == 2)
         hipLaunchKernelGGL(k_scale_scan, dim3(parts, q), dim3(NTHREADS), 0, s, (const float *)A, n_pad, row0, row1, lda, strideA, (int)naug_pad, scl,
                            sc_lat, part0);
     }
-  };
-  auto split_scales = [&](hipStream_t s) {                // scales of the operand families (SplitB3: ones), before anything splits
-    if constexpr (bf3) hipLaunchKernelGGL((k_split_scales<SS>), dim3(q), dim3(64), 0, s, n_pad, eig_lo, scl, sc_lat);
-  };
-  // A sweep that also assembles (plmc_factorize_ex_*, `job`) with the look-ahead on: only the first group's own block triangle is written
-  // in front of the chain, everything else rides on the helper stream H beside the first group's chain (the first consumer, the
-  // transpose + head panel of group 0, waits for it: e_sc).  So does the scan for the scales -- but only of the rows below the first
-  // group: chain(0) overwrites the diagonal of the first group's rows (Schur updates, then U_ii) while H runs, so those rows are
-  // scanned on the caller's stream in front of the chain, into slots of their own (the scales are those of the input matrix, as in
-  // the two-call path, whatever the timing).  `fused_la` is settled below, once the look-ahead is known to run.
-  auto finish = [&](hipStream_t s) {
-    hipLaunchKernelGGL(k_logdet<T>, dim3(q), dim3(NTHREADS), 0, s, (const T *)A, n_pad, lda, strideA, logdet, info,
-                       (const T *)(Wg + (int64_t)LDG + (int64_t)GMAX * NB), strideV, q);    // (the chain kernel's abort words: one per launch, at its first latent)
-    return launch_status("potrf_impl");
-  };
-  // Group boundaries.  Large groups divide the read-modify-write traffic of the trailing matrix by G and put
-  // G (G + 1) / 2 tile products into every group-panel strip; the chain of a group costs ~3 G small launches.
-  std::vector<int> gb;                                    // group boundaries: gb[i] .. gb[i+1]
-  {
-    const int big = grp_rows;
-    gb.push_back(0);
-    for (int r = 0; r < m;) {
-      int g = big;
-      if (r + g > m) g = m - r;
-      r += g;
-      gb.push_back(r);
-    }
   }
-  const int ng = (int)gb.size() - 1;
-  auto G0 = [&](int gi) { return gb[gi < ng ? gi : ng]; };   // first block row of group gi (m beyond the last group)
+  void split_scales(hipStream_t s) {                       // scales of the operand families (SplitB3: ones), before anything splits
+    if constexpr (bf3) hipLaunchKernelGGL((k_split_scales<S>), dim3(q), dim3(64), 0, s, n_pad, eig_lo, scl, sc_lat);
+  }
+  // log det and the pivot / abort check (the chain kernel's abort words: one per launch, at its first latent)
+  int finish(hipStream_t s) {
+    hipLaunchKernelGGL(k_logdet<T>, dim3(q), dim3(NTHREADS), 0, s, (const T *)A, n_pad, lda, strideA, logdet, info,
+                       (const T *)(Wg + VdLayout::CTL), strideV, q);
+    return launch_status("potrf_impl");
+  }
 
   // ---- the pieces of one group gi (rows g0 .. g1-1; next group g1 .. g2-1; the one after g2 .. g3-1)
   // chain: the group's diagonal triangle + its inverse triangle in Wg
@@ -1178,9 +1120,8 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // and group of 8 (12-16 us each).  The pool is sized to keep up with the critical workgroups' ~40 us per block row without
   // holding more CUs than that (a chain workgroup does not fit on a CU beside a 228-register bulk workgroup); PLMC_CHAIN_NW
   // overrides, PLMC_CHAIN=0 brings the launches back.
-  constexpr int CHAIN_QB = 32;
-  const int chain_pool = kn.chain_nw > 0 ? (kn.chain_nw < 200 ? kn.chain_nw : 200) : (q >= 8 ? 80 : (q >= 4 ? 44 : (q >= 2 ? 36 : 31)));   // (PLMC_CHAIN_NW > 80: dev only)
-  auto chain = [&](int gi, hipStream_t s) {
+  static constexpr int CHAIN_QB = 32;
+  void chain(int gi, hipStream_t s) {
     const int g0 = G0(gi), g1 = G0(gi + 1);
     if (kn.chain) {
       const int G = g1 - g0;
@@ -1216,104 +1157,111 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
       //    q = 1; step 7.35 vs 7.35 ms at q = 1, 11.4 vs 10.9 at q = 2, 37.8 vs 36.8 at q = 8).
       if (r + 1 < g1) update(r + 1, g1 - r - 1, r, r, cm_tri(g0, r + 1, g1 - r - 1, g0, r + 1 - g0), s, PK_TRAIL_ROW);
     }
-  };
-  auto vtrans = [&](int gi, hipStream_t s) {
+  }
+  // Vgg of group gi into Vg2[gi & 1] (split engine: and its planes, zero blocks included -- one workgroup per block of the
+  // GMAX x GMAX grid -- into VgP2[gi & 1]), from the inverse triangle in Wg, which is also copied into the W columns of the factor
+  // buffer; from_w (a substitution): from the triangle already in those W columns
+  void vtrans(int gi, hipStream_t s, bool from_w = false) {
     const int g0 = G0(gi), G = G0(gi + 1) - g0;
-    T *wo = WA ? WA + (int64_t)g0 * NB * lda + (int64_t)g0 * NB : (T *)nullptr;
-    // (split engine: also the planes of Vgg, zero blocks included -- one workgroup per block of the GMAX x GMAX grid)
-    hipLaunchKernelGGL((k_vtrans<T, S>), dim3(bf3 ? GMAX * GMAX : G * (G + 1) / 2, q), dim3(NTHREADS), 0, s, (const T *)Wg, (int64_t)LDG, strideV,
-                       strideV, Vg2[gi & 1], G, wo, lda, strideA, VgP2[gi & 1], pl_lat, (const float *)scl, sc_lat);
-  };
+    T *const tri = WA ? WA + (int64_t)g0 * NB * lda + (int64_t)g0 * NB : (T *)nullptr;
+    hipLaunchKernelGGL((k_vtrans<T, S>), dim3(bf3 ? GMAX * GMAX : G * (G + 1) / 2, q), dim3(NTHREADS), 0, s, from_w ? (const T *)tri : (const T *)Wg,
+                       from_w ? lda : (int64_t)LDG, from_w ? strideA : strideV, strideV, Vg2[gi & 1], G, from_w ? (T *)nullptr : tri, lda, strideA,
+                       VgP2[gi & 1], pl_lat, (const float *)scl, sc_lat);
+  }
   // split engine: planes of the group's inverse triangle (read back from the W columns k_vtrans wrote; any stream behind it)
-  auto wtri_planes = [&](int gi, hipStream_t s) {
+  void wtri_planes(int gi, hipStream_t s) {
     if constexpr (bf3) {
       if (!WA) return;
       const int g0 = G0(gi), G = G0(gi + 1) - g0;
-      hipLaunchKernelGGL((k_wtri_planes<SS>), dim3(G * (G + 1) / 2, q), dim3(NTHREADS), 0, s, (const float *)WA, lda, strideA, g0, (const float *)scl, sc_lat, Wk, pl_lat,
-                         n_pad);
+      hipLaunchKernelGGL((k_wtri_planes<S>), dim3(G * (G + 1) / 2, q), dim3(NTHREADS), 0, s, (const float *)WA, lda, strideA, g0, (const float *)scl,
+                         sc_lat, Wk, pl_lat, n_pad);
     }
-  };
-  // split engine: planes of the first group's raw rows (columns of the bulk panel: everything right of the second group + aug)
-  auto raw_planes0 = [&](hipStream_t s, int u0) {
+  }
+  // split engine: planes of the first group's raw rows, columns `cm` (the sweep: those of the bulk panel -- everything right of the
+  // second group + aug)
+  void raw_planes0(hipStream_t s, const ColMap<T> &cm) {
     if constexpr (bf3) {
-      const int g1 = G0(1);
-      const ColMap<float> cm = cm_buf(u0, m - u0, aug_fp32 ? 0 : Taug, 0, 0);
       const int nt = cm.nU + cm.Taug + cm.nW;
       if (nt > 0)
-        hipLaunchKernelGGL((k_raw_planes<SS>), dim3(nt, g1, q), dim3(NTHREADS), 0, s, (const float *)A, lda, strideA, 0, cm, Praw, pl_lat, wcol0,
+        hipLaunchKernelGGL((k_raw_planes<S>), dim3(nt, G0(1), q), dim3(NTHREADS), 0, s, (const float *)A, lda, strideA, 0, cm, Praw, pl_lat, wcol0,
                            (const float *)scl, sc_lat);
     }
-  };
-
-  auto kacc = [&](int gi, hipStream_t s) {
-    if (!kacc_on) return;
+  }
+  void kacc(int gi, hipStream_t s) {
+    if (with_inverse != 2) return;
     const int g0 = G0(gi), g1 = G0(gi + 1);
     const int nt = g1 * (g1 + 1) / 2;
     double fl = 0.0;
     for (int jb = 0; jb < g1; ++jb) fl += (jb + 0.5) * 2.0 * nb * nb * (double)(g1 - (jb >= g0 ? jb : g0)) * nb;   // diagonal tiles: half
     ProfScope ps(PK_KACC, s, q * fl, q * (2.0 * nt - (double)(g1 - g0) * (g0 + g1 + 1) / 2.0) * nb * nb * esz);
     if constexpr (bf3) {
-      hipLaunchKernelGGL((k_kacc_bf3<SS>), dim3(g1, (g1 + 1) / 2, q), dim3(B3_NT), 0, s, (float *)A, lda, strideA, (float *)Kd, strideV,
+      hipLaunchKernelGGL((k_kacc_bf3<S>), dim3(g1, (g1 + 1) / 2, q), dim3(B3_NT), 0, s, (float *)A, lda, strideA, (float *)Kd, strideV,
                          (const unsigned short *)Wk, pl_lat, n_pad, g0, g1, (const float *)scl, sc_lat);
     } else {
       hipLaunchKernelGGL((k_kacc<T>), dim3(nt, q), dim3(NTHREADS), bulk_lds, s, A, lda, strideA, (const T *)WA, lda, strideA, Kd, strideV, g0, g1);
     }
-  };
-
-  // the helper streams and ordering events of THIS caller stream (api.hip: sweeps from different streams may overlap)
-  if (!serial) bind_sweep_ctx(st, 8);
-  // PLMC_BULK_STREAMS=1: the group panel of the other columns and the head rows ride on the caller's stream, in front of the tail
-  hipStream_t C = serial ? nullptr : side_stream(), H = serial ? nullptr : (kn.bulk_streams == 1 ? st : side_stream(1));
-  // the K^-1 accumulation rides on the caller's stream behind the tail (e_tail is recorded before it, so nothing on the
-  // critical path waits for it).  A stream of its own shared a hardware queue with one of the others (HIP maps streams
-  // onto four hardware queues; with the gradient stream of the Python layer this library already uses four) and
-  // serialised the chain behind bulk launches: sweep + accumulation took exactly the sum of the two.
-  hipEvent_t e_entry = sync_event(0), e_v = sync_event(1), e_gh = sync_event(2), e_p = sync_event(3), e_hd = sync_event(4),
-             e_tail = sync_event(5), e_doneC = sync_event(6), e_doneH = sync_event(7), e_prev = sync_event(8);
-  // split engine: the accumulation reads the full-height planes of W (rows of group gi: final behind e_p, never rewritten) and
-  // is pure filler, so it gets a (low-priority) stream of its own
-  hipStream_t K = (serial || !kacc_on || !bf3) ? nullptr : side_stream(2);
-  hipEvent_t e_doneK = sync_event(11);
-  if (!e_doneK) K = nullptr;
-  hipEvent_t e_sc = sync_event(12);
-  const bool la = C && H && e_entry && e_v && e_gh && e_p && e_hd && e_tail && e_doneC && e_doneH && e_prev && ng > 2;
-  const bool fused_la = la && job && e_sc;
-  if (job && !fused_la) {                                // no overlap to be had: the whole matrix first, as the separate call would
-    const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, st);
-    if (rc != 0) return rc;
   }
-  if (!fused_la) {
+
+  // The helper streams and ordering events of THIS caller stream (api.hip: sweeps from different streams may overlap).  True when
+  // the look-ahead can run: both helper streams and its nine events exist, and the sweep has more than two groups.
+  bool bind_streams() {
+    if (!kn.serial) bind_sweep_ctx(st, 8);
+    // PLMC_BULK_STREAMS=1: the group panel of the other columns and the head rows ride on the caller's stream, in front of the tail
+    C = kn.serial ? nullptr : side_stream();
+    H = kn.serial ? nullptr : (kn.bulk_streams == 1 ? st : side_stream(1));
+    // the K^-1 accumulation rides on the caller's stream behind the tail (e_tail is recorded before it, so nothing on the
+    // critical path waits for it).  A stream of its own shared a hardware queue with one of the others (HIP maps streams
+    // onto four hardware queues; with the gradient stream of the Python layer this library already uses four) and
+    // serialised the chain behind bulk launches: sweep + accumulation took exactly the sum of the two.
+    hipEvent_t *const ev[] = {&e_entry, &e_v, &e_gh, &e_p, &e_hd, &e_tail, &e_doneC, &e_doneH, &e_prev};
+    bool la = C && H && ng > 2;
+    for (int i = 0; i < 9; ++i) la = (*ev[i] = sync_event(i)) && la;
+    // split engine: the accumulation reads the full-height planes of W (rows of group gi: final behind e_p, never rewritten) and
+    // is pure filler, so it gets a (low-priority) stream of its own
+    K = (kn.serial || with_inverse != 2 || !bf3) ? nullptr : side_stream(2);
+    e_doneK = sync_event(11);
+    if (!e_doneK) K = nullptr;
+    e_sc = sync_event(12);
+    return la;
+  }
+
+  // the whole matrix (a fused call's assembly) and the scales of the split engine, on the caller's stream in front of the sweep
+  int inputs(const AssembleJob *job) {
+    if (job) {                                             // no overlap to be had: the whole matrix first, as the separate call would
+      const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, st);
+      if (rc != 0) return rc;
+    }
     scan(st, 0, n_pad, 0, SCAN_PARTS);
     split_scales(st);
+    return 0;
   }
-  if (!la) {
-    // one stream: chain -> transpose -> group panel over every column -> trailing update of every row below
-    // split engine: which engine a tile goes through must not depend on the schedule -- the same launches as under the look-ahead
-    // (head panel, rest panel, tail, U1), one after the other
-    raw_planes0(st, G0(1));
+
+  // One stream: chain -> transpose -> group panel over every column -> trailing update of every row below.
+  // Split engine: which engine a tile goes through must not depend on the schedule -- the same launches as under the look-ahead
+  // (head panel, rest panel, tail, U1), one after the other
+  int one_stream(const AssembleJob *job) {
+    const int rc = inputs(job);
+    if (rc != 0) return rc;
+    raw_planes0(st, cm_buf(G0(1), m - G0(1), Taug, 0, 0));
     for (int gi = 0; gi < ng; ++gi) {
-      const int g0 = G0(gi), g1 = G0(gi + 1);
+      const int g0 = G0(gi), g1 = G0(gi + 1), g2 = G0(gi + 2);
       chain(gi, st);
       vtrans(gi, st);
       wtri_planes(gi, st);
       if (bf3) {
-        const int g2 = G0(gi + 2);
-        gpanel(g0, g1 - g0, cm_buf(g1, g2 - g1, 0, 0, 0), Vg2[gi & 1], st, 1);
-        gpanel(g0, g1 - g0, cm_buf(g2, m - g2, Taug, 0, g0), Vg2[gi & 1], st, 0);
-      } else {
-        gpanel(g0, g1 - g0, cm_buf(g1, m - g1, Taug, 0, g0), Vg2[gi & 1], st, 0);
-      }
-      if (bf3) {
-        const int g2 = G0(gi + 2);
+        gpanel(g0, g1 - g0, cm_buf(g1, g2 - g1, 0, 0, 0), gi & 1, st, 1);
+        gpanel(g0, g1 - g0, cm_buf(g2, m - g2, Taug, 0, g0), gi & 1, st, 0);
         update(g1, m - g1, g0, g1 - 1, cm_buf(g1, m - g1, Taug, 0, g1), st, PK_TRAIL, g2, g2, false, g2);
         update(g1, g2 - g1, g0, g1 - 1, cm_buf(g1, g2 - g1, 0, 0, 0), st, PK_TRAIL_HEAD, 0, 0, true);
       } else {
+        gpanel(g0, g1 - g0, cm_buf(g1, m - g1, Taug, 0, g0), gi & 1, st, 0);
         update(g1, m - g1, g0, g1 - 1, cm_buf(g1, m - g1, Taug, 0, g1), st, PK_TRAIL);
       }
       kacc(gi, st);
     }
     return finish(st);
   }
+
   // Look-ahead on three streams.  With R0 = the rows of group gi, R1 = the next group, R2 = the one after:
   //   C (helper, high priority; latency-bound): chain(gi) -> vtrans(gi) -> [e_v] -> (wait e_hd(gi-1)) gpanel_head(gi):
   //       panel columns R1 -> [e_gh] -> (wait e_tail(gi-1)) U1(gi): update of the next triangle R1 x R1 -> chain(gi+1) ...
@@ -1326,71 +1274,118 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // gpanel_rest(gi) read: by then C has waited for e_hd(gi), recorded behind it.  U1 / head / tail touch disjoint
   // tiles; every tile receives its updates in the same order as on one stream, so the result is bit-identical to the
   // serial schedule (tests/test_gpu_edges.py).
-  if (fused_la) {                                                               // the first group's own triangle: all its chain reads
-    const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, G0(1), st, G0(1));
-    if (rc != 0) return rc;
-    scan(st, 0, (int64_t)G0(1) * NB, 0, SCAN_PARTS / 2);                        // the first group's rows, before chain(0) writes them
-  }
-  (void)hipEventRecord(e_entry, st);
-  (void)hipStreamWaitEvent(C, e_entry, 0);
-  (void)hipStreamWaitEvent(H, e_entry, 0);
-  if (fused_la) {
-    const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, H, -1, G0(1));            // everything else, beside chain(0)
-    if (rc != 0) return rc;
-    // (nothing else H queues beside chain(0) touches the first group's triangle: the assembly skips it, k_raw_planes reads the
-    // columns right of it, k_split_scales the partials)
-    scan(H, (int64_t)G0(1) * NB, n_pad, SCAN_PARTS / 2, SCAN_PARTS / 2);         // the other rows
-    split_scales(H);
-    (void)hipEventRecord(e_sc, H);
-  }
-  raw_planes0(H, G0(1));                                                        // (the head panel of the first group waits for it: e_hd)
-  (void)hipEventRecord(e_hd, H);
-  for (int gi = 0; gi < ng; ++gi) {
-    const int g0 = G0(gi), g1 = G0(gi + 1), g2 = G0(gi + 2), G = g1 - g0;
-    const T *Vg = Vg2[gi & 1];
-    chain(gi, C);
-    if (fused_la && gi == 0) (void)hipStreamWaitEvent(C, e_sc, 0);             // rows below the first group and the scales (planes of V, head panel)
-    vtrans(gi, C);
-    (void)hipEventRecord(e_v, C);
-    if (gi > 0 || bf3) (void)hipStreamWaitEvent(C, e_hd, 0);                   // head(gi - 1): rows R0 final (split engine: and their raw planes)
-    gpanel(g0, G, cm_buf(g1, g2 - g1, 0, 0, 0), Vg, C, 1);                      // head columns R1
-    (void)hipEventRecord(e_gh, C);
-    if (gi > 0) (void)hipStreamWaitEvent(C, e_tail, 0);                        // tail(gi - 1): rows R1 up to date
-    update(g1, g2 - g1, g0, g1 - 1, cm_buf(g1, g2 - g1, 0, 0, 0), C, PK_TRAIL_HEAD, 0, 0, true);   // U1: next triangle
-
-    (void)hipStreamWaitEvent(H, e_v, 0);
-    wtri_planes(gi, H);
-    gpanel(g0, G, cm_buf(g2, m - g2, Taug, 0, g0), Vg, H, 0);                   // rest of the panel columns
-    (void)hipEventRecord(e_p, H);
-    if (K) {                                                                   // rows R0 of W are final and in planes: filler work
-      (void)hipStreamWaitEvent(K, e_p, 0);
-      kacc(gi, K);
+  // A sweep that also assembles (plmc_factorize_ex_*, `job`): only the first group's own block triangle is written in front of the
+  // chain, everything else rides on the helper stream H beside the first group's chain (the first consumer, the transpose + head
+  // panel of group 0, waits for it: e_sc).  So does the scan for the scales -- but only of the rows below the first group: chain(0)
+  // overwrites the diagonal of the first group's rows (Schur updates, then U_ii) while H runs, so those rows are scanned on the
+  // caller's stream in front of the chain, into slots of their own (the scales are those of the input matrix, as in the two-call
+  // path, whatever the timing).
+  int lookahead(const AssembleJob *job) {
+    const bool fused = job && e_sc;
+    if (fused) {                                                                  // the first group's own triangle: all its chain reads
+      const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, G0(1), st, G0(1));
+      if (rc != 0) return rc;
+      scan(st, 0, (int64_t)G0(1) * NB, 0, SCAN_PARTS / 2);                        // the first group's rows, before chain(0) writes them
+    } else {
+      const int rc = inputs(job);
+      if (rc != 0) return rc;
     }
-    (void)hipStreamWaitEvent(H, e_gh, 0);
-    if (gi > 0) (void)hipStreamWaitEvent(H, e_tail, 0);
-    update(g1, g2 - g1, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), H, PK_TRAIL_HEAD, 0, 0, false, g2);   // head: rows R1, columns right of R1
+    (void)hipEventRecord(e_entry, st);
+    (void)hipStreamWaitEvent(C, e_entry, 0);
+    (void)hipStreamWaitEvent(H, e_entry, 0);
+    if (fused) {
+      const int rc = assemble_rows(*job, (int)sizeof(T), A, lda, strideA, q, 0, m, H, -1, G0(1));            // everything else, beside chain(0)
+      if (rc != 0) return rc;
+      // (nothing else H queues beside chain(0) touches the first group's triangle: the assembly skips it, k_raw_planes reads the
+      // columns right of it, k_split_scales the partials)
+      scan(H, (int64_t)G0(1) * NB, n_pad, SCAN_PARTS / 2, SCAN_PARTS / 2);         // the other rows
+      split_scales(H);
+      (void)hipEventRecord(e_sc, H);
+    }
+    raw_planes0(H, cm_buf(G0(1), m - G0(1), Taug, 0, 0));                       // (the head panel of the first group waits for it: e_hd)
     (void)hipEventRecord(e_hd, H);
+    for (int gi = 0; gi < ng; ++gi) {
+      const int g0 = G0(gi), g1 = G0(gi + 1), g2 = G0(gi + 2), G = g1 - g0;
+      chain(gi, C);
+      if (fused && gi == 0) (void)hipStreamWaitEvent(C, e_sc, 0);                 // rows below the first group and the scales (planes of V, head panel)
+      vtrans(gi, C);
+      (void)hipEventRecord(e_v, C);
+      if (gi > 0 || bf3) (void)hipStreamWaitEvent(C, e_hd, 0);                   // head(gi - 1): rows R0 final (split engine: and their raw planes)
+      gpanel(g0, G, cm_buf(g1, g2 - g1, 0, 0, 0), gi & 1, C, 1);                 // head columns R1
+      (void)hipEventRecord(e_gh, C);
+      if (gi > 0) (void)hipStreamWaitEvent(C, e_tail, 0);                        // tail(gi - 1): rows R1 up to date
+      update(g1, g2 - g1, g0, g1 - 1, cm_buf(g1, g2 - g1, 0, 0, 0), C, PK_TRAIL_HEAD, 0, 0, true);   // U1: next triangle
 
-    (void)hipStreamWaitEvent(st, e_p, 0);
-    (void)hipStreamWaitEvent(st, e_gh, 0);
-    update(g2, m - g2, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL);         // tail: rows below R1
-    (void)hipEventRecord(e_tail, st);
-    if (!K) kacc(gi, st);    // rows R0 of the inverse factor are final (e_p: panel copy; e_gh is behind vtrans): filler work
-  }
-  if (K) {
-    (void)hipEventRecord(e_doneK, K);
-    (void)hipStreamWaitEvent(st, e_doneK, 0);
-  }
-  // log det and the pivot / abort check read the diagonal of U and the chain kernels' control words: final behind the last chain,
-  // so they ride on the chain stream beside the last group's panel instead of behind the whole sweep (25 us + a launch gap)
-  const int rc_fin = finish(C);
-  (void)hipEventRecord(e_doneC, C);
-  (void)hipEventRecord(e_doneH, H);
-  (void)hipStreamWaitEvent(st, e_doneC, 0);
-  (void)hipStreamWaitEvent(st, e_doneH, 0);
-  (void)hipEventRecord(e_prev, st);                      // everything of this sweep is behind this point of the caller's stream
+      (void)hipStreamWaitEvent(H, e_v, 0);
+      wtri_planes(gi, H);
+      gpanel(g0, G, cm_buf(g2, m - g2, Taug, 0, g0), gi & 1, H, 0);              // rest of the panel columns
+      (void)hipEventRecord(e_p, H);
+      if (K) {                                                                   // rows R0 of W are final and in planes: filler work
+        (void)hipStreamWaitEvent(K, e_p, 0);
+        kacc(gi, K);
+      }
+      (void)hipStreamWaitEvent(H, e_gh, 0);
+      if (gi > 0) (void)hipStreamWaitEvent(H, e_tail, 0);
+      update(g1, g2 - g1, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), H, PK_TRAIL_HEAD, 0, 0, false, g2);   // head: rows R1, columns right of R1
+      (void)hipEventRecord(e_hd, H);
 
-  return rc_fin;
+      (void)hipStreamWaitEvent(st, e_p, 0);
+      (void)hipStreamWaitEvent(st, e_gh, 0);
+      update(g2, m - g2, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL);         // tail: rows below R1
+      (void)hipEventRecord(e_tail, st);
+      if (!K) kacc(gi, st);    // rows R0 of the inverse factor are final (e_p: panel copy; e_gh is behind vtrans): filler work
+    }
+    if (K) {
+      (void)hipEventRecord(e_doneK, K);
+      (void)hipStreamWaitEvent(st, e_doneK, 0);
+    }
+    // log det and the pivot / abort check read the diagonal of U and the chain kernels' control words: final behind the last chain,
+    // so they ride on the chain stream beside the last group's panel instead of behind the whole sweep (25 us + a launch gap)
+    const int rc_fin = finish(C);
+    (void)hipEventRecord(e_doneC, C);
+    (void)hipEventRecord(e_doneH, H);
+    (void)hipStreamWaitEvent(st, e_doneC, 0);
+    (void)hipStreamWaitEvent(st, e_doneH, 0);
+    (void)hipEventRecord(e_prev, st);                      // everything of this sweep is behind this point of the caller's stream
+    return rc_fin;
+  }
+};
+
+template <typename T, class S>
+int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *Vd, double *logdet, int *info,
+               int with_inverse_arg, int q, const float *eig_lo, void *stream, const AssembleJob *job = nullptr) {
+  // with_inverse & 4 (split engine, with the inverse factor): KEEP the planes of the solved rows of every group instead of
+  // rolling over two buffers -- Vd then has plmc_vd_blocks_keep blocks per latent -- so that plmc_potrs_aug_kept_* can later run
+  // its updates on the split engine too (the eval-mode factorisation cache)
+  const bool keep = !std::is_void<S>::value && (with_inverse_arg & 4) != 0 && (with_inverse_arg & 3) != 0;
+  const int with_inverse = with_inverse_arg & 3;
+  PLMC_REQUIRE(A && Vd && logdet && info, "null pointer");
+  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && lda % NB == 0 && lda >= n_pad, "n_pad/lda must be multiples of NB");
+  const int64_t naug_pad = plmc_pad(naug);
+  PLMC_REQUIRE(naug >= 0 && n_pad + naug_pad + (with_inverse ? n_pad : 0) <= lda,
+               "lda too small for naug (+ the n_pad columns of the inverse factor)");
+  PLMC_REQUIRE(q > 0 && aligned16(A) && aligned16(Vd), "bad q or unaligned buffer");
+  const Knobs &kn = knobs();
+  // block rows per group (the dev knob PLMC_GRP).  A sweep that KEEPS its planes always works in groups of GMAX:
+  // plmc_vd_blocks_keep reserves one buffer per GMAX block rows and plmc_potrs_aug_kept walks them in groups of GMAX (a
+  // smaller PLMC_GRP would write more buffers than were reserved and hand the cached substitution planes of the wrong rows)
+  const int grp = (!keep && kn.grp > 0 && kn.grp < GMAX) ? kn.grp : GMAX;
+  // With one or two latents the chain is the critical path: the bulk kernels then ask for LDS they do not use, which caps
+  // their occupancy -- 16 KB (three workgroups per CU) at q = 2, 20 KB (two per CU: 46 KB of LDS and half the register file
+  // stay free, so a chain workgroup is placed at once instead of waiting for a bulk workgroup to retire) at q = 1.
+  // q = 2: 11.4 -> 11.0 ms/step; q = 1: sweep 5.55 -> 5.30 (16 KB) -> 5.03 ms (20 KB); 26 KB and more lose again (5.36);
+  // with many latents the bulk is the bound and a cap costs 1-2 %.
+  const unsigned bulk_lds = (unsigned)(kn.bulk_lds >= 0 ? kn.bulk_lds : (q == 1 ? 20000 : (q == 2 ? 16000 : 0)));
+  Sweep<T, S> sw(A, n_pad, lda, naug, n_pad + naug_pad, strideA, Vd, q, with_inverse, keep, grp, bulk_lds, (hipStream_t)stream);
+  sw.eig_lo = eig_lo;
+  sw.logdet = logdet;
+  sw.info = info;
+  // whole-sweep bracket on the caller's stream (the per-kernel records of overlapped kernels add up to
+  // more than the wall time once the look-ahead runs the chain beside the trailing update)
+  const double npd = (double)n_pad;
+  ProfScope whole(PK_SWEEP, sw.st, q * (with_inverse == 2 ? 3.0 : (with_inverse ? 2.0 : 1.0)) * npd * npd * npd / 3.0, 0.0);
+  sw.clear();
+  return sw.bind_streams() ? sw.lookahead(job) : sw.one_stream(job);
 }
 
 // Where a sweep of the split engine left the full-height planes of W and the scale of that operand family inside its `Vd`
@@ -1398,13 +1393,12 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
 // elements / floats.  Returns false when the layout has no such planes.
 bool vd_w_planes(const float *Vd, int64_t n_pad, int64_t lda, const unsigned short **wk, int64_t *wk_lat_stride, const float **w_scale,
                  int64_t *w_scale_lat_stride) {
-  if (vd_wk_blocks(n_pad, lda, 4) <= 0) return false;
-  const int64_t strideV = plmc_vd_blocks_for(n_pad, lda, 4) * (int64_t)NB * NB;
-  const float *scl = Vd + plmc_split_scales_offset(n_pad, lda);
-  *wk = reinterpret_cast<const unsigned short *>(scl + (int64_t)NB * NB);
-  *wk_lat_stride = strideV * 2;
-  *w_scale = scl + SC_SW;                                        // (the scheme tag sits SC_TAG - SC_SW floats behind it)
-  *w_scale_lat_stride = strideV;
+  const VdLayout L(n_pad, lda, 4, false);
+  if (L.wk < 0) return false;
+  *wk = L.at<const unsigned short>(Vd, L.wk);
+  *wk_lat_stride = L.stride_u16();
+  *w_scale = L.at<const float>(Vd, L.scl) + SC_SW;               // (the scheme tag sits VD_W_TAG floats behind it)
+  *w_scale_lat_stride = L.stride_f32();
   return true;
 }
 
@@ -1413,7 +1407,8 @@ bool vd_w_planes(const float *Vd, int64_t n_pad, int64_t lda, const unsigned sho
 // (projected_lmc.py:1133-1134: gpytorch's prediction strategy keeps the factorisation): n^2 naug flops instead of a new sweep.
 // Per group of block rows: the group's inverse triangle W[R][R] (in the W columns) is transposed into the Vg scratch, the
 // group panel solves the rows R of the augmented columns, one depth-(128 G) update takes them out of the rows below.
-// MFMA of the element type (no planes of the factor exist any more); one stream.  wcol0 = first inverse-factor column.
+// MFMA of the element type (no planes of the factor exist any more); one stream, groups of GMAX, no dynamic-LDS cap on the bulk
+// launches.  wcol0 = first inverse-factor column.
 template <typename T>
 int potrs_aug_at(T *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0, int64_t strideA, T *Vd, int q, void *stream) {
   PLMC_REQUIRE(A && Vd, "null pointer");
@@ -1421,31 +1416,15 @@ int potrs_aug_at(T *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0, int6
   const int64_t naug_pad = plmc_pad(naug);
   PLMC_REQUIRE(naug > 0 && q > 0 && n_pad + naug_pad <= wcol0 && wcol0 + n_pad <= lda, "augmented columns must fit between the square part and the W columns");
   PLMC_REQUIRE(aligned16(A) && aligned16(Vd), "unaligned buffer");
-  const hipStream_t st = (hipStream_t)stream;
-  const int m = (int)(n_pad / NB), Tu = (int)(naug_pad / NB);
-  const int64_t strideV = plmc_vd_blocks_for(n_pad, lda, (int)sizeof(T)) * (int64_t)NB * NB;
-  const double nb = (double)NB, nb3 = nb * nb * nb, esz = sizeof(T);
-  T *const Wg = Vd + (int64_t)m * NB * NB;
-  T *const Vg = Wg + (int64_t)GMAX * NB * LDG;
-  T *const Pbulk = Wg + 4 * (int64_t)GMAX * NB * LDG;
-  T *const WA = A + wcol0;
-  const ColMap<T> cm{0, 0, Tu, 0, 0, n_pad, (T *)nullptr, lda, strideA};
-  for (int g0 = 0; g0 < m; g0 += GMAX) {
-    const int g1 = g0 + GMAX < m ? g0 + GMAX : m, G = g1 - g0;
-    hipLaunchKernelGGL((k_vtrans<T, void>), dim3(G * (G + 1) / 2, q), dim3(NTHREADS), 0, st, (const T *)(WA + (int64_t)g0 * NB * lda + (int64_t)g0 * NB), lda,
-                       strideA, strideV, Vg, G, (T *)nullptr, lda, strideA, (unsigned short *)nullptr, (int64_t)0, (const float *)nullptr, (int64_t)0);
-    {
-      const double prods = G * (G + 1) / 2.0;
-      ProfScope ps(PK_GPANEL, st, q * (double)Tu * prods * 2.0 * nb3, q * (double)Tu * (prods + G) * nb * nb * esz);
-      hipLaunchKernelGGL((k_gpanel_rows<T, 0>), dim3(Tu, (G + 1) / 2, q), dim3(NTHREADS), 0, st, (const T *)A, lda, strideA, g0, G, cm, (const T *)Vg,
-                         (int64_t)LDG, strideV, Pbulk, lda, strideV);
-      hipLaunchKernelGGL((k_gpanel_copy<T>), dim3(Tu, G, q), dim3(NTHREADS), 0, st, A, lda, strideA, g0, cm, (const T *)Pbulk, lda, strideV);
-    }
-    if (g1 < m) {
-      const double tiles = (double)Tu * (m - g1);
-      ProfScope ps(PK_TRAIL, st, q * tiles * 2.0 * nb * nb * (G * nb), q * 2.0 * tiles * nb * nb * esz);
-      hipLaunchKernelGGL((k_update<T, 0, 4>), dim3(Tu, m - g1, q), dim3(NTHREADS), 0, st, A, lda, strideA, g1, g0, g1 - 1, cm, 0, 0);
-    }
+  Sweep<T, void> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, 1, false, GMAX, 0u, (hipStream_t)stream);
+  const ColMap<T> cm{0, 0, sw.Taug, 0, 0, n_pad, (T *)nullptr, lda, strideA};        // the augmented columns only
+  for (int gi = 0; gi < sw.ng; ++gi) {
+    const int g0 = sw.G0(gi), g1 = sw.G0(gi + 1), G = g1 - g0;
+    // (one Vg copy for every group, unlike the sweep's vtrans)
+    hipLaunchKernelGGL((k_vtrans<T, void>), dim3(G * (G + 1) / 2, q), dim3(NTHREADS), 0, sw.st, (const T *)(sw.WA + (int64_t)g0 * NB * lda + (int64_t)g0 * NB),
+                       lda, strideA, sw.strideV, sw.Vg2[0], G, (T *)nullptr, lda, strideA, (unsigned short *)nullptr, (int64_t)0, (const float *)nullptr, (int64_t)0);
+    sw.gpanel(g0, G, cm, 0, sw.st, 0);
+    sw.update(g1, sw.m - g1, g0, g1 - 1, cm, sw.st, PK_TRAIL);
   }
   return launch_status("plmc_potrs_aug");
 }
@@ -1469,7 +1448,8 @@ __global__ __launch_bounds__(64) void k_aug_scales(int64_t n_pad, float *__restr
 // The same forward substitution on the split engine, against a factorisation that KEPT its planes (plmc_potrf_ex_f32 with
 // with_inverse | 4; Vd sized by plmc_vd_blocks_keep): per group the planes of Vgg from the W columns (k_vtrans), the group panel
 // of the augmented columns (k_gpanel_bf3: in place + planes), one depth-(128 G) macro-tile update of the rows below whose A
-// operand is the kept planes of the group's U rows; its epilogue writes the raw planes of the next group's rows.  One stream.
+// operand is the kept planes of the group's U rows; its epilogue writes the raw planes of the next group's rows.  One stream:
+// the sweep's own launches on the augmented columns, in groups of GMAX.
 template <class S>
 int potrs_aug_kept(float *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0, int64_t strideA, float *Vd, int q, void *stream) {
   PLMC_REQUIRE(A && Vd, "null pointer");
@@ -1477,48 +1457,17 @@ int potrs_aug_kept(float *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0
   const int64_t naug_pad = plmc_pad(naug);
   PLMC_REQUIRE(naug > 0 && q > 0 && n_pad + naug_pad <= wcol0 && wcol0 + n_pad <= lda, "augmented columns must fit between the square part and the W columns");
   PLMC_REQUIRE(aligned16(A) && aligned16(Vd), "unaligned buffer");
-  const hipStream_t st = (hipStream_t)stream;
-  const int m = (int)(n_pad / NB), Tu = (int)(naug_pad / NB);
-  const int64_t strideV = plmc_vd_blocks_keep(n_pad, lda) * (int64_t)NB * NB;
-  const double nb = (double)NB, nb3 = nb * nb * nb;
-  // the scratch layout of potrf_impl (fp32)
-  float *const Wg = Vd + (int64_t)m * NB * NB;
-  float *const Vg2[2] = {Wg + (int64_t)GMAX * NB * LDG, Wg + 2 * (int64_t)GMAX * NB * LDG};
-  float *const Pbulk = Wg + 4 * (int64_t)GMAX * NB * LDG;
-  const int64_t pl_buf = b3_elems<SplitB3>((int64_t)GMAX * NB, lda), vgp_elems = b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB);
-  unsigned short *const Pl0 = reinterpret_cast<unsigned short *>(Pbulk + (int64_t)GMAX * NB * lda);
-  unsigned short *const Praw = Pl0 + 2 * pl_buf;
-  unsigned short *const VgP2[2] = {Praw + pl_buf, Praw + pl_buf + vgp_elems};
-  float *const scl = Vd + plmc_split_scales_offset(n_pad, lda);        // behind VgP2[1]: one block
-  unsigned short *const Wk = reinterpret_cast<unsigned short *>(scl + (int64_t)NB * NB);
-  unsigned short *const Uk0 = reinterpret_cast<unsigned short *>(reinterpret_cast<float *>(Wk) + vd_wk_blocks(n_pad, lda, 4) * (int64_t)NB * NB);
-  const int64_t pl_lat = strideV * 2, sc_lat = strideV;
-  float *const WA = A + wcol0;
-  const ColMap<float> cm{0, 0, Tu, 0, 0, n_pad, (float *)nullptr, lda, strideA};
-  hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, st, (const float *)A, n_pad, (int64_t)0, n_pad, lda, strideA, (int)naug_pad,
-                     scl, sc_lat, 0);
-  hipLaunchKernelGGL((k_aug_scales<S>), dim3(q), dim3(64), 0, st, n_pad, scl, sc_lat);
-  const int G0 = GMAX < m ? GMAX : m;
-  hipLaunchKernelGGL((k_raw_planes<S>), dim3(Tu, G0, q), dim3(NTHREADS), 0, st, (const float *)A, lda, strideA, 0, cm, Praw, pl_lat, wcol0, (const float *)scl,
-                     sc_lat);
-  for (int g0 = 0, gi = 0; g0 < m; g0 += GMAX, ++gi) {
-    const int g1 = g0 + GMAX < m ? g0 + GMAX : m, g2 = g1 + GMAX < m ? g1 + GMAX : m, G = g1 - g0, nm = (G + 1) / 2;
-    unsigned short *const Pg = Uk0 + (int64_t)gi * pl_buf;
-    hipLaunchKernelGGL((k_vtrans<float, S>), dim3(GMAX * GMAX, q), dim3(NTHREADS), 0, st, (const float *)(WA + (int64_t)g0 * NB * lda + (int64_t)g0 * NB), lda,
-                       strideA, strideV, Vg2[gi & 1], G, (float *)nullptr, lda, strideA, VgP2[gi & 1], pl_lat, (const float *)scl, sc_lat);
-    {
-      const double prods = G * (G + 1) / 2.0;
-      ProfScope ps(PK_GPANEL, st, q * (double)Tu * prods * 2.0 * nb3, q * (double)Tu * (prods + G) * nb * nb * 4.0);
-      hipLaunchKernelGGL((k_gpanel_bf3<S>), dim3(Tu, (nm + 1) / 2, q), dim3(B3_NT), 0, st, A, lda, strideA, g0, G, cm, (const unsigned short *)VgP2[gi & 1], pl_lat,
-                         (const unsigned short *)Praw, pl_lat, Pg, pl_lat, wcol0, (const float *)scl, sc_lat, 1, Wk, pl_lat);
-    }
-    if (g1 < m) {
-      const int nrows = m - g1;
-      const double tiles = (double)Tu * nrows;
-      ProfScope ps(PK_TRAIL, st, q * tiles * 2.0 * nb * nb * (G * nb), q * 2.0 * tiles * nb * nb * 4.0);
-      hipLaunchKernelGGL((k_update_bf3<S, 0>), dim3(Tu, (nrows + 1) / 2, q), dim3(B3_NT), 0, st, A, lda, strideA, g1, nrows, g0, g1 - 1, cm, 0, 0,
-                         (const unsigned short *)Pg, pl_lat, wcol0, Praw, pl_lat, g2, (const float *)scl, sc_lat, (const unsigned short *)Wk, pl_lat);
-    }
+  Sweep<float, S> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, 1, true, GMAX, 0u, (hipStream_t)stream);
+  const ColMap<float> cm{0, 0, sw.Taug, 0, 0, n_pad, (float *)nullptr, lda, strideA};   // the augmented columns only
+  hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, sw.st, (const float *)A, n_pad, (int64_t)0, n_pad, lda, strideA, (int)naug_pad,
+                     sw.scl, sw.sc_lat, 0);
+  hipLaunchKernelGGL((k_aug_scales<S>), dim3(q), dim3(64), 0, sw.st, n_pad, sw.scl, sw.sc_lat);
+  sw.raw_planes0(sw.st, cm);
+  for (int gi = 0; gi < sw.ng; ++gi) {
+    const int g0 = sw.G0(gi), g1 = sw.G0(gi + 1);
+    sw.vtrans(gi, sw.st, true);
+    sw.gpanel(g0, g1 - g0, cm, gi & 1, sw.st, 0);
+    sw.update(g1, sw.m - g1, g0, g1 - 1, cm, sw.st, PK_TRAIL, 0, 0, false, sw.G0(gi + 2));
   }
   return launch_status("plmc_potrs_aug_kept");
 }
@@ -1562,32 +1511,15 @@ int w_diag_impl(const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, T *kinv
 }  // namespace plmc
 
 extern "C" {
-// Vd blocks per latent: m diagonal inverses + the fixed group scratch + the bulk panel buffer (GMAX block rows of lda) + m
-// diagonal K^-1 tiles; for 4-byte elements also the plane buffers of the split engine -- whether or not PLMC_SPLIT is
-// on, so that a workspace never depends on a knob.
-int64_t plmc_vd_blocks_for(int64_t n_pad, int64_t lda, int elem_bytes) {
-  const int64_t ldb = (lda + plmc::NB - 1) / plmc::NB;
-  // (version 4) + the full-height planes of W for plmc_kinv_grad_vd_*, when the layout has inverse-factor columns
-  // planes (4-byte elements): rolling buffer of the solved panel rows (2 groups) + raw rows of the next group (1 group), each
-  // 128 GMAX rows x 3 planes x lda x 2 bytes = 12 ldb blocks at GMAX = 8, + two copies of Vgg (3 x (128 GMAX)^2 x 2 bytes = 96 blocks each)
-  // + 1 block holding the scales of the operand families
-  const int64_t planes = elem_bytes == 4 ? 3 * (3 * plmc::GMAX * ldb / 2) + 2 * (6 * plmc::GMAX * plmc::GMAX / 4) + 1 : 0;
-  return 2 * (n_pad / plmc::NB) + plmc::VD_FIXED_BLOCKS + plmc::GMAX * ldb + planes + plmc::vd_wk_blocks(n_pad, lda, elem_bytes);
-}
+// Vd blocks per latent (vd_layout.hpp): for 4-byte elements the plane buffers of the split engine are counted whether or not
+// PLMC_SPLIT is on, so that a workspace never depends on a knob.
+int64_t plmc_vd_blocks_for(int64_t n_pad, int64_t lda, int elem_bytes) { return plmc::VdLayout(n_pad, lda, elem_bytes, false).blocks; }
 int64_t plmc_vd_blocks(int64_t n_pad, int64_t lda) { return plmc_vd_blocks_for(n_pad, lda, 4); }
 // ... when the sweep keeps the planes of every group's solved rows (with_inverse | 4, fp32): one 128 GMAX-row plane buffer per
 // group instead of the two rolling ones
-int64_t plmc_vd_blocks_keep(int64_t n_pad, int64_t lda) {
-  const int64_t ldb = (lda + plmc::NB - 1) / plmc::NB, m = n_pad / plmc::NB;
-  return plmc_vd_blocks_for(n_pad, lda, 4) + ((m + plmc::GMAX - 1) / plmc::GMAX) * (3 * plmc::GMAX * ldb / 2);
-}
-// where potrf_impl / potrs_aug_kept put `scl` (4-byte elements): behind the m diagonal inverses, the group scratch (Wg, Vg2, Ph),
-// the bulk panel buffer, three plane buffers of 128 GMAX rows (two rolling + raw) and the two plane copies of Vgg
-int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) {
-  using namespace plmc;
-  const int64_t pl_buf = b3_elems<SplitB3>((int64_t)GMAX * NB, lda), vgp_elems = b3_elems<SplitB3>((int64_t)GMAX * NB, (int64_t)GMAX * NB);
-  return (n_pad / NB) * NB * NB + 4 * (int64_t)GMAX * NB * LDG + (int64_t)GMAX * NB * lda + (3 * pl_buf + 2 * vgp_elems) / 2;
-}
+int64_t plmc_vd_blocks_keep(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, true).blocks; }
+// where potrf_impl / potrs_aug_kept put the scale block (4-byte elements), in floats
+int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, false).scl * plmc::NB * plmc::NB; }
 // PLMC_SPLIT picks the arithmetic of the bulk fp32 products: 0 = fp32 MFMA everywhere, 3 = SplitB3, 2 (default) = SplitH2
 // where the caller supplies eigenvalue bounds (plmc_potrf_ex_f32), SplitB3 otherwise.
 static int potrf_f32_any(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,

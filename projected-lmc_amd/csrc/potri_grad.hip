@@ -11,6 +11,7 @@
 #include "api_common.hpp"
 #include "covariance.hpp"
 #include "bf3_engine.hpp"
+#include "vd_layout.hpp"
 #include "../../include/plmc.h"
 
 namespace plmc {
@@ -373,8 +374,9 @@ int grad_tiles_impl(int kind, const T *A, int64_t n_pad, int64_t lda, int64_t st
   PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
   hipStream_t st = (hipStream_t)stream;
   const int m = (int)(n_pad / NB);
-  const int64_t strideV = plmc_vd_blocks_for(n_pad, lda, (int)sizeof(T)) * (int64_t)NB * NB;
-  const T *Kd = Vd + strideV - (int64_t)m * NB * NB;                  // last m blocks of the scratch: diagonal K^-1 tiles
+  const VdLayout L(n_pad, lda, (int)sizeof(T), false);
+  const int64_t strideV = L.stride();
+  const T *Kd = L.at<const T>(Vd, L.kd);                             // diagonal K^-1 tiles
   double *part = reinterpret_cast<double *>(partials);
   const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);
 #define PLMC_LAUNCH_GT(DC) \
