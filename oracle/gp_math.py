@@ -49,25 +49,65 @@ def kernel_matrix(kind, X1, X2, ell, outputscale=None, nu=2.5):
     a = X1.unsqueeze(0) / ell                                   # (q,n1,d)
     b = X2.unsqueeze(0) / ell
     diff = a.unsqueeze(2) - b.unsqueeze(1)                      # (q,n1,n2,d)
-    r2 = (diff * diff).sum(-1)
-    if kind == "rbf":
-        K = torch.exp(-0.5 * r2)
-    elif kind == "matern":
-        r = torch.sqrt(r2.clamp_min(1e-30))
-        e = torch.exp(-math.sqrt(2.0 * nu) * r)
-        if nu == 0.5:
-            K = e
-        elif nu == 1.5:
-            K = (1.0 + math.sqrt(3.0) * r) * e
-        elif nu == 2.5:
-            K = (1.0 + math.sqrt(5.0) * r + (5.0 / 3.0) * r2) * e
-        else:
-            raise ValueError("nu must be 0.5, 1.5 or 2.5")
-    else:
-        raise ValueError("unknown kernel kind %r" % (kind,))
+    K = _profile(kind, (diff * diff).sum(-1), nu)
     if outputscale is not None:
         K = K * outputscale.reshape(-1, 1, 1)
     return K
+
+
+def _profile(kind, r2, nu):
+    """Unit-outputscale stationary kernel as a function of the squared scaled distance r2."""
+    if kind == "rbf":
+        return torch.exp(-0.5 * r2)
+    if kind != "matern":
+        raise ValueError("unknown kernel kind %r" % (kind,))
+    r = torch.sqrt(r2.clamp_min(1e-30))
+    e = torch.exp(-math.sqrt(2.0 * nu) * r)
+    if nu == 0.5:
+        return e
+    if nu == 1.5:
+        return (1.0 + math.sqrt(3.0) * r) * e
+    if nu == 2.5:
+        return (1.0 + math.sqrt(5.0) * r + (5.0 / 3.0) * r2) * e
+    raise ValueError("nu must be 0.5, 1.5 or 2.5")
+
+
+def kernel_vjp(kind, X1, X2, ell, oscale, G, nu=2.5):
+    """Vector-Jacobian product of K_i = os_i k(X1, X2; ell_i) with G = d loss / d K  (G: (q,n1,n2)), by autograd of
+    sum_i <G_i, K_i>.  Returns (gX1 (n1,d) summed over the latents, gEll (q,d), gOs (q) | None).
+
+    Only the FIRST argument is differentiated: X2 is held constant even when it is the same tensor as X1 (the K_ZZ role
+    of the variational backward adds the second role itself).
+
+    Convention at coincident points (r = 0): the distance is sqrt(clamp_min(r2, 1e-30)), as in gpytorch's
+    distance computation [gpytorch-knowledge], and kernel_matrix uses it.  The clamp passes no gradient below 1e-30, so
+    a pair at r = 0 contributes NOTHING to gX1 or gEll, for every kind -- also for Matern-1/2, whose derivative
+    exp(-r) (x - x') / (ell^2 r) has no limit there."""
+    X1 = X1.detach().clone().requires_grad_(True)
+    ell = ell.detach().clone().requires_grad_(True)
+    osc = None if oscale is None else oscale.detach().clone().requires_grad_(True)
+    K = kernel_matrix(kind, X1, X2.detach(), ell, osc, nu)
+    ins = [X1, ell] + ([osc] if osc is not None else [])
+    g = torch.autograd.grad((G.to(K.dtype) * K).sum(), ins)
+    return g[0], g[1], (g[2] if osc is not None else None)
+
+
+def kernel_vjp_abs_terms(kind, X1, X2, ell, oscale, G, nu=2.5):
+    """The sums of ABSOLUTE terms behind each output of kernel_vjp -- sum_{i,b} |G_iab dK_iab / dx1_ak|,
+    sum_{a,b} |G_iab dK_iab / dell_ik|, sum_{a,b} |G_iab dK_iab / dos_i| -- the scale of a rounding-error bound for
+    an evaluation of the same sums in lower precision.  Entry derivatives by autograd through the scaled differences
+    D = x1 / ell - x2 / ell:  dK / dx1_k = dK / dD_k / ell_k,  dK / dell_k = -dK / dD_k D_k / ell_k."""
+    q, d = ell.shape
+    e = ell.detach().reshape(q, 1, 1, d)
+    D = (X1.detach().unsqueeze(0).unsqueeze(2) / e - X2.detach().unsqueeze(0).unsqueeze(1) / e).requires_grad_(True)
+    Ku = _profile(kind, (D * D).sum(-1), nu)                    # (q,n1,n2), unit outputscale
+    dKdD, = torch.autograd.grad(Ku.sum(), D)
+    os_ = torch.ones(q, dtype=Ku.dtype) if oscale is None else oscale.detach().to(Ku.dtype)
+    Ga = (G.detach().to(Ku.dtype) * os_.reshape(q, 1, 1)).abs()
+    tX = (Ga.unsqueeze(-1) * (dKdD / e).abs()).sum((0, 2))
+    tE = (Ga.unsqueeze(-1) * (dKdD * D / e).abs()).sum((1, 2))
+    tO = (G.detach().to(Ku.dtype) * Ku.detach()).abs().sum((1, 2))
+    return tX, tE, tO
 
 
 def kernel_matrix_chunked(kind, X1, X2, ell_1d, outputscale=None, nu=2.5, chunk=1024):

@@ -27,11 +27,11 @@ __global__ __launch_bounds__(NTHREADS) void k_kernel_vjp(int kind, const T *__re
   if (a >= n1) return;
   const T *el = ell + (int64_t)lat * d;
   const T os = oscale ? oscale[lat] : T(1);
-  T u1[DCAP], il[DCAP];
+  T x1[DCAP], il[DCAP];
 #pragma unroll
   for (int k = 0; k < DCAP; ++k) {
     il[k] = k < d ? T(1) / el[k] : T(0);
-    u1[k] = k < d ? X1[(int64_t)a * d + k] * il[k] : T(0);
+    x1[k] = k < d ? X1[(int64_t)a * d + k] : T(0);
   }
   double sx[DCAP], sl[DCAP], so = 0.0;
 #pragma unroll
@@ -41,9 +41,11 @@ __global__ __launch_bounds__(NTHREADS) void k_kernel_vjp(int kind, const T *__re
     const T g = Grow[b];
     T df[DCAP];
     T r2 = T(0);
+    // difference of the raw inputs, then scaled: exactly 0 at coincident points.  (x1 il - x2 il contracts to an fma
+    // whose result there is the rounding error of x1 il; the Matern-1/2 factor exp(-r) / r turned it into an O(1) term.)
 #pragma unroll
     for (int k = 0; k < DCAP; ++k) {
-      df[k] = k < d ? u1[k] - X2[(int64_t)b * d + k] * il[k] : T(0);
+      df[k] = k < d ? (x1[k] - X2[(int64_t)b * d + k]) * il[k] : T(0);
       r2 += df[k] * df[k];
     }
     T val, base;

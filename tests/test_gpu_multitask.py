@@ -46,25 +46,31 @@ def _oracle_inputs(model, lik):
     return sd, ell, B, S, mc
 
 
-@pytest.mark.parametrize("model_type,kernel,rank,d", [("LMC", "RBFKernel", 0, 3), ("LMC", "MaternKernel", 2, 3),
-                                                      ("ICM", "RBFKernel", 0, 3),
-                                                      # more than 8 / more than 16 input dimensions: the gradient
-                                                      # epilogue takes the lengthscale sums 8 dimensions per tile walk
-                                                      ("LMC", "MaternKernel", 0, 12), ("LMC", "RBFKernel", 2, 20)])
-def test_exact_lmc_mll_and_gradients(plmc, model_type, kernel, rank, d):
+@pytest.mark.parametrize("model_type,kernel,rank,d,ker_kwargs", [
+    pytest.param("LMC", "RBFKernel", 0, 3, None, id="LMC-RBFKernel-0-3"),
+    pytest.param("LMC", "MaternKernel", 2, 3, None, id="LMC-MaternKernel-2-3"),
+    pytest.param("ICM", "RBFKernel", 0, 3, None, id="ICM-RBFKernel-0-3"),
+    # more than 8 / more than 16 input dimensions: the gradient epilogue takes the lengthscale sums 8 dimensions per
+    # tile walk
+    pytest.param("LMC", "MaternKernel", 0, 12, None, id="LMC-MaternKernel-0-12"),
+    pytest.param("LMC", "RBFKernel", 2, 20, None, id="LMC-RBFKernel-2-20"),
+    # Matern-1/2 and 3/2 through k_lmc_assemble, k_lmc_kinv_grad and k_lmc_cross
+    pytest.param("LMC", "MaternKernel", 2, 3, {"nu": 0.5}, id="LMC-MaternKernel-2-3-nu0.5"),
+    pytest.param("LMC", "MaternKernel", 0, 12, {"nu": 1.5}, id="LMC-MaternKernel-0-12-nu1.5")])
+def test_exact_lmc_mll_and_gradients(plmc, model_type, kernel, rank, d, ker_kwargs):
     n, p, q = 70, 4, 2
     X, Y = _data(n, d, p, seed=5)
     torch.manual_seed(3)
     lik = plmc.MultitaskGaussianLikelihood(num_tasks=p, rank=rank)
     model = plmc.MultitaskGPModel(X, Y, lik, n_tasks=p, n_latents=q, model_type=model_type, init_lmc_coeffs=True,
-                                  mean_type=plmc.ConstantMean, kernel_type=getattr(plmc, kernel))
+                                  mean_type=plmc.ConstantMean, kernel_type=getattr(plmc, kernel), ker_kwargs=ker_kwargs)
     model, lik = model.double(), lik.double()
     g = torch.Generator().manual_seed(7)
     with torch.no_grad():
         for prm in list(model.parameters()) + list(lik.parameters()):
             prm.add_(0.2 * torch.randn(prm.shape, generator=g, dtype=torch.float64))
     sd, ell, B, S, mc = _oracle_inputs(model, lik)
-    okind, nu = ("rbf", 2.5) if kernel == "RBFKernel" else ("matern", 2.5)
+    okind, nu = ("rbf", 2.5) if kernel == "RBFKernel" else ("matern", (ker_kwargs or {}).get("nu", 2.5))
     ref = ld.lmc_exact_mll(okind, X, Y, ell, B, S, mean_const=mc, nu=nu)
     ref.backward()
     assert torch.allclose(model.lmc_coefficients().double(),

@@ -1,6 +1,7 @@
 """GPU parity of the variational LMC path (`VariationalMultitaskGPModel` + `VariationalELBO`,
 SURVEY.md 8a row a12 / BASELINE config 4) against the CPU oracle: ELBO value and the gradient of
 every parameter, including the learned inducing locations."""
+import math
 import warnings
 
 import pytest
@@ -20,7 +21,7 @@ def plmc():
     return projectedlmc
 
 
-def _build(plmc, n, d, p, q, kernel, oscale, dtype, seed=0):
+def _build(plmc, n, d, p, q, kernel, oscale, dtype, seed=0, ker_kwargs=None):
     g = torch.Generator().manual_seed(seed)
     X = (2 * torch.rand(n, d, generator=g, dtype=torch.float64) - 1).to(dtype)
     Y = torch.randn(n, p, generator=g, dtype=torch.float64).to(dtype)
@@ -33,7 +34,8 @@ def _build(plmc, n, d, p, q, kernel, oscale, dtype, seed=0):
             warnings.simplefilter("ignore")
             model = plmc.VariationalMultitaskGPModel(X, n_latents=q, n_tasks=p, train_ind_ratio=1.5, seed=0,
                                                      init_lmc_coeffs=True, train_y=Y, mean_type=plmc.ConstantMean,
-                                                     kernel_type=getattr(plmc, kernel), outputscales=oscale)
+                                                     kernel_type=getattr(plmc, kernel), outputscales=oscale,
+                                                     ker_kwargs=ker_kwargs)
     finally:
         torch.set_default_dtype(old)
     g2 = torch.Generator().manual_seed(seed + 1)
@@ -63,11 +65,16 @@ def _oracle_elbo(model, lik, X, Y, kind, nu, dtype_jitter):
     return val, sd
 
 
-@pytest.mark.parametrize("kernel,oscale", [("RBFKernel", False), ("MaternKernel", True)])
-def test_elbo_and_all_gradients_fp64(plmc, kernel, oscale):
+@pytest.mark.parametrize("kernel,oscale,ker_kwargs", [
+    pytest.param("RBFKernel", False, None, id="RBFKernel-False"),
+    pytest.param("MaternKernel", True, None, id="MaternKernel-True"),
+    # Matern-1/2 and 3/2 through plmc_kernel_vjp (K_ZZ: coincident points on the diagonal) and the assembly kernels
+    pytest.param("MaternKernel", True, {"nu": 0.5}, id="MaternKernel-True-nu0.5"),
+    pytest.param("MaternKernel", False, {"nu": 1.5}, id="MaternKernel-False-nu1.5")])
+def test_elbo_and_all_gradients_fp64(plmc, kernel, oscale, ker_kwargs):
     n, d, p, q = 150, 3, 4, 2
-    X, Y, model, lik = _build(plmc, n, d, p, q, kernel, oscale, torch.float64)
-    kind, nu = ("rbf", 2.5) if kernel == "RBFKernel" else ("matern", 2.5)
+    X, Y, model, lik = _build(plmc, n, d, p, q, kernel, oscale, torch.float64, ker_kwargs=ker_kwargs)
+    kind, nu = ("rbf", 2.5) if kernel == "RBFKernel" else ("matern", (ker_kwargs or {}).get("nu", 2.5))
     ref, sd = _oracle_elbo(model, lik, X, Y, kind, nu, 1e-6)
     ref.backward()
     model, lik = model.to(DEV), lik.to(DEV)
@@ -102,6 +109,46 @@ def test_elbo_fp32_config4_shape(plmc):
     with torch.no_grad():
         pred = lik(model(X[:50].to(DEV)))
     assert pred.mean.shape == (50, p) and bool((pred.variance > 0).all())
+
+
+@pytest.mark.parametrize("kernel,ker_kwargs", [pytest.param("RBFKernel", None, id="RBFKernel"),
+                                               pytest.param("MaternKernel", {"nu": 0.5}, id="MaternKernel-nu0.5")])
+def test_elbo_and_all_gradients_fp32(plmc, kernel, ker_kwargs):
+    """Small fp32 case (n = 300, m = 200 inducing points, d = 9): the ELBO within 1e-4 relative (the BASELINE fp32
+    tolerance) and EVERY gradient against the fp64 oracle at the fp32-rounded parameters.  Matern-1/2 sends the
+    coincident points of the K_ZZ diagonal through plmc_kernel_vjp (r = 0: zero contribution).
+
+    Bound, a priori: each gradient is a chain of ~4 products / triangular solves of length L = max(m, n) that applies
+    L^-1 twice (the Cholesky adjoint Kbar = L^-T Phi(L^T Lbar) L^-1), so the conditioning enters as
+    kappa(L)^2 = kappa(K_ZZ + jitter I).  With the rounding errors modelled as independent (the probabilistic bound of
+    Higham & Mary, SIAM J. Sci. Comput. 41 (2019): sqrt(L) u for a length-L accumulation) the error of a gradient is at
+    most 4 sqrt(L) kappa u of its largest entry, kappa the largest over the latents, from the oracle's K_ZZ."""
+    n, d, p, q = 300, 9, 4, 2
+    X, Y, model, lik = _build(plmc, n, d, p, q, kernel, False, torch.float32, seed=3, ker_kwargs=ker_kwargs)
+    kind, nu = ("rbf", 2.5) if kernel == "RBFKernel" else ("matern", ker_kwargs["nu"])
+    ref, sd = _oracle_elbo(model, lik, X, Y, kind, nu, 1e-4)
+    ref.backward()
+    Z = sd["variational_strategy.base_variational_strategy.inducing_points"].detach()
+    m = Z.shape[0]
+    assert m == 200
+    ell = gm.softplus(sd["covar_module.raw_lengthscale"].detach()).reshape(q, -1)
+    ev = torch.linalg.eigvalsh(gm.kernel_matrix(kind, Z, Z, ell, None, nu) + 1e-4 * torch.eye(m, dtype=torch.float64))
+    kappa = float((ev[:, -1] / ev[:, 0]).max())
+    tol = 4.0 * math.sqrt(max(m, n)) * kappa * 2.0 ** -24
+    model, lik = model.to(DEV), lik.to(DEV)
+    model.train(); lik.train()
+    out = plmc.VariationalELBO(lik, model, num_data=n)(model(X.to(DEV)), Y.to(DEV))
+    out.backward()
+    assert abs(float(out.detach()) - float(ref.detach())) < 1e-4 * abs(float(ref.detach())), (float(out), float(ref))
+    named = dict(list(model.named_parameters()) + [("lik." + k, v) for k, v in lik.named_parameters()])
+    for name, leaf in sd.items():
+        if leaf.grad is None:
+            continue
+        got, ref_g = named[name].grad.cpu().double(), leaf.grad
+        if name.endswith("chol_variational_covar"):
+            got, ref_g = got.tril(), ref_g.tril()
+        err, scale = float((got - ref_g).abs().max()), float(ref_g.abs().max())
+        assert err <= tol * scale, (name, err / scale, tol, kappa)
 
 
 # ------------------------------------------------------------------------------------------------

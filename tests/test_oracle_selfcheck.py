@@ -1,5 +1,6 @@
 """Reference-independent checks that pin the oracle: closed forms,
 finite differences, the projected == dense-LMC identity, batch == loop, p == q edge."""
+import itertools
 import math
 
 import pytest
@@ -83,6 +84,41 @@ def test_analytic_gradient_matches_autograd_and_fd(kind, nu, oscale):
                                            None if osc is None else osc.detach(), nu).sum()
     fd = (f(e1) - f(e2)) / (2 * h)
     assert abs(fd - g_ell[1, 2]) < 1e-5 * max(1.0, abs(fd))
+
+
+@pytest.mark.parametrize("kind,nu", [("rbf", 2.5), ("matern", 0.5), ("matern", 1.5), ("matern", 2.5)])
+def test_kernel_vjp_helper_against_finite_differences(kind, nu):
+    """gm.kernel_vjp, the reference of the HIP kernel VJP: central finite differences of sum_i <G_i, os_i k(X1, X2; ell_i)>
+    w.r.t. X1 (X2 held), ell and os at points away from r = 0; with one term per output its sums of absolute terms are
+    the absolute values; a pair at r = 0 adds nothing to gX1 or gEll (gpytorch's clamp convention)."""
+    g = torch.Generator().manual_seed(6)
+    q, n1, n2, d = 2, 4, 5, 3
+    X1 = 2 * torch.rand(n1, d, generator=g) - 1
+    X2 = 2 * torch.rand(n2, d, generator=g) - 1
+    ell = 0.5 + torch.rand(q, d, generator=g)
+    osc = 0.5 + torch.rand(q, generator=g)
+    G = torch.randn(q, n1, n2, generator=g)
+    got = gm.kernel_vjp(kind, X1, X2, ell, osc, G, nu)
+    F = lambda args: float((G * gm.kernel_matrix(kind, args[0], X2, args[1], args[2], nu)).sum())
+    h = 1e-6
+    for arg in range(3):
+        fd = torch.zeros_like(got[arg])
+        for idx in itertools.product(*[range(s) for s in fd.shape]):
+            up, dn = [X1.clone(), ell.clone(), osc.clone()], [X1.clone(), ell.clone(), osc.clone()]
+            up[arg][idx] += h
+            dn[arg][idx] -= h
+            fd[idx] = (F(up) - F(dn)) / (2 * h)
+        assert torch.allclose(got[arg], fd, rtol=1e-6, atol=1e-8), (arg, got[arg], fd)
+    one = (X1[:1], X2[:1], ell[:1], osc[:1], G[:1, :1, :1])
+    for t, w in zip(gm.kernel_vjp_abs_terms(kind, *one, nu), gm.kernel_vjp(kind, *one, nu)):
+        assert torch.allclose(t, w.abs(), rtol=1e-12, atol=0)
+    # X2 gets a copy of row 2 of X1: with or without the G weight of that pair, gX1 and gEll are the same
+    X2c = torch.cat([X2, X1[2:3]])
+    Gc = torch.cat([G, torch.randn(q, n1, 1, generator=g)], -1)
+    Gz = Gc.clone()
+    Gz[:, 2, -1] = 0.0
+    a, b = gm.kernel_vjp(kind, X1, X2c, ell, osc, Gc, nu), gm.kernel_vjp(kind, X1, X2c, ell, osc, Gz, nu)
+    assert torch.allclose(a[0], b[0], rtol=1e-14, atol=1e-15) and torch.allclose(a[1], b[1], rtol=1e-14, atol=1e-15)
 
 
 VARIANTS = {
