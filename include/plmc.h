@@ -126,10 +126,8 @@ int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, 
  * (the identity rides along as further right-hand sides) -- the first half of the Khat^-1 that
  * `loss.backward()` needs (experiments.py:270).  No initialisation of those
  * columns is required.
- * with_inverse == 2: additionally accumulate Khat^-1 = W^T W group by group while the sweep runs (the second half of
- * that work, as filler beside the latency-bound end of the factorisation): tile (ib < jb) of Khat^-1 is left in the
- * strictly LOWER triangle of the square part at block (jb, ib) -- never read otherwise -- and the diagonal tiles in the
- * last n_pad/NB blocks of Vd.  plmc_grad_tiles_* then turns it into the MLL gradient in one HBM-bound pass.
+ * with_inverse with bit 1 set (2, 3, ...) is refused before anything is launched: Khat^-1 and the gradient come from
+ * plmc_kinv_grad_* behind the sweep.
  */
 #define PLMC_INFO_CHAIN_ABORT 0x7ffffff0
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,
@@ -201,18 +199,6 @@ int plmc_wt_matvec_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strid
                        float *alpha, int q, void *stream);
 int plmc_wt_matvec_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *z,
                        double *alpha, int q, void *stream);
-
-/*
- * MLL gradient from the Khat^-1 a sweep with with_inverse = 2 accumulated (same outputs as plmc_kinv_grad_*: grad, and
- * optionally kinv_diag; partials: the same scratch): (alpha alpha^T - Khat^-1) o dKhat/dtheta reduced per tile from X in
- * LDS, one read of the stored tiles.  A, Vd: the buffers of that sweep.
- */
-int plmc_grad_tiles_f32(int kind, const float *A, int64_t n_pad, int64_t lda, int64_t strideA, const float *Vd,
-                        const float *alpha, const float *X, int n, int d, const float *ell, const float *oscale,
-                        double *grad, float *kinv_diag, void *partials, int q, void *stream);
-int plmc_grad_tiles_f64(int kind, const double *A, int64_t n_pad, int64_t lda, int64_t strideA, const double *Vd,
-                        const double *alpha, const double *X, int n, int d, const double *ell, const double *oscale,
-                        double *grad, double *kinv_diag, void *partials, int q, void *stream);
 
 /*
  * Batched "TN" product on the tile engine:  C[b] (=, +=, -=) A[b]^T B[b]  with A: K x M and B: K x N, both stored
@@ -414,14 +400,14 @@ int plmc_qr_small_f64(const double *A, int m, int n, int64_t lda, double *Q, int
  * events, then returns per kernel class (index < plmc_prof_kernels(), name plmc_prof_name(i)):
  * total milliseconds, number of launches, and the ALGORITHMIC flops / bytes of those launches;
  * it clears the record.
- * Process-global state of the library (all of it): this profiler record; per device, TWO sets of three helper streams and
+ * Process-global state of the library (all of it): this profiler record; per device, TWO sets of two helper streams and
  * sixteen ordering events for the look-ahead in plmc_potrf_* (created on first use, never destroyed), each bound to the
  * caller stream that used it last.  Sweeps queued on one stream share a set (stream order protects it); sweeps from two
  * streams get a set each and may overlap on the device (their buffers must differ); a third stream takes over the least
  * recently used set and waits (stream-side, an event) for that set's last sweep.  Calls from several host THREADS are
  * serialised by one library-wide lock while they enqueue (the kernels overlap on the device as their streams allow); each
  * thread keeps its own choice of sweep set.  The Python layer calls from one thread per process.
- * Dev knobs are environment variables read once per process (PLMC_HALF_TILES, PLMC_GRP, PLMC_KINV_ORDER,
+ * Dev knobs are environment variables read once per process (PLMC_HALF_TILES, PLMC_GRP,
  * PLMC_SERIAL, PLMC_BULK_LDS, PLMC_CHAIN, PLMC_CHAIN_NW, PLMC_CHAIN_EDGE); plmc_dev_reload_knobs() re-reads them (tests and bench.py change one and reload).  They change
  * schedules; PLMC_GRP also changes the depth of the updates and with it the rounding.  PLMC_SPLIT (0, 2, 3) selects the
  * arithmetic of the bulk fp32 products (see plmc_potrf_ex_f32).  Buffer sizes do not depend on any knob.

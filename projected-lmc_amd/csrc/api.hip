@@ -18,7 +18,7 @@ char *err_buf() {
 static const char *kProfNames[PK_COUNT] = {"k_assemble", "k_write_rhs", "k_assemble_cross", "k_diag",   "k_panel",
                                            "k_trail",    "k_wdiag",     "k_trtri_row",      "k_extract_col",
                                            "k_wt_matvec", "k_kinv_grad", "k_reduce_grad", "k_kernel_vjp",
-                                           "sweep_total", "k_trail_row", "k_trail_head", "k_gpanel", "k_kacc", "k_grad_tiles", "k_split_w", "k_posterior_moments"};
+                                           "sweep_total", "k_trail_row", "k_trail_head", "k_gpanel", "k_split_w", "k_posterior_moments"};
 struct ProfRec { int id; hipEvent_t a, b; double flops, bytes; };
 static unsigned g_prof_mask = 0;          // bit i: bracket kernel class i
 static std::vector<ProfRec> g_recs;
@@ -42,11 +42,10 @@ void api_unlock() { g_api_mutex.unlock(); }
 static Knobs g_knobs;
 static bool g_knobs_loaded = false;
 static void load_knobs() {
-  const char *h = getenv("PLMC_HALF_TILES"), *g = getenv("PLMC_GRP"), *o = getenv("PLMC_KINV_ORDER");
+  const char *h = getenv("PLMC_HALF_TILES"), *g = getenv("PLMC_GRP");
   g_knobs.half_tiles = h ? (atoi(h) == 1 ? 1e30 : (double)atoi(h)) : 640.0;
   g_knobs.grp = g ? atoi(g) : 0;
   g_knobs.serial = getenv("PLMC_SERIAL") && atoi(getenv("PLMC_SERIAL")) != 0;
-  g_knobs.kinv_order = o ? atoi(o) : 4;
   g_knobs.bulk_lds = getenv("PLMC_BULK_LDS") ? atoi(getenv("PLMC_BULK_LDS")) : -1;
   g_knobs.split = getenv("PLMC_SPLIT") ? atoi(getenv("PLMC_SPLIT")) : 2;     // fp32 entry points only
   if (g_knobs.split != 0 && g_knobs.split != 3) g_knobs.split = 2;
@@ -74,7 +73,7 @@ struct SweepCtx {
   hipStream_t caller = nullptr;
   bool used = false;
   unsigned long long stamp = 0;
-  hipStream_t side[3] = {nullptr, nullptr, nullptr};
+  hipStream_t side[2] = {nullptr, nullptr};
   hipEvent_t ev[16] = {nullptr};
 };
 static SweepCtx g_ctx[64][SWEEP_CTX];
@@ -86,14 +85,14 @@ static SweepCtx *cur_ctx() {
   return &g_ctx[dev][t_ctx];
 }
 // which: 0 = the chain (highest priority: its small launches must get CU slots ahead of queued bulk tiles), 1 = the group
-// panel + head rows (high), 2 = the K^-1 accumulation (lowest priority: filler work)
+// panel + head rows (high)
 hipStream_t side_stream(int which) {
   SweepCtx *c = cur_ctx();
-  if (!c || which < 0 || which > 2) return nullptr;
+  if (!c || which < 0 || which > 1) return nullptr;
   if (!c->side[which]) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&c->side[which], hipStreamNonBlocking, which == 2 ? lo : hi) != hipSuccess) c->side[which] = nullptr;
+    if (hipStreamCreateWithPriority(&c->side[which], hipStreamNonBlocking, hi) != hipSuccess) c->side[which] = nullptr;
   }
   return c->side[which];
 }

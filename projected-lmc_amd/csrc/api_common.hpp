@@ -32,7 +32,7 @@ inline int launch_status(const char *fn) {
 
 // kernel classes known to the optional profiler (api.hip)
 enum ProfKernel { PK_ASSEMBLE, PK_WRITE_RHS, PK_CROSS, PK_DIAG, PK_PANEL, PK_TRAIL, PK_WDIAG, PK_TRTRI, PK_EXTRACT,
-                  PK_WTMV, PK_KINV_GRAD, PK_REDUCE, PK_VJP, PK_SWEEP, PK_TRAIL_ROW, PK_TRAIL_HEAD, PK_GPANEL, PK_KACC, PK_GRAD_TILES, PK_SPLIT, PK_POST, PK_COUNT };
+                  PK_WTMV, PK_KINV_GRAD, PK_REDUCE, PK_VJP, PK_SWEEP, PK_TRAIL_ROW, PK_TRAIL_HEAD, PK_GPANEL, PK_SPLIT, PK_POST, PK_COUNT };
 
 // Brackets the launches made while it is alive with two hipEvents (no-op unless its class is enabled, plmc_prof_enable).
 // flops / bytes = ALGORITHMIC work of the bracketed launch (DESIGN.md gives the formulas).
@@ -58,7 +58,6 @@ struct Knobs {
   int chain;           // PLMC_CHAIN: 1 (default) = the chain of a group as one resident launch (k_chain), 0 = three launches per block row
   int chain_edge;      // PLMC_CHAIN_EDGE: pool size for the first and the last two groups of a sweep (<= 0: as the others)
   int chain_nw;        // PLMC_CHAIN_NW: pool workgroups of the resident chain beside the q critical ones (0 = by the number of latents)
-  int kinv_order;      // PLMC_KINV_ORDER: tile order of the gradient kernel (0 XCD-dealt, 1 grid, 4 longest first, 5 = 4 + general epilogue)
 };
 const Knobs &knobs();
 
@@ -73,7 +72,7 @@ struct AssembleJob {
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,
                   int ncols = -1, int skip = 0);
 
-hipStream_t side_stream(int which = 0);   // per-device helper streams (api.hip), which in {0, 1, 2}; nullptr on failure
+hipStream_t side_stream(int which = 0);   // per-device helper streams (api.hip), which in {0, 1}; nullptr on failure
 hipEvent_t sync_event(int idx);     // per-device ordering events, idx in [0,16)
 void bind_sweep_ctx(hipStream_t caller, int e_prev_idx);   // select the stream / event set of this caller stream (api.hip)
 

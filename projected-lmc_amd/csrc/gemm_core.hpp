@@ -351,6 +351,15 @@ __device__ __forceinline__ void tile_writeback(const Acc<T, MT> &acc, T *Cg, int
   }
 }
 
+// Packed triangle index t = jb (jb + 1) / 2 + ib, ib <= jb  ->  (ib, jb): the float square root, corrected to exact.
+__device__ __forceinline__ void tri_decode(int t, int &ib, int &jb) {
+  int j = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while ((j + 1) * (j + 2) / 2 <= t) ++j;
+  while (j * (j + 1) / 2 > t) --j;
+  jb = j;
+  ib = t - j * (j + 1) / 2;
+}
+
 // XCD-aware enumeration of the upper-triangular tile set {(ib, jb): ib <= jb < m} of `nlat` matrices.
 // Tiles are grouped in 8 x 8 super-blocks (64 tiles that share 8 + 8 operand strips); super-blocks
 // are ordered by decreasing K-depth (jb ascending) and dealt round-robin to the 8 XCDs; workgroup w is
@@ -367,11 +376,8 @@ __device__ __forceinline__ bool xcd_tri_decode(int w, int m, int nlat, int &lat,
   const int g = xcd + 8 * (slot >> 6);
   if (g >= G) return false;
   lat = g / NSB;
-  const int k = g - lat * NSB;
-  int JB = (int)((sqrtf(8.0f * (float)k + 1.0f) - 1.0f) * 0.5f);
-  while ((JB + 1) * (JB + 2) / 2 <= k) ++JB;
-  while (JB * (JB + 1) / 2 > k) --JB;
-  const int IB = k - JB * (JB + 1) / 2;
+  int IB, JB;
+  tri_decode(g - lat * NSB, IB, JB);
   const int t = slot & 63;
   ib = IB * 8 + (t >> 3);
   jb = JB * 8 + (t & 7);

@@ -1,7 +1,7 @@
 // kinv_epilogue.inc -- body of the gradient epilogue of one 128 x 128 tile (ib, jb) of K^-1 held in `acc`; textually included
 // by k_kinv_grad (256 threads, potri_grad.hip) and by kinv_tile_epilogue (the halves of the 512-thread macro-tile kernel).
 // Names it expects in scope: T, DCAP, SPLINE, acc, smem, tid (0..255), live, kind, ib, jb, lat, m, n_pad, alpha, X, n, d, ell,
-// oscale, Kinv, ldk, strideK, kinv_diag, partials, plain; and the macro PLMC_KINV_KEEP (bool expression: one pass over the tile with every
+// oscale, Kinv, ldk, strideK, kinv_diag, partials; and the macro PLMC_KINV_KEEP (bool expression: one pass over the tile with every
 // lengthscale sum in registers, or one pass per 8 dimensions).
   // stage scaled inputs u = x / ell and alpha for the tile's rows and columns
   const int lane = tid & 63, wave = tid >> 6;
@@ -37,7 +37,7 @@
       smem[L::AJ + tid] = live ? alpha[(int64_t)lat * n_pad + jb * NB + tid] : T(0);
     }
     __syncthreads();
-    const bool interior = ib < jb && (jb + 1) * NB <= n && !Kinv && !kinv_diag && plain != 5;
+    const bool interior = ib < jb && (jb + 1) * NB <= n && !Kinv && !kinv_diag;
 #define PLMC_GRAD_TILE(KIND, INT) \
   grad_tile_small<T, DCAP, KIND, INT>(acc, smem, tid, os, ib, jb, n, lat, n_pad, Kinv, ldk, strideK, kinv_diag, g, g_noise, g_os)
     if (interior) {

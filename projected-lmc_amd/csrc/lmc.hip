@@ -135,7 +135,7 @@ __global__ __launch_bounds__(NTHREADS, TILE_MIN_WAVES<T>) void k_lmc_kinv_grad(i
                                                              int n, int d, int p, int q, const T *__restrict__ ell,
                                                              const T *__restrict__ oscale, const T *__restrict__ B,
                                                              double *__restrict__ partials) {
-  // XCD-dealt 8 x 8 super-tiles (gemm_core.hpp, the order of k_kinv_grad): the tiles of a super-tile stream their strips of W through
+  // XCD-dealt 8 x 8 super-tiles (gemm_core.hpp): the tiles of a super-tile stream their strips of W through
   // one L2 (round 4; a plain (jb, ib) grid before)
   const int m = (int)(N_pad / NB);
   int lat_, ib, jb;

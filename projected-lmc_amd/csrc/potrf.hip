@@ -726,71 +726,6 @@ __global__ __launch_bounds__(B3_NT, 2) void k_gpanel_bf3(float *A, int64_t lda, 
   }
 }
 
-// K^-1 accumulation inside the sweep (with_inverse = 2).  Khat^-1 = W^T W = sum over groups of W[R]^T W[R] (R = the block
-// rows of one group): as soon as the rows R of the inverse factor are final, their rank-(128 G) contribution goes into
-// the K^-1 tiles (ib <= jb < g1) -- bulk work that is largest for the LAST groups, where the trailing updates of the
-// sweep have shrunk and the GPU would otherwise idle behind the chain.  Only rows l >= jb contribute (W[l][jb] = 0 for
-// l < jb), so tiles with jb inside the group take a shorter range and are written for the first time (plain store).
-// Storage (no extra buffer): tile (ib < jb) lives in the strictly lower triangle of the factor buffer's square part,
-// at block (jb, ib) -- the lower triangle is never read by anything else -- and the diagonal tiles (ib == jb) in a
-// strip of the Vd scratch (Kd, leading dimension NB).  grid (g1 (g1 + 1) / 2, q).
-template <typename T>
-__global__ __launch_bounds__(NTHREADS, TILE_MIN_WAVES<T>) void k_kacc(T *A, int64_t lda, int64_t strideA, const T *__restrict__ W,
-                                                    int64_t ldw, int64_t strideW, T *Kd, int64_t strideKd, int g0, int g1) {
-  __shared__ __align__(16) T smem[tile_smem_elems<T>()];
-  const int lat = blockIdx.y, t = blockIdx.x;
-  int jb = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-  while ((jb + 1) * (jb + 2) / 2 <= t) ++jb;
-  while (jb * (jb + 1) / 2 > t) --jb;
-  const int ib = t - jb * (jb + 1) / 2;
-  const bool first = jb >= g0;
-  const int r0 = first ? jb : g0;
-  const T *Wl = W + (int64_t)lat * strideW + (int64_t)r0 * NB * ldw;
-  Acc<T> acc;
-  acc.zero();
-  tile_mainloop<T, false, false>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (g1 - r0) * NB, smem);
-  T *C;
-  int64_t ldc;
-  if (ib == jb) { C = Kd + (int64_t)lat * strideKd + (int64_t)ib * NB * NB; ldc = NB; }
-  else { C = A + (int64_t)lat * strideA + (int64_t)jb * NB * lda + (int64_t)ib * NB; ldc = lda; }
-  if (first) tile_writeback<T, WB_STORE>(acc, C, ldc, smem);
-  else tile_writeback<T, WB_ADD>(acc, C, ldc, smem);
-}
-
-// The same on the split engine (fp32): the operands are the planes of the group's rows of W that the group panel and
-// k_wtri_planes already wrote into the full-height plane buffer `Wk` (family SC_SW), so the accumulation needs no pass over W
-// of its own.  Macro tile = K^-1 tiles (ibm, jb) and (ibm + 1, jb): both live at block row
-// jb of the lower triangle, side by side.  grid (g1, (g1 + 1) / 2, q); workgroups above the diagonal leave at once.
-template <class S>
-__global__ __launch_bounds__(B3_NT, 2) void k_kacc_bf3(float *A, int64_t lda, int64_t strideA, float *Kd, int64_t strideKd,
-                                                       const unsigned short *__restrict__ Wk, int64_t wk_lat_stride, int64_t n_pad, int g0, int g1,
-                                                       const float *__restrict__ sc, int64_t sc_stride) {
-  __shared__ __align__(16) unsigned char lds[b3_lds_bytes<S>()];
-  const int jb = blockIdx.x, ibm = 2 * (int)blockIdx.y, lat = blockIdx.z;
-  if (ibm > jb) return;
-  const bool first = jb >= g0;
-  const int r0 = first ? jb : g0;
-  const float sW = sc[(int64_t)lat * sc_stride + SC_SW];
-  const unsigned short *Pr = Wk + (int64_t)lat * wk_lat_stride + b3_index<S>((int64_t)r0 * NB, 0, 0, n_pad);
-  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8), ib = ibm + half;
-  const bool live = ib <= jb;
-  float *C;
-  int64_t ldc;
-  if (ib == jb) { C = Kd + (int64_t)lat * strideKd + (int64_t)ib * NB * NB; ldc = NB; }
-  else { C = A + (int64_t)lat * strideA + (int64_t)jb * NB * lda + (int64_t)ib * NB; ldc = lda; }
-  float *stg = reinterpret_cast<float *>(lds + half * B3_WB_BYTES);
-  const int tid = (int)threadIdx.x & 255;
-  Acc<float> acc0, acc1;
-  acc0.zero();
-  acc1.zero();
-  f32x4 vc0[B3_WB_NCH];
-  auto pre = [&]() { b3_preload(vc0, C, ldc, tid, live && !first); };
-  b3_mainloop<S, 2, B3_WB_NCH>(acc0, acc1, Pr + (int64_t)ibm * NB * 8, n_pad, Pr + (int64_t)jb * NB * 8, n_pad, (g1 - r0) * NB, lds, pre);
-  b3_combine<S>(acc0, acc1, 1.0f / (sW * sW));
-  if (first) b3_writeback<S, WB_STORE, false>(acc0, C, ldc, stg, tid, live);
-  else b3_writeback<S, WB_ADD, false, true>(acc0, C, ldc, stg, tid, live, nullptr, 0, true, 1.0f, vc0);
-}
-
 // ----------------------------------------------------------------------------------------------
 // z[lat][i] = A[i][n_pad + c];  quad[lat] = sum z^2 (double).  grid (q).
 template <typename T>
@@ -929,14 +864,14 @@ struct Sweep {
 
   T *A;
   int64_t n_pad, lda, strideA, naug_pad, wcol0;   // wcol0: first inverse-factor column
-  int q, m, Taug, with_inverse;
-  bool keep;
+  int q, m, Taug;
+  bool with_inverse, keep;
   const float *eig_lo = nullptr;                  // q lower bounds of the smallest eigenvalue (device), needed by SplitH2 only
   double *logdet = nullptr;                       // outputs of finish()
   int *info = nullptr;
   // Vd regions of latent 0; the per-latent strides in elements, 16-bit plane elements and floats.  The split engine's regions are
   // null unless it runs, the full-height planes of W also without the inverse factor, the kept buffers unless `keep`.
-  T *Vd, *Wg, *Vg2[2], *Ph, *Pbulk, *Kd;
+  T *Vd, *Wg, *Vg2[2], *Ph, *Pbulk;
   unsigned short *Pl[2], *Praw, *VgP2[2], *Wk, *Uk;
   float *scl;
   int64_t strideV, pl_lat, sc_lat, uk_step;       // uk_step: 16-bit elements per kept buffer
@@ -945,11 +880,11 @@ struct Sweep {
   double hthr;
   unsigned bulk_lds;
   int grp, ng, chain_pool;                        // block rows per group, groups
-  hipStream_t st, C = nullptr, H = nullptr, K = nullptr;
+  hipStream_t st, C = nullptr, H = nullptr;
   hipEvent_t e_entry = nullptr, e_v = nullptr, e_gh = nullptr, e_p = nullptr, e_hd = nullptr, e_tail = nullptr, e_doneC = nullptr,
-             e_doneH = nullptr, e_prev = nullptr, e_doneK = nullptr, e_sc = nullptr;
+             e_doneH = nullptr, e_prev = nullptr, e_sc = nullptr;
 
-  Sweep(T *A_, int64_t n_pad_, int64_t lda_, int naug, int64_t wcol0_, int64_t strideA_, T *Vd_, int q_, int with_inverse_, bool keep_,
+  Sweep(T *A_, int64_t n_pad_, int64_t lda_, int naug, int64_t wcol0_, int64_t strideA_, T *Vd_, int q_, bool with_inverse_, bool keep_,
         int grp_, unsigned bulk_lds_, hipStream_t st_)
       : A(A_), n_pad(n_pad_), lda(lda_), strideA(strideA_), naug_pad(plmc_pad(naug)), wcol0(wcol0_), q(q_), m((int)(n_pad_ / NB)),
         Taug((int)(plmc_pad(naug) / NB)), with_inverse(with_inverse_), keep(keep_), Vd(Vd_), kn(knobs()), hthr(kn.half_tiles),
@@ -961,7 +896,6 @@ struct Sweep {
     Wg = L.at<T>(Vd, L.wg);
     Ph = L.at<T>(Vd, L.ph);
     Pbulk = L.at<T>(Vd, L.pbulk);
-    Kd = L.at<T>(Vd, L.kd);
     for (int b = 0; b < 2; ++b) {
       Vg2[b] = L.at<T>(Vd, L.vg[b]);
       Pl[b] = bf3 ? L.at<unsigned short>(Vd, L.pl[b]) : nullptr;
@@ -1187,20 +1121,6 @@ struct Sweep {
                            (const float *)scl, sc_lat);
     }
   }
-  void kacc(int gi, hipStream_t s) {
-    if (with_inverse != 2) return;
-    const int g0 = G0(gi), g1 = G0(gi + 1);
-    const int nt = g1 * (g1 + 1) / 2;
-    double fl = 0.0;
-    for (int jb = 0; jb < g1; ++jb) fl += (jb + 0.5) * 2.0 * nb * nb * (double)(g1 - (jb >= g0 ? jb : g0)) * nb;   // diagonal tiles: half
-    ProfScope ps(PK_KACC, s, q * fl, q * (2.0 * nt - (double)(g1 - g0) * (g0 + g1 + 1) / 2.0) * nb * nb * esz);
-    if constexpr (bf3) {
-      hipLaunchKernelGGL((k_kacc_bf3<S>), dim3(g1, (g1 + 1) / 2, q), dim3(B3_NT), 0, s, (float *)A, lda, strideA, (float *)Kd, strideV,
-                         (const unsigned short *)Wk, pl_lat, n_pad, g0, g1, (const float *)scl, sc_lat);
-    } else {
-      hipLaunchKernelGGL((k_kacc<T>), dim3(nt, q), dim3(NTHREADS), bulk_lds, s, A, lda, strideA, (const T *)WA, lda, strideA, Kd, strideV, g0, g1);
-    }
-  }
 
   // The helper streams and ordering events of THIS caller stream (api.hip: sweeps from different streams may overlap).  True when
   // the look-ahead can run: both helper streams and its nine events exist, and the sweep has more than two groups.
@@ -1209,18 +1129,12 @@ struct Sweep {
     // PLMC_BULK_STREAMS=1: the group panel of the other columns and the head rows ride on the caller's stream, in front of the tail
     C = kn.serial ? nullptr : side_stream();
     H = kn.serial ? nullptr : (kn.bulk_streams == 1 ? st : side_stream(1));
-    // the K^-1 accumulation rides on the caller's stream behind the tail (e_tail is recorded before it, so nothing on the
-    // critical path waits for it).  A stream of its own shared a hardware queue with one of the others (HIP maps streams
-    // onto four hardware queues; with the gradient stream of the Python layer this library already uses four) and
-    // serialised the chain behind bulk launches: sweep + accumulation took exactly the sum of the two.
+    // no third helper stream: HIP maps streams onto four hardware queues, and with the gradient stream of the Python layer this
+    // library already uses four -- a further stream shares a queue with one of the others and serialises the chain behind bulk
+    // launches (an in-sweep K^-1 accumulation on a stream of its own took exactly the sum of the two)
     hipEvent_t *const ev[] = {&e_entry, &e_v, &e_gh, &e_p, &e_hd, &e_tail, &e_doneC, &e_doneH, &e_prev};
     bool la = C && H && ng > 2;
     for (int i = 0; i < 9; ++i) la = (*ev[i] = sync_event(i)) && la;
-    // split engine: the accumulation reads the full-height planes of W (rows of group gi: final behind e_p, never rewritten) and
-    // is pure filler, so it gets a (low-priority) stream of its own
-    K = (kn.serial || with_inverse != 2 || !bf3) ? nullptr : side_stream(2);
-    e_doneK = sync_event(11);
-    if (!e_doneK) K = nullptr;
     e_sc = sync_event(12);
     return la;
   }
@@ -1257,7 +1171,6 @@ struct Sweep {
         gpanel(g0, g1 - g0, cm_buf(g1, m - g1, Taug, 0, g0), gi & 1, st, 0);
         update(g1, m - g1, g0, g1 - 1, cm_buf(g1, m - g1, Taug, 0, g1), st, PK_TRAIL);
       }
-      kacc(gi, st);
     }
     return finish(st);
   }
@@ -1320,10 +1233,6 @@ struct Sweep {
       wtri_planes(gi, H);
       gpanel(g0, G, cm_buf(g2, m - g2, Taug, 0, g0), gi & 1, H, 0);              // rest of the panel columns
       (void)hipEventRecord(e_p, H);
-      if (K) {                                                                   // rows R0 of W are final and in planes: filler work
-        (void)hipStreamWaitEvent(K, e_p, 0);
-        kacc(gi, K);
-      }
       (void)hipStreamWaitEvent(H, e_gh, 0);
       if (gi > 0) (void)hipStreamWaitEvent(H, e_tail, 0);
       update(g1, g2 - g1, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), H, PK_TRAIL_HEAD, 0, 0, false, g2);   // head: rows R1, columns right of R1
@@ -1333,11 +1242,6 @@ struct Sweep {
       (void)hipStreamWaitEvent(st, e_gh, 0);
       update(g2, m - g2, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL);         // tail: rows below R1
       (void)hipEventRecord(e_tail, st);
-      if (!K) kacc(gi, st);    // rows R0 of the inverse factor are final (e_p: panel copy; e_gh is behind vtrans): filler work
-    }
-    if (K) {
-      (void)hipEventRecord(e_doneK, K);
-      (void)hipStreamWaitEvent(st, e_doneK, 0);
     }
     // log det and the pivot / abort check read the diagonal of U and the chain kernels' control words: final behind the last chain,
     // so they ride on the chain stream beside the last group's panel instead of behind the whole sweep (25 us + a launch gap)
@@ -1357,8 +1261,9 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // with_inverse & 4 (split engine, with the inverse factor): KEEP the planes of the solved rows of every group instead of
   // rolling over two buffers -- Vd then has plmc_vd_blocks_keep blocks per latent -- so that plmc_potrs_aug_kept_* can later run
   // its updates on the split engine too (the eval-mode factorisation cache)
-  const bool keep = !std::is_void<S>::value && (with_inverse_arg & 4) != 0 && (with_inverse_arg & 3) != 0;
-  const int with_inverse = with_inverse_arg & 3;
+  PLMC_REQUIRE((with_inverse_arg & 2) == 0, "with_inverse bit 1 (K^-1 accumulated in the sweep) is gone: use plmc_kinv_grad_* behind the sweep");
+  const bool with_inverse = (with_inverse_arg & 1) != 0;
+  const bool keep = !std::is_void<S>::value && (with_inverse_arg & 4) != 0 && with_inverse;
   PLMC_REQUIRE(A && Vd && logdet && info, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && lda % NB == 0 && lda >= n_pad, "n_pad/lda must be multiples of NB");
   const int64_t naug_pad = plmc_pad(naug);
@@ -1383,7 +1288,7 @@ int potrf_impl(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *V
   // whole-sweep bracket on the caller's stream (the per-kernel records of overlapped kernels add up to
   // more than the wall time once the look-ahead runs the chain beside the trailing update)
   const double npd = (double)n_pad;
-  ProfScope whole(PK_SWEEP, sw.st, q * (with_inverse == 2 ? 3.0 : (with_inverse ? 2.0 : 1.0)) * npd * npd * npd / 3.0, 0.0);
+  ProfScope whole(PK_SWEEP, sw.st, q * (with_inverse ? 2.0 : 1.0) * npd * npd * npd / 3.0, 0.0);
   sw.clear();
   return sw.bind_streams() ? sw.lookahead(job) : sw.one_stream(job);
 }
@@ -1416,7 +1321,7 @@ int potrs_aug_at(T *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0, int6
   const int64_t naug_pad = plmc_pad(naug);
   PLMC_REQUIRE(naug > 0 && q > 0 && n_pad + naug_pad <= wcol0 && wcol0 + n_pad <= lda, "augmented columns must fit between the square part and the W columns");
   PLMC_REQUIRE(aligned16(A) && aligned16(Vd), "unaligned buffer");
-  Sweep<T, void> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, 1, false, GMAX, 0u, (hipStream_t)stream);
+  Sweep<T, void> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, true, false, GMAX, 0u, (hipStream_t)stream);
   const ColMap<T> cm{0, 0, sw.Taug, 0, 0, n_pad, (T *)nullptr, lda, strideA};        // the augmented columns only
   for (int gi = 0; gi < sw.ng; ++gi) {
     const int g0 = sw.G0(gi), g1 = sw.G0(gi + 1), G = g1 - g0;
@@ -1457,7 +1362,7 @@ int potrs_aug_kept(float *A, int64_t n_pad, int64_t lda, int naug, int64_t wcol0
   const int64_t naug_pad = plmc_pad(naug);
   PLMC_REQUIRE(naug > 0 && q > 0 && n_pad + naug_pad <= wcol0 && wcol0 + n_pad <= lda, "augmented columns must fit between the square part and the W columns");
   PLMC_REQUIRE(aligned16(A) && aligned16(Vd), "unaligned buffer");
-  Sweep<float, S> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, 1, true, GMAX, 0u, (hipStream_t)stream);
+  Sweep<float, S> sw(A, n_pad, lda, naug, wcol0, strideA, Vd, q, true, true, GMAX, 0u, (hipStream_t)stream);
   const ColMap<float> cm{0, 0, sw.Taug, 0, 0, n_pad, (float *)nullptr, lda, strideA};   // the augmented columns only
   hipLaunchKernelGGL(k_scale_scan, dim3(SCAN_PARTS, q), dim3(NTHREADS), 0, sw.st, (const float *)A, n_pad, (int64_t)0, n_pad, lda, strideA, (int)naug_pad,
                      sw.scl, sw.sc_lat, 0);

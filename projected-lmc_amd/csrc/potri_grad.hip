@@ -132,7 +132,7 @@ template <typename T, int DCAP, bool SPLINE>
 __device__ __forceinline__ void kinv_tile_epilogue(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ib, int jb, int lat,
                                                    int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                    const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
-                                                   int64_t strideK, T *kinv_diag, double *__restrict__ partials, int plain) {
+                                                   int64_t strideK, T *kinv_diag, double *__restrict__ partials) {
   if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
   // 512 threads = two waves per SIMD = 256 registers: with 32 dimensions the one-pass form does not fit beside the accumulators
 #define PLMC_KINV_KEEP (DCAP <= 16)
@@ -148,21 +148,15 @@ __global__ __launch_bounds__(NTHREADS, (KG_MIN_WAVES<T, DCAP>)) void k_kinv_grad
                                                          const T *__restrict__ X, int n, int d,
                                                          const T *__restrict__ ell, const T *__restrict__ oscale,
                                                          T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag,
-                                                         double *__restrict__ partials, int nlat, int plain) {
+                                                         double *__restrict__ partials, int nlat) {
   const int m = (int)(n_pad / NB);
-  int lat, ib, jb;
-  if (plain >= 4) {                    // longest tiles first: jb ascending outermost, latent fastest
-    const int w = blockIdx.x;
-    lat = w % nlat;
-    const int t = w / nlat;
-    jb = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while ((jb + 1) * (jb + 2) / 2 <= t) ++jb;
-    while (jb * (jb + 1) / 2 > t) --jb;
-    ib = t - jb * (jb + 1) / 2;
-  } else if (plain) {                  // (jb, ib, lat) grid
-    jb = blockIdx.x; ib = blockIdx.y; lat = blockIdx.z;
-    if (jb < ib) return;
-  } else if (!xcd_tri_decode(blockIdx.x, m, nlat, lat, ib, jb)) return;   // XCD-dealt 8 x 8 super-tiles
+  // longest tiles first: jb ascending outermost, latent fastest.  A (jb, ib, lat) grid ran the long tiles of the last latent
+  // at the end of the launch: 112 vs 120 TF at n = 8192, q = 8, 97 vs 118 TF at q = 1, 77 vs 104 TF at n = 4096 (the same
+  // launch with every tile reading one panel pair ran no faster, so operand locality is not what limits it; an XCD-dealt
+  // super-tile order was level with the grid).
+  const int lat = (int)blockIdx.x % nlat;
+  int ib, jb;
+  tri_decode((int)blockIdx.x / nlat, ib, jb);
   __shared__ __align__(16) T smem[tile_smem_elems<T>()];
   const T *Wl = W + (int64_t)lat * strideW + (int64_t)jb * NB * ldw;
   Acc<T> acc;
@@ -186,14 +180,14 @@ template <class S, int DCAP, bool SPLINE = false>
 __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_pad, const float *__restrict__ alpha, const float *__restrict__ X, int n,
                                                             int d, const float *__restrict__ ell, const float *__restrict__ oscale, float *Kinv,
                                                             int64_t ldk, int64_t strideK, float *kinv_diag, double *__restrict__ partials, int nlat,
-                                                            int plain, const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
+                                                            const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
                                                             int64_t wp_lat_stride, int64_t ws_stride) {
   constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float);
   __shared__ __align__(16) unsigned char lds[LDS_BYTES];
   const int m = (int)(n_pad / NB);
   // latent-major: the ~256 resident workgroups are consecutive macro tiles of ONE matrix (a few block columns jb, all their
   // ibm): 16 + 16 operand strips instead of one B and 32 A strips per XCD and latent -- the strips are shared across the XCDs
-  // through the Infinity Cache (step 18.5 -> 18.1 ms at q = 8; PLMC_KINV_ORDER=7: latent fastest, the fp32 kernel's order)
+  // through the Infinity Cache (step 18.5 -> 18.1 ms at q = 8 against latent fastest, the fp32 kernel's order)
   // Tile order: XCD-dealt super-blocks of 4 macro rows x 8 block columns (= the 32 workgroups an XCD holds; workgroup w lands on
   // XCD w % 8), longest K range first, latent by latent.  With the K range walked from its END (every range ends at row n) the
   // 32 tiles of a block read their 4 A strips and 8 B strips in lockstep through one L2, and the blocks in flight on the eight
@@ -203,11 +197,9 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
   const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
   const int gb = xcd + 8 * (slot >> 5), in = slot & 31;
   if (gb >= nlat * NSB) return;
-  const int lat = gb / NSB, kb = gb - lat * NSB;
-  int sj = (int)((sqrtf(8.0f * (float)kb + 1.0f) - 1.0f) * 0.5f);
-  while ((sj + 1) * (sj + 2) / 2 <= kb) ++sj;
-  while (sj * (sj + 1) / 2 > kb) --sj;
-  const int sa = kb - sj * (sj + 1) / 2;
+  const int lat = gb / NSB;
+  int sa, sj;
+  tri_decode(gb - lat * NSB, sa, sj);
   const int ibm = 2 * (4 * sa + (in >> 3)), jb = 8 * sj + (in & 7);
   if (jb >= m || ibm > jb) return;
   Acc<float> acc0, acc1;
@@ -229,7 +221,7 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
   const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
   const int ib = ibm + half;
   kinv_tile_epilogue<float, DCAP, SPLINE>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind,
-                                          ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, plain);
+                                          ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials);
 }
 
 
@@ -272,131 +264,6 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad(const double *__restrict
   }
 }
 
-// ---- gradient pass over a K^-1 that the sweep accumulated (plmc_potrf_* with_inverse = 2; storage: potrf.hip, k_kacc).
-// HBM-bound: one read of the q n^2 / 2 stored elements; per upper tile the same sums as the fused epilogue above,
-//     g[k] += wt os w base df_k^2,  g_os += wt w val,  g_noise += w on the diagonal,   w = alpha_i alpha_j - Kinv_ij,
-// but with the tile coming from memory there are no accumulators to keep alive: thread = one column of the tile (its
-// scaled inputs in registers) x 64 rows (row inputs are wave-uniform LDS broadcasts); loads are whole 512-byte rows.
-// Same partials layout and fixed-order reduction (k_reduce_grad) as k_kinv_grad.  grid (m (m + 1) / 2 * q).
-template <typename T, int DCAP>
-__global__ __launch_bounds__(NTHREADS) void k_grad_tiles(int kind, const T *__restrict__ A, int64_t n_pad, int64_t lda, int64_t strideA,
-                                                         const T *__restrict__ Kd, int64_t strideKd, const T *__restrict__ alpha,
-                                                         const T *__restrict__ X, int n, int d, const T *__restrict__ ell,
-                                                         const T *__restrict__ oscale, T *kinv_diag, double *__restrict__ partials,
-                                                         int nlat) {
-  const int m = (int)(n_pad / NB);
-  const int w = blockIdx.x, lat = w % nlat, t = w / nlat;
-  int jb = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-  while ((jb + 1) * (jb + 2) / 2 <= t) ++jb;
-  while (jb * (jb + 1) / 2 > t) --jb;
-  const int ib = t - jb * (jb + 1) / 2;
-  __shared__ T ui[NB][DCAP + 1];
-  __shared__ T ai[NB];
-  __shared__ double red[4][GP];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const T *el = ell + (int64_t)lat * d;
-  for (int e = tid; e < NB * DCAP; e += NTHREADS) {
-    const int r = e / DCAP, k = e % DCAP, gi = ib * NB + r;
-    ui[r][k] = (k < d && gi < n) ? X[(int64_t)gi * d + k] / el[k] : T(0);
-  }
-  if (tid < NB) ai[tid] = alpha[(int64_t)lat * n_pad + ib * NB + tid];
-  const int col = tid & (NB - 1), rh = tid >> 7;                    // column of the tile, row parity
-  const int gj = jb * NB + col;
-  T uj[DCAP];
-#pragma unroll
-  for (int k = 0; k < DCAP; ++k) uj[k] = (k < d && gj < n) ? X[(int64_t)gj * d + k] / el[k] : T(0);
-  const T a_j = alpha[(int64_t)lat * n_pad + gj];
-  const T os = oscale ? oscale[lat] : T(1);
-  const T *Kt;
-  int64_t ldk;
-  if (ib == jb) { Kt = Kd + (int64_t)lat * strideKd + (int64_t)ib * NB * NB; ldk = NB; }
-  else { Kt = A + (int64_t)lat * strideA + (int64_t)jb * NB * lda + (int64_t)ib * NB; ldk = lda; }
-  __syncthreads();
-  T g[DCAP];
-#pragma unroll
-  for (int k = 0; k < DCAP; ++k) g[k] = T(0);
-  T g_noise = T(0), g_os = T(0);
-#pragma unroll 4
-  for (int rr = 0; rr < NB / 2; ++rr) {
-    const int row = 2 * rr + rh, gi = ib * NB + row;
-    const T kin = Kt[(int64_t)row * ldk + col];
-    if (kinv_diag && gi == gj) kinv_diag[(int64_t)lat * n_pad + gi] = kin;
-    const bool live = gi < n && gj < n && gj >= gi;
-    T wv = ai[row] * a_j - kin;
-    if (live && gi == gj) g_noise += wv;
-    wv = live ? (gj > gi ? T(2) * wv : wv) : T(0);
-    T df[DCAP];
-    T r2 = T(0), sp = T(1);
-#pragma unroll
-    for (int k = 0; k < DCAP; ++k) {
-      df[k] = ui[row][k] - uj[k];
-      r2 += df[k] * df[k];
-      if (kind == K_SPLINE) sp *= spline_factor(ui[row][k], uj[k]);
-    }
-    T val, base;
-    if (kind == K_SPLINE) { val = sp; base = T(0); }
-    else kern_value_base_fast(kind, r2, val, base);
-    g_os += wv * val;
-    const T c = wv * os * base;
-#pragma unroll
-    for (int k = 0; k < DCAP; ++k) g[k] += c * df[k] * df[k];
-  }
-  auto wave_sum = [&](double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-  };
-#pragma unroll
-  for (int k = 0; k < DCAP; ++k) {
-    double s = wave_sum((double)g[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  {
-    double s = wave_sum((double)g_noise);
-    if (lane == 0) red[wave][MAX_DIM] = s;
-    s = wave_sum((double)g_os);
-    if (lane == 0) red[wave][MAX_DIM + 1] = s;
-  }
-  __syncthreads();
-  double *out = partials + (((int64_t)lat * m + ib) * m + jb) * GP;
-  if (tid < GP) {
-    const bool lv = tid < DCAP || tid >= MAX_DIM;
-    out[tid] = lv ? red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid] : 0.0;
-  }
-}
-
-template <typename T>
-int grad_tiles_impl(int kind, const T *A, int64_t n_pad, int64_t lda, int64_t strideA, const T *Vd, const T *alpha, const T *X, int n, int d,
-                    const T *ell, const T *oscale, double *grad, T *kinv_diag, void *partials, int q, void *stream) {
-  PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
-  PLMC_REQUIRE(A && Vd && alpha && X && ell && grad && partials, "null pointer");
-  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && lda % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
-  hipStream_t st = (hipStream_t)stream;
-  const int m = (int)(n_pad / NB);
-  const VdLayout L(n_pad, lda, (int)sizeof(T), false);
-  const int64_t strideV = L.stride();
-  const T *Kd = L.at<const T>(Vd, L.kd);                             // diagonal K^-1 tiles
-  double *part = reinterpret_cast<double *>(partials);
-  const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);
-#define PLMC_LAUNCH_GT(DC) \
-  hipLaunchKernelGGL((k_grad_tiles<T, DC>), grid, block, 0, st, kind, A, n_pad, lda, strideA, Kd, strideV, alpha, X, n, d, ell, oscale, kinv_diag, part, q)
-  {
-    const double np = (double)n_pad;
-    ProfScope ps(PK_GRAD_TILES, st, 0.0, q * (np * np / 2) * sizeof(T));
-    if (d <= 4) PLMC_LAUNCH_GT(4);
-    else if (d <= 8) PLMC_LAUNCH_GT(8);
-    else if (d <= 16) PLMC_LAUNCH_GT(16);
-    else PLMC_LAUNCH_GT(32);
-  }
-#undef PLMC_LAUNCH_GT
-  {
-    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * GP * sizeof(double) / 2);
-    hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
-  }
-  return launch_status(__func__);
-}
-
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -437,18 +304,10 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   PLMC_REQUIRE(aligned16(W), "unaligned W");
   hipStream_t st = (hipStream_t)stream;
   const int m = (int)(n_pad / NB);
-  // tile order: longest K range first (jb ascending outermost, latent fastest).  The (jb, ib, lat) grid ran the
-  // long tiles of the last latent at the end of the launch: 112 -> 120 TF at n = 8192, q = 8, 97 -> 118 TF at q = 1,
-  // 77 -> 104 TF at n = 4096 (the same launch with every tile reading one panel pair ran no faster, so operand
-  // locality is not what limits it; an XCD-dealt super-tile order was level with the grid).  Dev knob
-  // PLMC_KINV_ORDER: 0 = XCD-dealt 8 x 8 super-tiles, 1 = (jb, ib, lat) grid, 5 = default order, general epilogue only.
-  const int plain = knobs().kinv_order;
-  const dim3 grid = plain >= 4 ? dim3(q * (m * (m + 1) / 2)) : plain ? dim3(m, m, q) : dim3(xcd_tri_grid(m, q)), block(NTHREADS);
   double *part = reinterpret_cast<double *>(partials);
   const double np = (double)n_pad;
   // split engine (bf3_engine.hpp): split W into k8-ordered planes behind the partials (and the q scales behind the
   // planes), then the macro-tile kernel
-  bool done = false;
   if constexpr (!std::is_void<S>::value) {
     PLMC_REQUIRE(q <= 1024, "too many latents for one scale launch");
     // the planes of W and the scale of that operand family: the ones the sweep left in its Vd scratch (plmc_kinv_grad_vd_*:
@@ -472,26 +331,25 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
     const dim3 gridb(8 * ((q * NSB + 7) / 8) * 32);                       // XCD-dealt super-blocks of 32 macro tiles (see the kernel)
 #define PLMC_LAUNCH_KB(DC, SP) \
   hipLaunchKernelGGL((k_kinv_grad_bf3<S, DC, SP>), gridb, dim3(B3_NT), 0, st, kind, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, \
-                     part, q, plain, wp, wsc, wp_lat, ws_lat)
+                     part, q, wp, wsc, wp_lat, ws_lat)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     if (d <= 4) PLMC_LAUNCH_KB(4, false);
     else if (d <= 8) PLMC_LAUNCH_KB(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KB(16, true); else PLMC_LAUNCH_KB(16, false); }
     else { if (kind == K_SPLINE) PLMC_LAUNCH_KB(32, true); else PLMC_LAUNCH_KB(32, false); }
 #undef PLMC_LAUNCH_KB
-    done = true;
-  }
+  } else {
+    const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);          // longest tiles first (see the kernel)
 #define PLMC_LAUNCH_KG(DC, SP)                                                                                       \
   hipLaunchKernelGGL((k_kinv_grad<T, DC, SP>), grid, block, 0, st, kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, \
-                     oscale, Kinv, ldk, strideK, kinv_diag, part, q, plain)
-  if (!done) {
+                     oscale, Kinv, ldk, strideK, kinv_diag, part, q)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     if (d <= 4) PLMC_LAUNCH_KG(4, false);
     else if (d <= 8) PLMC_LAUNCH_KG(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KG(16, true); else PLMC_LAUNCH_KG(16, false); }
     else { if (kind == K_SPLINE) PLMC_LAUNCH_KG(32, true); else PLMC_LAUNCH_KG(32, false); }
-  }
 #undef PLMC_LAUNCH_KG
+  }
   {
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * GP * sizeof(double) / 2);
     hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
@@ -502,16 +360,6 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
 }  // namespace plmc
 
 extern "C" {
-int plmc_grad_tiles_f32(int kind, const float *A, int64_t n_pad, int64_t lda, int64_t strideA, const float *Vd, const float *alpha,
-                        const float *X, int n, int d, const float *ell, const float *oscale, double *grad, float *kinv_diag,
-                        void *partials, int q, void *stream) {
-  return plmc::grad_tiles_impl<float>(kind, A, n_pad, lda, strideA, Vd, alpha, X, n, d, ell, oscale, grad, kinv_diag, partials, q, stream);
-}
-int plmc_grad_tiles_f64(int kind, const double *A, int64_t n_pad, int64_t lda, int64_t strideA, const double *Vd, const double *alpha,
-                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad, double *kinv_diag,
-                        void *partials, int q, void *stream) {
-  return plmc::grad_tiles_impl<double>(kind, A, n_pad, lda, strideA, Vd, alpha, X, n, d, ell, oscale, grad, kinv_diag, partials, q, stream);
-}
 // per-tile partial sums + (4-byte elements) the planes of W for the split engine (the entry points without Vd); independent of the knobs
 int64_t plmc_grad_scratch_bytes_for(int64_t n_pad, int q, int elem_bytes) {
   int64_t m = n_pad / plmc::NB;

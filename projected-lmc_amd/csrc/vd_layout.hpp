@@ -1,5 +1,5 @@
 // vd_layout.hpp -- the one description of the per-latent `Vd` scratch of the factorisation sweep (potrf.hip): where the sweep
-// puts its group scratch, panel buffers, plane buffers, scales and diagonal K^-1 tiles, and where the substitutions, the
+// puts its group scratch, panel buffers, plane buffers and scales, and where the substitutions, the
 // gradient (potri_grad.hip) and the C-ABI size queries find them.  No other file computes an offset into Vd; indexing by
 // latent or, inside a region, by group is the caller's.
 #pragma once
@@ -47,7 +47,6 @@ inline int64_t vd_wk_blocks(int64_t n_pad, int64_t lda, int elem_bytes) {
 //   scl      the scale block (SC_*)
 //   wk       full-height planes of W (n_pad rows x n_pad columns), lda >= 2 n_pad only
 //   uk       keep only: one buffer of `plane_blocks` per GMAX block rows, the solved panel rows of every group
-//   kd       the diagonal tiles of the accumulated K^-1: the last m blocks
 struct VdLayout {
   // element offsets inside wg: row 0 of the pad column holds the chain's 2 GMAX^2 tile counters, row 1 (latent 0 of a chain
   // launch) [0] finished workgroups, [1] abort, [2] tickets
@@ -57,7 +56,7 @@ struct VdLayout {
   int64_t wg, vg[2], ph, pbulk;
   int64_t pl[2] = {-1, -1}, praw = -1, vgp[2] = {-1, -1}, scl = -1, wk = -1, uk = -1;
   int64_t plane_blocks = 0;
-  int64_t kd, blocks;                     // blocks: the per-latent size
+  int64_t blocks;                         // the per-latent size
 
   VdLayout(int64_t n_pad, int64_t lda, int elem_bytes_, bool keep) : elem_bytes(elem_bytes_) {
     const int64_t m = n_pad / NB, ldb = (lda + NB - 1) / NB, grp = GMAX * (GMAX + 1);
@@ -86,8 +85,7 @@ struct VdLayout {
         b += ((m + GMAX - 1) / GMAX) * plane_blocks;
       }
     }
-    kd = b;
-    blocks = kd + m;
+    blocks = b;
   }
   int64_t stride() const { return blocks * NB * NB; }                         // per latent, in elements
   int64_t stride_u16() const { return stride() * (elem_bytes / 2); }           // ... in 16-bit plane elements

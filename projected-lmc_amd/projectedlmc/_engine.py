@@ -122,10 +122,9 @@ def _contig(t, dtype=None):
     return t.contiguous()
 
 
-def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, kacc=False):
+def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
     """Assemble Khat (+ rhs / cross-covariance columns) and run the blocked Cholesky.
-    rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info).
-    kacc: also accumulate Khat^-1 = W^T W inside the sweep (plmc_potrf with_inverse = 2; needs ws.with_inverse)."""
+    rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info)."""
     L = _hip.lib()
     dt, dev = ws.dtype, ws.device
     st = _hip.stream_ptr(dev)
@@ -145,26 +144,13 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, kacc=False):
                _hip.ptr(oscale), _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + nrhs, ws.n_pad, q, st)
     # eig_lo = the noise variances: lambda_min(K + s2 I) >= s2 -- the bound the two-plane fp16 split of the bulk fp32 products
     # scales its operands with (include/plmc.h, plmc_potrf_ex_*); ignored by the fp64 entry point
-    flags = ((2 if kacc else 1) | (4 if ws.keep_planes else 0)) if ws.with_inverse else 0
+    flags = (1 | (4 if ws.keep_planes else 0)) if ws.with_inverse else 0
     if fused:
         L.call("plmc_factorize_ex", dt, k, _hip.ptr(X), n, d, _hip.ptr(ell), _hip.ptr(oscale), _hip.ptr(noise), _hip.ptr(ws.A), ws.n_pad,
                ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st)
     else:
         L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
                _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st)
-
-
-def sweep_accumulates_kinv():
-    """PLMC_KINV_IN_SWEEP=1: the sweep accumulates Khat^-1 = W^T W group by group (plmc_potrf with_inverse = 2; fp32: on the
-    split engine from the planes of the group's rows of W, on a low-priority stream of its own) and the gradient is one
-    HBM-bound pass over it (plmc_grad_tiles).  Default: one fused K^-1 + gradient kernel behind the sweep (plmc_kinv_grad)
-    on the gradient stream.  Measured on MI355X (n = 8192, fp32; ms/step fused vs in-sweep), round 3 / split engine:
-    q = 8 18.7 / 19.4, q = 2 6.26 / 6.24, q = 1 4.77 / 4.78 (round 2 / fp32 MFMA engine: 37.4 / 37.4, 11.2 / 11.7,
-    7.6 / 8.3).  The accumulation does not hide: W is lower triangular, so (g + 1)^2 / 204 of the work belongs to group g --
-    54 % of it only becomes available with the last two of eight groups -- and until then the bulk stream is busy back to
-    back anyway (profiles/r03_sweep_phases_q8_kinv_in_sweep.txt); beside the chain it slows the chain.  It stays an
-    option."""
-    return os.environ.get("PLMC_KINV_IN_SWEEP", "0") == "1"
 
 
 def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
@@ -275,11 +261,9 @@ class ExactLatentLogProb(torch.autograd.Function):
         grad = table if table is not None else (torch.empty(q, d + 2, dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
 
-        kacc = need_grad and sweep_accumulates_kinv()
-
         def enqueue(noise_eff):
             """factorisation + everything that consumes it; returns (logp, deferred pivot check)."""
-            factorize(kind, Xc, ellc, osc, noise_eff, yc.reshape(q, 1, n), ws, kacc=kacc)
+            factorize(kind, Xc, ellc, osc, noise_eff, yc.reshape(q, 1, n), ws)
             # (the copy of `info` stays right behind the sweep: the late pivot check of a training step waits for it, and with one
             # latent per rank the host, which then still has the optimiser step and the next projection to queue, is nearly critical)
             info = _DeferredInfo(ws) if check else None
@@ -296,14 +280,9 @@ class ExactLatentLogProb(torch.autograd.Function):
                     for t in (grad, Xc, ellc, osc, noise_eff):
                         if t is not None:
                             t.record_stream(gs)
-                if kacc:
-                    L.call("plmc_grad_tiles", dt, _hip.KIND[kind], _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, _hip.ptr(ws.Vd),
-                           _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(grad), None,
-                           _hip.ptr(ws.partials), q, gst)
-                else:
-                    L.call("plmc_kinv_grad_vd", dt, _hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
-                           _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(grad),
-                           None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst)
+                L.call("plmc_kinv_grad_vd", dt, _hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
+                       _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(grad),
+                       None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst)
                 if gs is not None:
                     ws.pending = torch.cuda.Event()
                     ws.pending.record(gs)

@@ -286,6 +286,35 @@ def _schedule_independence_body(eng, n, q, dtype, osc=None, noise=(0.05, 0.5)):
     torch.cuda.empty_cache()
 
 
+def test_potrf_refuses_with_inverse_bit_1(eng):
+    """with_inverse bit 1 once asked the sweep to accumulate K^-1 itself; that path is gone.  plmc_potrf_f32 / _f64 must refuse
+    2 and 3 with an error that points to plmc_kinv_grad_*, before anything is launched: the factor buffer, log det and info
+    keep their bits."""
+    from projectedlmc import _hip
+    L = _hip.lib()
+    n, q = 300, 2
+    g = torch.Generator().manual_seed(13)
+    for dtype, suf, it in ((torch.float32, "_f32", torch.int32), (torch.float64, "_f64", torch.int64)):
+        ws = eng.Workspace(n, q, 1, dtype, torch.device(DEV), True)
+        ws.A.copy_(torch.randn(ws.A.shape, generator=g, dtype=dtype))
+        ws.logdet.fill_(-7.0)
+        ws.info.fill_(-3)
+        torch.cuda.synchronize()
+        before = ws.A.view(it).clone()
+        fn = getattr(L.cdll, "plmc_potrf" + suf)
+        for flag in (2, 3):
+            rc = fn(_hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info),
+                    flag, q, _hip.stream_ptr(torch.device(DEV)))
+            torch.cuda.synchronize()
+            err = L.cdll.plmc_last_error().decode()
+            assert rc != 0, (suf, flag)
+            assert "plmc_kinv_grad" in err, (suf, flag, err)
+            assert torch.equal(ws.A.view(it), before), (suf, flag)
+            assert bool((ws.logdet == -7.0).all()) and bool((ws.info == -3).all()), (suf, flag)
+        del ws, before
+    torch.cuda.empty_cache()
+
+
 def test_sweeps_from_three_caller_streams_overlap_safely(eng):
     """The helper streams and ordering events of the look-ahead are bound to the CALLER stream (two sets per device, api.hip):
     sweeps queued on two streams at once (own buffers) run concurrently on their own sets, a third stream takes over the least

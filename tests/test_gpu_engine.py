@@ -53,17 +53,14 @@ def test_logprob_and_grad_fp64(eng, kind, n, d, q, use_os):
 
 @pytest.mark.parametrize("n,d,q,env", [(1300, 3, 2, None), (2100, 4, 8, None), (3300, 3, 2, None), (1300, 3, 2, "PLMC_SERIAL=1"),
                                        (2100, 4, 8, "PLMC_GRP=4"), (1300, 3, 2, "PLMC_GRP=3"), (2100, 4, 8, "PLMC_HALF_TILES=0"),
-                                       (1300, 3, 2, "PLMC_HALF_TILES=1"), (1300, 3, 2, "PLMC_GRAD_STREAM=0"),
-                                       (1300, 3, 2, "PLMC_KINV_IN_SWEEP=1"), (2100, 4, 8, "PLMC_KINV_IN_SWEEP=1"),
-                                       (1300, 3, 2, "PLMC_KINV_ORDER=1"), (1300, 3, 2, "PLMC_KINV_ORDER=0"),
-                                       (1300, 3, 2, "PLMC_KINV_ORDER=5")])
+                                       (1300, 3, 2, "PLMC_HALF_TILES=1"), (1300, 3, 2, "PLMC_GRAD_STREAM=0")])
 def test_multi_group_sweep_fp64(eng, n, d, q, env, monkeypatch):
     """Sizes at which the sweep runs its look-ahead schedule (more than two groups of block rows: chain, group panel +
     head rows and tail on three streams; ragged last group), against the dense fp64 oracle; also with the look-ahead
-    off, other group sizes, half / full tiles for the small launches, the gradient stream and the tile order / general
-    epilogue of the gradient kernel switched (the dev knobs must not change results)."""
+    off, other group sizes, half / full tiles for the small launches and the gradient stream switched (the dev knobs must
+    not change results)."""
     from projectedlmc import _hip
-    if env and env.startswith(("PLMC_GRAD_STREAM", "PLMC_KINV_IN_SWEEP")):
+    if env and env.startswith("PLMC_GRAD_STREAM"):
         monkeypatch.setenv(*env.split("="))                     # Python-level knob, read per call
     elif env:
         with _hip.knob(*env.split("=")):
@@ -87,7 +84,7 @@ def _multi_group_body(eng, n, d, q):
 
 
 @pytest.mark.parametrize("n,d,q", [(1000, 8, 2), (2300, 12, 3), (4200, 5, 2)])
-def test_split_engines_against_fp32_mfma_path(eng, n, d, q, monkeypatch):
+def test_split_engines_against_fp32_mfma_path(eng, n, d, q):
     """Arithmetic of the bulk fp32 products (the depth-1024 trailing updates and group panels of the sweep, from three groups
     of block rows on, and the W^T W products of the gradient kernel; csrc/bf3_engine.hpp):
       default (PLMC_SPLIT=2): two fp16 planes per operand, scaled by bounds from the diagonal and the noise, three plane
@@ -116,14 +113,7 @@ def test_split_engines_against_fp32_mfma_path(eng, n, d, q, monkeypatch):
         b3 = run()
     with _hip.knob("PLMC_SPLIT", "0"):
         plain = run()
-    # K^-1 accumulated group by group inside the sweep (split engine: from the planes of the group's rows of W, on a filler
-    # stream) + the one-pass gradient kernel, instead of the fused K^-1 + gradient kernel behind the sweep
-    monkeypatch.setenv("PLMC_KINV_IN_SWEEP", "1")
-    h2_in_sweep = run()
-    with _hip.knob("PLMC_SPLIT", "3"):
-        b3_in_sweep = run()
-    monkeypatch.delenv("PLMC_KINV_IN_SWEEP")
-    for split in (h2, b3, h2_in_sweep, b3_in_sweep):
+    for split in (h2, b3):
         for got, base, want, tol in ((split[0], plain[0], ref[0], 1e-4), (split[1], plain[1], ref[1], 2e-3),
                                      (split[2], plain[2], ref[2], 2e-3), (split[3], plain[3], ref[4], 2e-3)):
             scale = want.abs().max()
