@@ -9,6 +9,7 @@ import torch
 
 from . import _hip
 from ._engine import get_workspace
+from ._pivot import PivotCheck
 
 
 def _load(ws, M, R):
@@ -34,9 +35,9 @@ def _factor(ws, what):
     from . import settings
     if not settings.check_cholesky.on():       # no pivot check wanted: no host sync either
         return
-    info = ws.info.cpu()
-    if bool(info.any()):
-        raise RuntimeError("%s: matrix not positive definite (first failing pivot per matrix: %s)" % (what, info.tolist()))
+    check = PivotCheck.eager(ws)
+    if check.failed():
+        raise RuntimeError("%s: matrix not positive definite (first failing pivot per matrix: %s)" % (what, check.first_bad))
 
 
 class SpdQuadLogdet(torch.autograd.Function):

@@ -8,12 +8,12 @@ What it replaces in the reference: the gpytorch evaluation chain behind
 """
 import math
 import os
-import warnings
 
 import torch
 
 from . import _hip
 from . import settings
+from ._pivot import PivotCheck, deferred_pivot_checks, walk      # noqa: F401 (deferred_pivot_checks: re-exported for callers)
 
 LOG2PI = math.log(2.0 * math.pi)
 
@@ -85,11 +85,7 @@ def get_workspace(n, q, naug, dtype, device, need_grad):
             _drop_all()
         ws = Workspace(n, q, naug, dtype, device, need_grad)
         _ws_cache[key] = ws
-    # a gradient kernel of the previous evaluation may still be reading this workspace on the gradient stream
-    pending = getattr(ws, "pending", None)
-    if pending is not None:
-        torch.cuda.current_stream(device).wait_event(pending)
-        ws.pending = None
+    _release(ws)       # a gradient kernel of the previous evaluation may still be reading this workspace on the gradient stream
     return ws
 
 
@@ -154,83 +150,20 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
 
 
 def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
-    """factorize + the jitter ladder of gpytorch's psd_safe_cholesky [gpytorch-knowledge]:
-    on a non-PD pivot retry with noise + jitter * 10^k (jitter 1e-6 fp32 / 1e-8 fp64) up to
-    settings.cholesky_max_tries, warning each time; raise if still not PD.
-    (reference call sites: experiments.py:265, projected_lmc.py:416,649)."""
+    """factorize + the jitter ladder (_pivot.walk) with the check read at once: on a non-PD pivot retry with noise + jitter.
+    Returns the jitter that was added."""
     factorize(kind, X, ell, oscale, noise, rhs, ws, Xs)
     if not settings.check_cholesky.on():
         return 0.0
-    info = ws.info.cpu()
-    _check_chain_abort(info)
-    if not bool(info.any()):
+    check = PivotCheck.eager(ws)
+    if not check.failed():
         return 0.0
-    base = settings.cholesky_jitter.value(ws.dtype)
-    tries = settings.cholesky_max_tries.value()
-    for i in range(tries):
-        jit = base * (10 ** i)
-        warnings.warn("A not p.d., added jitter of %.1e to the diagonal" % jit, RuntimeWarning)
+
+    def attempt(jit):
         factorize(kind, X, ell, oscale, noise + jit, rhs, ws, Xs)
-        info = ws.info.cpu()
-        if not bool(info.any()):
-            return jit
-    raise RuntimeError("Matrix not positive definite after repeatedly adding jitter up to %.1e "
-                       "(first failing pivot per latent: %s)" % (jit, info.tolist()))
+        return PivotCheck.eager(ws), None
 
-
-INFO_CHAIN_ABORT = 0x7ffffff0      # csrc/diag_block.hpp: the sweep's resident chain kernel gave up a bounded wait (never a pivot index)
-
-
-def _check_chain_abort(info_host):
-    if bool((info_host == INFO_CHAIN_ABORT).any()):
-        raise RuntimeError("projectedlmc: the resident chain kernel of the blocked sweep timed out waiting for another workgroup "
-                           "(internal error -- not a property of the matrix); PLMC_CHAIN=0 selects the launch-per-step chain")
-
-
-class deferred_pivot_checks:
-    """Context manager for a caller that can redo its whole forward pass: inside it the exact log-prob does not wait
-    for the pivot check of its factorisation (the host goes on queueing the rest of the forward pass while the sweep
-    runs); `failed()` after the block waits for the checks.  `jitter` is added to the noise of every factorisation
-    inside the block -- the caller's retry ladder (ProjectedLMCmll.forward) plays psd_safe_cholesky's."""
-    current = None
-
-    def __init__(self, jitter=0.0):
-        self.jitter = float(jitter)
-        self.pending = []
-        self.first_bad = None
-
-    def __enter__(self):
-        self._outer = deferred_pivot_checks.current
-        deferred_pivot_checks.current = self
-        return self
-
-    def __exit__(self, *exc):
-        deferred_pivot_checks.current = self._outer
-        return False
-
-    def failed(self):
-        bad = [i for i in self.pending if i.failed()]
-        self.first_bad = bad[0].host.tolist() if bad else None
-        return bool(bad)
-
-
-class _DeferredInfo:
-    """Pivot check of a factorisation without stalling the stream: `info` is copied to pinned host memory right
-    behind the sweep and looked at only after the kernels that follow it have been queued, so the GPU runs
-    from the sweep straight into them while the host waits for the copy (not for those kernels)."""
-
-    def __init__(self, ws):
-        if getattr(ws, "info_host", None) is None:
-            ws.info_host = torch.empty(ws.info.shape, dtype=ws.info.dtype, pin_memory=True)
-        self.host = ws.info_host
-        self.host.copy_(ws.info, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record(torch.cuda.current_stream(ws.device))
-
-    def failed(self):
-        self.event.synchronize()
-        _check_chain_abort(self.host)
-        return bool(self.host.any())
+    return walk(ws.dtype, check, attempt)[0]
 
 
 class ExactLatentLogProb(torch.autograd.Function):
@@ -262,11 +195,11 @@ class ExactLatentLogProb(torch.autograd.Function):
         check = settings.check_cholesky.on()
 
         def enqueue(noise_eff):
-            """factorisation + everything that consumes it; returns (logp, deferred pivot check)."""
+            """factorisation + everything that consumes it; returns (deferred pivot check, logp)."""
             factorize(kind, Xc, ellc, osc, noise_eff, yc.reshape(q, 1, n), ws)
             # (the copy of `info` stays right behind the sweep: the late pivot check of a training step waits for it, and with one
             # latent per rank the host, which then still has the optimiser step and the next projection to queue, is nearly critical)
-            info = _DeferredInfo(ws) if check else None
+            info = PivotCheck(ws) if check else None
             L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
                    _hip.ptr(ws.quad), q, st)
             if need_grad:
@@ -289,35 +222,26 @@ class ExactLatentLogProb(torch.autograd.Function):
             # (the three small kernels of this line are queued BEHIND the gradient kernel's launch: in front of plmc_wt_matvec they
             # sat on the serial path sweep -> alpha -> gradient kernel)
             lp = -0.5 * (ws.quad + ws.logdet + n * LOG2PI)
-            return lp, info
+            return info, lp
 
-        # jitter ladder of gpytorch's psd_safe_cholesky [gpytorch-knowledge] (see factorize_checked)
         dc = deferred_pivot_checks.current if check else None
         if dc is not None:                 # the caller owns the ladder and looks at the check after its forward pass
-            logp, info = enqueue(nzc + dc.jitter if dc.jitter > 0.0 else nzc)
+            info, logp = enqueue(nzc + dc.jitter if dc.jitter > 0.0 else nzc)
             dc.pending.append(info)
-            jit, check = dc.jitter, False
         else:
-            logp, info = enqueue(nzc)
-            jit = 0.0
-        if check and info.failed():
-            base, tries = settings.cholesky_jitter.value(dt), settings.cholesky_max_tries.value()
-            for i in range(tries):
-                jit = base * (10 ** i)
-                warnings.warn("A not p.d., added jitter of %.1e to the diagonal" % jit, RuntimeWarning)
-                ws = get_workspace(n, q, 1, dt, dev, need_grad)      # waits for the failed attempt's gradient kernel
-                logp, info = enqueue(nzc + jit)
-                if not info.failed():
-                    break
-            else:
-                raise RuntimeError("Matrix not positive definite after repeatedly adding jitter up to %.1e "
-                                   "(first failing pivot per latent: %s)" % (jit, info.host.tolist()))
+            info, logp = enqueue(nzc)
+            if check and info.failed():
+                def attempt(jit):
+                    nonlocal ws
+                    ws = get_workspace(n, q, 1, dt, dev, need_grad)      # waits for the failed attempt's gradient kernel
+                    return enqueue(nzc + jit)
+
+                logp = walk(dt, info, attempt)[1]
         if need_grad:
             ctx.save_for_backward(grad, ws.alpha[:, :n].clone())
         ctx.grad_ready = getattr(ws, "pending", None) if need_grad else None
         ctx.d = d
         ctx.has_os = oscale is not None
-        ctx.jitter = jit
         ctx.table_out = table is not None
         return logp.to(dt)
 

@@ -4,12 +4,11 @@ buffer, Kronecker-sum assembly kernel, the shared blocked sweep, and the fused g
 Replaces gpytorch's LCMKernel / MultitaskKernel evaluation + MultitaskGaussianLikelihood +
 MultitaskMultivariateNormal.log_prob + autograd that `MultitaskGPModel` triggers
 (projected_lmc.py:462-466, 586-589; experiments.py:184,233,270)."""
-import warnings
-
 import torch
 
 from . import _hip, settings
 from ._engine import Workspace, LOG2PI, _contig
+from ._pivot import PivotCheck, walk
 
 _ws = {}
 
@@ -25,7 +24,7 @@ def _workspace(N, naug, dtype, device, with_inverse):
 
 
 def _factorize(kind, X, ell, osc, B, Sigma, rhs, ws, p, Xs=None):
-    """assemble K_full (+ rhs, + cross columns) and factorise; walks gpytorch's jitter ladder on
+    """assemble K_full (+ rhs, + cross columns) and factorise; walks the jitter ladder (_pivot.walk) on
     failure (psd_safe_cholesky: jitter on the diagonal == on diag(Sigma))."""
     L = _hip.lib()
     dt, dev = ws.dtype, ws.device
@@ -48,18 +47,11 @@ def _factorize(kind, X, ell, osc, B, Sigma, rhs, ws, p, Xs=None):
                    _hip.ptr(osc), _hip.ptr(B), _hip.ptr(ws.A), ws.lda, ws.n_pad + nrhs, ws.n_pad, st)
         L.call("plmc_potrf", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
                _hip.ptr(ws.logdet), _hip.ptr(ws.info), int(ws.with_inverse), 1, st)
+        return PivotCheck.eager(ws) if settings.check_cholesky.on() else None, None
 
-    run(0.0)
-    if not settings.check_cholesky.on() or not bool(ws.info.cpu().any()):
-        return
-    base = settings.cholesky_jitter.value(dt)
-    for i in range(settings.cholesky_max_tries.value()):
-        jit = base * (10 ** i)
-        warnings.warn("A not p.d., added jitter of %.1e to the diagonal" % jit, RuntimeWarning)
-        run(jit)
-        if not bool(ws.info.cpu().any()):
-            return
-    raise RuntimeError("Matrix not positive definite after repeatedly adding jitter up to %.1e" % jit)
+    check = run(0.0)[0]
+    if check is not None and check.failed():
+        walk(dt, check, run)
 
 
 class LmcExactLogProb(torch.autograd.Function):

@@ -15,7 +15,8 @@ tile engine (`plmc_gemm_tn` through `_dense.gemm_tn`; every product is written i
 import torch
 
 from . import _hip
-from ._engine import Workspace, _contig, _DeferredInfo, _check_chain_abort
+from ._engine import Workspace, _contig
+from ._pivot import PivotCheck
 
 _ws = {}
 
@@ -30,10 +31,36 @@ def _workspace(m, q, n, dtype, device, with_inverse):
     return ws
 
 
-def _raise_if_not_pd(check):
-    """Wait for the deferred pivot check of a sweep (a copy of `info` in pinned memory + its event) and raise as the eager check did."""
+def _factorize_kzz(kind, Z, ell, oscale, jitter, ws, rhs=None, X=None, eager=False):
+    """Assemble [K_ZZ + jitter I | rhs | K_ZX] into ws and run the sweep; returns its pivot check (read at once if `eager`).
+    rhs: (q, nrhs, m) right-hand-side columns or None; X: (n, d) for cross columns K(Z, X) behind them, or None.  The number of
+    augmented columns and the inverse factor are the workspace's (ws.naug, ws.with_inverse)."""
+    L = _hip.lib()
+    dt, dev = ws.dtype, ws.device
+    st = _hip.stream_ptr(dev)
+    k = _hip.KIND[kind]
+    m, d = Z.shape
+    q = ws.q
+    jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
+    L.call("plmc_assemble", dt, k, _hip.ptr(Z), m, d, _hip.ptr(ell), _hip.ptr(oscale), _hip.ptr(jit),
+           _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
+    if ws.naug_pad > 0:
+        L.call("plmc_write_rhs", dt, _hip.ptr(rhs), 0 if rhs is None else rhs.shape[1], m, _hip.ptr(ws.A), ws.lda, ws.strideA, 0,
+               ws.naug_pad, q, st)
+    if X is not None:
+        L.call("plmc_assemble_cross", dt, k, _hip.ptr(Z), m, _hip.ptr(X), X.shape[0], d, _hip.ptr(ell), _hip.ptr(oscale),
+               _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad, ws.n_pad, q, st)
+    # eig_lo = the jitter: lambda_min(K_ZZ + jitter I) >= jitter (bound for the fp16 split of the bulk fp32 products)
+    L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
+           _hip.ptr(ws.logdet), _hip.ptr(ws.info), int(ws.with_inverse), q, _hip.ptr(jit), st)
+    return PivotCheck.eager(ws) if eager else PivotCheck(ws)
+
+
+def _raise_if_not_pd(check, pivots=True):
+    """Wait for the pivot check of a K_ZZ sweep and raise if a pivot failed."""
     if check.failed():
-        raise RuntimeError("K_ZZ + jitter not positive definite (first failing pivot per latent: %s)" % check.host.tolist())
+        raise RuntimeError("K_ZZ + jitter not positive definite"
+                           + (" (first failing pivot per latent: %s)" % check.first_bad if pivots else ""))
 
 
 def kernel_vjp(kind, X1, X2, ell, oscale, G):
@@ -60,29 +87,17 @@ class WhitenedInterp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Z, X, ell, oscale, kind, jitter):
         _hip.require_device(Z, X, ell)
-        L = _hip.lib()
         dt, dev = ell.dtype, ell.device
-        m, d = Z.shape
+        m = Z.shape[0]
         n = X.shape[0]
         q = ell.shape[0]
         need_grad = any(ctx.needs_input_grad[:4])
         Zc, Xc, ellc, osc = (_contig(t, dt) for t in (Z, X, ell, oscale))
         ws = _workspace(m, q, n, dt, dev, need_grad)
-        st = _hip.stream_ptr(dev)
-        k = _hip.KIND[kind]
-        jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
-        L.call("plmc_assemble", dt, k, _hip.ptr(Zc), m, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(jit),
-               _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
-        L.call("plmc_write_rhs", dt, None, 0, m, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
-        L.call("plmc_assemble_cross", dt, k, _hip.ptr(Zc), m, _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc),
-               _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad, ws.n_pad, q, st)
-        # eig_lo = the jitter: lambda_min(K_ZZ + jitter I) >= jitter (bound for the fp16 split of the bulk fp32 products)
-        L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, n, ws.strideA, _hip.ptr(ws.Vd),
-               _hip.ptr(ws.logdet), _hip.ptr(ws.info), int(need_grad), q, _hip.ptr(jit), st)
         # the pivot check does not stall the step: `info` goes to pinned host memory behind the sweep and is looked at in
-        # backward() (the whole forward pass -- the ELBO's contractions -- is queued by then; the pattern of
-        # _engine._DeferredInfo); without a backward pass (no gradient needed) it is looked at now
-        check = _DeferredInfo(ws)
+        # backward() (the whole forward pass -- the ELBO's contractions -- is queued by then; _pivot.PivotCheck, VERDICT r3
+        # item 6); without a backward pass (no gradient needed) it is looked at now
+        check = _factorize_kzz(kind, Zc, ellc, osc, jitter, ws, X=Xc)
         ctx.pivot_check = check if need_grad else None
         if not need_grad:
             _raise_if_not_pd(check)
@@ -171,22 +186,14 @@ class GaussianKLToKernelPrior(torch.autograd.Function):
     @staticmethod
     def forward(ctx, Z, ell, oscale, mvar, Ls, kind, jitter):
         _hip.require_device(Z, ell, mvar, Ls)
-        L = _hip.lib()
         dt, dev = ell.dtype, ell.device
-        n, d = Z.shape
+        n = Z.shape[0]
         q = ell.shape[0]
         Zc, ellc, osc = (_contig(t, dt) for t in (Z, ell, oscale))
         rhs = torch.cat([mvar.detach().to(dt).unsqueeze(-1), torch.tril(Ls.detach().to(dt))], -1)     # (q, n, n+1)
         rhs_t = rhs.transpose(-1, -2).contiguous()                                                  # write_rhs wants (q, nrhs, n)
         ws = _workspace(n, q, n + 1, dt, dev, True)
-        st = _hip.stream_ptr(dev)
-        jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
-        L.call("plmc_assemble", dt, _hip.KIND[kind], _hip.ptr(Zc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(jit),
-               _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
-        L.call("plmc_write_rhs", dt, _hip.ptr(rhs_t), n + 1, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
-        L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, n + 1, ws.strideA, _hip.ptr(ws.Vd),
-               _hip.ptr(ws.logdet), _hip.ptr(ws.info), 1, q, _hip.ptr(jit), st)
-        check = _DeferredInfo(ws)                                                      # looked at in backward() (see WhitenedInterp)
+        check = _factorize_kzz(kind, Zc, ellc, osc, jitter, ws, rhs=rhs_t)             # looked at in backward() (see WhitenedInterp)
         ctx.pivot_check = check if any(ctx.needs_input_grad[:5]) else None
         if ctx.pivot_check is None:
             _raise_if_not_pd(check)
@@ -226,45 +233,25 @@ def gaussian_kl_to_kernel_prior(kind, Z, ell, oscale, mvar, Ls, jitter):
 
 def prior_cholesky(kind, Z, ell, oscale, jitter):
     """Lower Cholesky factors of K_ZZ + jitter I (q, n, n), no gradient: the first-call initialisation of q(u)."""
-    L = _hip.lib()
     dt, dev = ell.dtype, ell.device
-    n, d = Z.shape
+    n = Z.shape[0]
     q = ell.shape[0]
     Zc, ellc, osc = (_contig(t, dt) for t in (Z, ell, oscale))
     ws = _workspace(n, q, 0, dt, dev, False)
-    st = _hip.stream_ptr(dev)
-    jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
-    L.call("plmc_assemble", dt, _hip.KIND[kind], _hip.ptr(Zc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(jit),
-           _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
-    L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, 0, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet),
-           _hip.ptr(ws.info), 0, q, _hip.ptr(jit), st)
-    if bool(ws.info.cpu().any()):
-        raise RuntimeError("K_ZZ + jitter not positive definite")
+    _raise_if_not_pd(_factorize_kzz(kind, Zc, ellc, osc, jitter, ws, eager=True), pivots=False)
     return torch.triu(ws.A[:, :n, :n]).transpose(-1, -2).contiguous()
 
 
 def unwhitened_predictive(kind, Z, X, ell, oscale, mvar, Ls, jitter):
     """Marginal q(f(X)) for X != Z (eval mode), no gradient:  B = Khat^-1 K_ZX,
     mean = B^T m,  var = k(x,x) - colsum((U^-T K_ZX)^2) + colsum((Ls^T B)^2)."""
-    L = _hip.lib()
     dt, dev = ell.dtype, ell.device
-    n, d = Z.shape
+    n = Z.shape[0]
     ns = X.shape[0]
     q = ell.shape[0]
     Zc, Xc, ellc, osc = (_contig(t, dt) for t in (Z, X, ell, oscale))
     ws = _workspace(n, q, ns, dt, dev, True)
-    st = _hip.stream_ptr(dev)
-    k = _hip.KIND[kind]
-    jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
-    L.call("plmc_assemble", dt, k, _hip.ptr(Zc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(jit), _hip.ptr(ws.A),
-           ws.lda, ws.strideA, q, st)
-    L.call("plmc_write_rhs", dt, None, 0, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
-    L.call("plmc_assemble_cross", dt, k, _hip.ptr(Zc), n, _hip.ptr(Xc), ns, d, _hip.ptr(ellc), _hip.ptr(osc),
-           _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad, ws.n_pad, q, st)
-    L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ns, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet),
-           _hip.ptr(ws.info), 1, q, _hip.ptr(jit), st)
-    if bool(ws.info.cpu().any()):
-        raise RuntimeError("K_ZZ + jitter not positive definite")
+    _raise_if_not_pd(_factorize_kzz(kind, Zc, ellc, osc, jitter, ws, X=Xc, eager=True), pivots=False)
     C = ws.A[:, :n, ws.n_pad:ws.n_pad + ns]                                          # U^-T K_ZX
     from ._dense import gemm_tn, TRI_A_LOWER
     B = gemm_tn(torch.tril(ws.W[:, :n, :n]), C, TRI_A_LOWER)                         # Khat^-1 K_ZX = W^T C

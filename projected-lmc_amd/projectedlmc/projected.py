@@ -14,6 +14,7 @@ import torch
 from torch.nn.utils import parametrize
 
 from . import _engine
+from . import _pivot
 from . import settings
 from . import _qr
 from . import kernels as _k
@@ -444,7 +445,7 @@ class ProjectedLMCmll(ExactMarginalLogLikelihood):
             return self._forward_once(latent_function_dist, target, inputs, *params)
         self._settle_late_check()
         args = (latent_function_dist, target, inputs) + tuple(params)
-        with _engine.deferred_pivot_checks(0.0) as dc:
+        with _pivot.deferred_pivot_checks(0.0) as dc:
             res = self._forward_once(*args)
         if (settings.late_pivot_check.on() and os.environ.get("PLMC_LATE_CHECK", "1") != "0" and torch.is_grad_enabled()
                 and res.requires_grad and self.model.training):
@@ -460,17 +461,11 @@ class ProjectedLMCmll(ExactMarginalLogLikelihood):
 
     def _jitter_ladder(self, args, dc):
         """The forward pass again with jitter 1e-6 (fp32) x 10^i -- gpytorch's psd_safe_cholesky [gpytorch-knowledge]."""
-        base, tries = settings.cholesky_jitter.value(args[1].dtype), settings.cholesky_max_tries.value()
-        jit = 0.0
-        for i in range(tries):
-            jit = base * (10 ** i)
-            warnings.warn("A not p.d., added jitter of %.1e to the diagonal" % jit, RuntimeWarning)
-            with _engine.deferred_pivot_checks(jit) as dc:
-                res = self._forward_once(*args)
-            if not dc.failed():
-                return res
-        raise RuntimeError("Matrix not positive definite after repeatedly adding jitter up to %.1e "
-                           "(first failing pivot per latent: %s)" % (jit, dc.first_bad))
+        def attempt(jit):
+            with _pivot.deferred_pivot_checks(jit) as dc:
+                return dc, self._forward_once(*args)
+
+        return _pivot.walk(args[1].dtype, dc, attempt)[1]
 
     def _settle_late_check(self):
         """A late check whose backward pass never ran (a loss evaluated with gradients on and dropped) is looked at now: by the

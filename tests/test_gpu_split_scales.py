@@ -236,8 +236,8 @@ def test_kept_factor_prediction_scales_bits_and_mean(eng):
         outs[sched] = (mean.clone(), var.clone(), ws.A.clone())
         cache.drop()
         del ws
-    for a, b in zip(outs["fused"], outs["two-call"]):
-        assert torch.equal(a, b), "cached prediction differs between a fused and a two-call caching sweep"
+    for a, b in zip(outs["fused"], outs["two-call"]):      # as bit patterns: a NaN left in a part of the buffer that no launch writes is unequal to itself
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)), "cached prediction differs between a fused and a two-call caching sweep"
     mu, cov = gm.exact_gp_posterior("matern", X, ell, noise, y2, Xs2, osc, 2.5)
     mean = outs["fused"][0].cpu().double()
     assert (mean - mu).abs().max() < 2e-4 * max(1.0, float(mu.abs().max()))

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "projected-lmc_amd")]
 import torch
 import projectedlmc as plmc
-from projectedlmc import _engine, _hip
+from projectedlmc import _engine, _hip, _pivot
 
 q = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 n, d, p = 8192, 8, 16
@@ -28,10 +28,10 @@ orig_factorize = _engine.factorize
 def timed_factorize(*a, **k):
     t0 = time.perf_counter(); r = orig_factorize(*a, **k); tick("  engine: factorize enqueue (assemble+rhs+potrf)", t0); return r
 _engine.factorize = timed_factorize
-orig_failed = _engine._DeferredInfo.failed
+orig_failed = _pivot.PivotCheck.failed
 def timed_failed(self):
     t0 = time.perf_counter(); r = orig_failed(self); tick("  engine: wait for pivot check (GPU sweep)", t0); return r
-_engine._DeferredInfo.failed = timed_failed
+_pivot.PivotCheck.failed = timed_failed
 orig_pd = model.project_data
 def timed_pd(Yv):
     t0 = time.perf_counter(); r = orig_pd(Yv); tick("  mll: project_data", t0); return r
