@@ -305,6 +305,52 @@ int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
                           double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
 
 /*
+ * Additive kernels: a sum of `ncomp` scaled ARD sub-kernels of ONE stationary kind (the reference's `decomp` constructor argument,
+ * handle_covar_ :131-167: k(x, x') = sum_g s_g k_g(x[idx_g], x'[idx_g]), batch_shape = [n_funcs]) on the batched exact engine:
+ *     Khat_i = sum_{g < ncomp} oscale[i][g] k(|(x - x') / ell[i][g][:]|) + noise[i] I,     1 <= ncomp <= plmc_max_components().
+ * Component table, per latent i:  ell (q x ncomp x d, contiguous) holds d lengthscale slots per component; a dimension k outside
+ *   component g has ell[i][g][k] = +inf, i.e. 1 / ell = 0 exactly: it adds nothing to that component's distance.  oscale
+ *   (q x ncomp) or NULL (all ones).  noise: q.  Stationary kinds only; PLMC_SPLINE is an argument error.
+ * Every entry point takes the arguments of its single-kernel form with `ncomp` in front of `ell`, and does what that form does:
+ *   plmc_assemble_add_*        plmc_assemble_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_add_*  plmc_assemble_cross_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_add_ex_*    plmc_factorize_ex_*    (assembly overlapped with the sweep; bit-identical to the two calls)
+ *   plmc_kinv_grad_add_vd_*    plmc_kinv_grad_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ * The inputs are staged raw; x - x' is formed once per element and scaled per component.  ncomp = 1 IS the single-kernel entry point:
+ * the same kernel instantiations on ell (q x 1 x d) = (q x d), bit-identical output and the gradient layout below with ncomp = 1.
+ * Gradient table of plmc_kinv_grad_add_vd_* (double), ncomp (d + 1) + 1 entries per latent:
+ *     grad[latent] = [ d logp / d ell: ncomp x d | d / d noise | d / d oscale: ncomp ]
+ *   with d / d ell[g][k] = 0 exactly where ell[g][k] = +inf.  `partials`: the scratch of plmc_kinv_grad_vd_* for q * ncomp latents
+ *   (plmc_grad_partials_bytes(n_pad, q * ncomp), resp. plmc_grad_scratch_bytes_for(n_pad, q * ncomp, elem_bytes) where the planes of W
+ *   are not taken from Vd): one row of partial sums per tile AND component.
+ */
+int plmc_max_components(void);                /* most components of an additive kernel (4) */
+int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
+                          const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_add_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale,
+                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp,
+                                const float *ell, const float *oscale, float *Out, int64_t ldo,
+                                int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream);
+int plmc_assemble_cross_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp,
+                                const double *ell, const double *oscale, double *Out, int64_t ldo,
+                                int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream);
+int plmc_factorize_add_ex_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
+                              const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,
+                              double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale,
+                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd,
+                              double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_add_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW,
+                              const float *alpha, const float *X, int n, int d, int ncomp, const float *ell,
+                              const float *oscale, double *grad, float *Kinv, int64_t ldk, int64_t strideK,
+                              float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW,
+                              const double *alpha, const double *X, int n, int d, int ncomp, const double *ell,
+                              const double *oscale, double *grad, double *Kinv, int64_t ldk, int64_t strideK,
+                              double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

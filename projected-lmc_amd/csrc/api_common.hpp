@@ -10,6 +10,7 @@
 namespace plmc {
 
 constexpr int MAX_DIM = 32;          // largest input dimension handled by the fused kernels
+constexpr int MAX_COMP = 4;          // most components of an additive kernel (plmc_max_components())
 
 char *err_buf();                     // thread-local, defined in api.hip
 
@@ -63,9 +64,11 @@ const Knobs &knobs();
 
 // Covariance assembly handed to the sweep (plmc_factorize_ex_*): the sweep queues the rows of its first group on the caller's stream and
 // the rest on a helper stream beside the first group's chain, instead of the caller assembling the whole matrix in front of the sweep
+// ncomp > 1: an additive kernel (plmc_factorize_add_ex_*), ell (q, ncomp, d) and oscale (q, ncomp)
 struct AssembleJob {
   int kind, n, d;
   const void *X, *ell, *oscale, *noise;
+  int ncomp = 1;
 };
 // block rows ib0 .. ib0 + nrows - 1 of the covariance matrices (assemble.hip), the first ncols block columns (< 0: all) without the
 // leading skip x skip block triangle; elem_bytes 4 / 8

@@ -223,6 +223,217 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross(int kind, const T *
   }
 }
 
+// ---- additive kernels: K = sum_{g < G} os_g k(|(x - x') / ell_g|) + noise I, G <= MAX_COMP components of one stationary kind, each with
+// its own d lengthscales; ell_g[k] = +inf (1 / ell = 0) takes dimension k out of component g.  The inputs are staged RAW, once: the
+// differences x - x' are formed once per element and scaled per component (one rounding each), so a component costs d multiplies,
+// d multiply-adds and one kernel profile.  Same tiling, padding and row-range interface as the kernels above.
+template <typename T, int DCAP, int KIND>
+__device__ __forceinline__ void assemble_tile_add(const T *xi, const T *xj, int ldu, const T *w, const T *osl, int G, T nz, T *Al, int64_t lda,
+                                                  int ib, int jb, int n, bool edge) {
+  typedef Pair<T> T2;
+  const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+  const int c0 = tx * 4;
+  T2 x2[2][DCAP];                                         // [pair][k]
+#pragma unroll
+  for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) x2[pp][k] = T2{xj[(c0 + 2 * pp) * ldu + k], xj[(c0 + 2 * pp + 1) * ldu + k]};
+#pragma unroll 1
+  for (int rr = 0; rr < 16; ++rr) {
+    const int r = ty + 8 * rr;
+    const int gi = ib * NB + r;
+    T xr[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) xr[k] = xi[r * ldu + k];
+    T2 v[2];
+#pragma unroll
+    for (int pp = 0; pp < 2; ++pp) {
+      T2 df[DCAP];
+#pragma unroll
+      for (int k = 0; k < DCAP; ++k) df[k] = xr[k] - x2[pp][k];
+      T2 sum = {T(0), T(0)};
+#pragma unroll 1
+      for (int g = 0; g < G; ++g) {
+        T2 r2 = {T(0), T(0)};
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) {
+          const T2 sd = df[k] * w[g * DCAP + k];
+          r2 += sd * sd;
+        }
+        sum += osl[g] * kern_value_pair<T>(KIND, r2);
+      }
+      v[pp] = sum;
+    }
+    T o[4] = {v[0].x, v[0].y, v[1].x, v[1].y};
+    if (edge) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int gj = jb * NB + c0 + c;
+        if (gi < n && gj < n) { if (gi == gj) o[c] += nz; }
+        else o[c] = (gi == gj) ? T(1) : T(0);             // identity padding keeps the padded factor trivial
+      }
+    }
+    T *dst = Al + (int64_t)gi * lda + jb * NB + c0;
+    using vec_t = typename Traits<T>::vec_t;
+    constexpr int EPV = Traits<T>::EPV;
+#pragma unroll
+    for (int c = 0; c < 4; c += EPV) {
+      vec_t o4;
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) o4[e] = o[c + e];
+      *reinterpret_cast<vec_t *>(dst + c) = o4;
+    }
+  }
+}
+
+// d <= 8 (DCAP in {4, 8}); ell: (q, G, d), oscale: (q, G) or null
+template <typename T, int DCAP>
+__global__ __launch_bounds__(NTHREADS) void k_assemble_small_add(int kind, const T *__restrict__ X, int n, int d, int G,
+                                                                  const T *__restrict__ ell, const T *__restrict__ oscale,
+                                                                  const T *__restrict__ noise, T *__restrict__ A,
+                                                                  int64_t lda, int64_t strideA, int ib0, int skip) {
+  const int jb = blockIdx.x, ib = ib0 + blockIdx.y, lat = blockIdx.z;
+  if (jb < ib || (ib < skip && jb < skip)) return;
+  constexpr int ldu = DCAP + 1;
+  __shared__ T xi[NB * ldu], xj[NB * ldu], w[MAX_COMP * DCAP], osl[MAX_COMP];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < NB * DCAP; e += NTHREADS) {      // unused dimensions: zeros (they add 0 to every distance)
+    const int r = e / DCAP, k = e % DCAP;
+    const int gi = ib * NB + r, gj = jb * NB + r;
+    xi[r * ldu + k] = (k < d && gi < n) ? X[(int64_t)gi * d + k] : T(0);
+    xj[r * ldu + k] = (k < d && gj < n) ? X[(int64_t)gj * d + k] : T(0);
+  }
+  if (tid < G * DCAP) {
+    const int g = tid / DCAP, k = tid % DCAP;
+    w[tid] = k < d ? T(1) / ell[((int64_t)lat * G + g) * d + k] : T(0);
+  }
+  if (tid < G) osl[tid] = oscale ? oscale[(int64_t)lat * G + tid] : T(1);
+  __syncthreads();
+  const T nz = noise[lat];
+  T *Al = A + (int64_t)lat * strideA;
+  const bool edge = ib == jb || (jb + 1) * NB > n;
+  if (kind == K_RBF) assemble_tile_add<T, DCAP, K_RBF>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
+  else if (kind == K_MATERN12) assemble_tile_add<T, DCAP, K_MATERN12>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
+  else if (kind == K_MATERN32) assemble_tile_add<T, DCAP, K_MATERN32>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
+  else assemble_tile_add<T, DCAP, K_MATERN52>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
+}
+
+// any d <= MAX_DIM: the thread layout of k_assemble; dynamic LDS: xi, xj [128][d + 1], w [G][d], os [G]
+template <typename T>
+__global__ __launch_bounds__(NTHREADS) void k_assemble_add(int kind, const T *__restrict__ X, int n, int d, int G,
+                                                            const T *__restrict__ ell, const T *__restrict__ oscale,
+                                                            const T *__restrict__ noise, T *__restrict__ A,
+                                                            int64_t lda, int64_t strideA, int ib0, int skip) {
+  const int jb = blockIdx.x, ib = ib0 + blockIdx.y, lat = blockIdx.z;
+  if (jb < ib || (ib < skip && jb < skip)) return;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T *xi = reinterpret_cast<T *>(smem_raw);
+  const int ldu = d + 1;
+  T *xj = xi + NB * ldu, *w = xj + NB * ldu, *osl = w + G * d;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < NB * d; e += NTHREADS) {
+    const int r = e / d, k = e % d;
+    const int gi = ib * NB + r, gj = jb * NB + r;
+    xi[r * ldu + k] = gi < n ? X[(int64_t)gi * d + k] : T(0);
+    xj[r * ldu + k] = gj < n ? X[(int64_t)gj * d + k] : T(0);
+  }
+  if (tid < G * d) w[tid] = T(1) / ell[(int64_t)lat * G * d + tid];
+  if (tid < G) osl[tid] = oscale ? oscale[(int64_t)lat * G + tid] : T(1);
+  __syncthreads();
+  const T nz = noise[lat];
+  T *Al = A + (int64_t)lat * strideA;
+  const int tx = tid & 15, ty = tid >> 4;
+#pragma unroll 1
+  for (int rr = 0; rr < 8; ++rr) {
+    const int r = ty + 16 * rr;
+    const int gi = ib * NB + r;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int c0 = tx * 4 + 64 * h;
+      T v[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int gj = jb * NB + c0 + c;
+        T val = T(0);
+        for (int g = 0; g < G; ++g) {
+          T r2 = T(0);
+          for (int k = 0; k < d; ++k) {
+            const T sd = (xi[r * ldu + k] - xj[(c0 + c) * ldu + k]) * w[g * d + k];
+            r2 += sd * sd;
+          }
+          val += osl[g] * kern_value<T>(kind, r2);
+        }
+        if (gi < n && gj < n) {
+          if (gi == gj) val += nz;
+        } else {
+          val = (gi == gj) ? T(1) : T(0);       // identity padding keeps the padded factor trivial
+        }
+        v[c] = val;
+      }
+      T *dst = Al + (int64_t)gi * lda + jb * NB + c0;
+      using vec_t = typename Traits<T>::vec_t;
+      constexpr int EPV = Traits<T>::EPV;
+#pragma unroll
+      for (int c = 0; c < 4; c += EPV) {
+        vec_t o;
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) o[e] = v[c + e];
+        *reinterpret_cast<vec_t *>(dst + c) = o;
+      }
+    }
+  }
+}
+
+// Out[i][col0 + j] = sum_g os_g k(x_i, xs_j; ell_g): the workgroup shape of k_assemble_cross, raw coordinates, the differences scaled per component
+template <typename T, int DCAP>
+__global__ __launch_bounds__(NTHREADS) void k_assemble_cross_add(int kind, const T *__restrict__ X, int n,
+                                                                  const T *__restrict__ Xs, int ns, int d, int G,
+                                                                  const T *__restrict__ ell, const T *__restrict__ oscale,
+                                                                  T *__restrict__ A, int64_t n_rows, int64_t lda,
+                                                                  int64_t strideA, int64_t col0) {
+  __shared__ T xi[CROSS_ROWS][DCAP + 1];
+  __shared__ T w[MAX_COMP * DCAP], osl[MAX_COMP];
+  const int lat = blockIdx.z;
+  const int j = blockIdx.x * NTHREADS + threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.y * CROSS_ROWS;
+  for (int e = threadIdx.x; e < CROSS_ROWS * DCAP; e += NTHREADS) {
+    const int r = e / DCAP, k = e % DCAP;
+    xi[r][k] = (k < d && i0 + r < n) ? X[(i0 + r) * d + k] : T(0);
+  }
+  if ((int)threadIdx.x < G * DCAP) {
+    const int g = threadIdx.x / DCAP, k = threadIdx.x % DCAP;
+    w[threadIdx.x] = k < d ? T(1) / ell[((int64_t)lat * G + g) * d + k] : T(0);
+  }
+  if ((int)threadIdx.x < G) osl[threadIdx.x] = oscale ? oscale[(int64_t)lat * G + threadIdx.x] : T(1);
+  T xs[DCAP];
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) xs[k] = (k < d && j < ns) ? Xs[(int64_t)j * d + k] : T(0);
+  __syncthreads();
+  if (j >= ns) return;
+  T *out = A + (int64_t)lat * strideA + i0 * lda + col0 + j;
+#pragma unroll 1
+  for (int r = 0; r < CROSS_ROWS; ++r) {
+    if (i0 + r >= n_rows) break;
+    T val = T(0);
+    if (i0 + r < n) {
+      T df[DCAP];
+#pragma unroll
+      for (int k = 0; k < DCAP; ++k) df[k] = xi[r][k] - xs[k];
+#pragma unroll 1
+      for (int g = 0; g < G; ++g) {
+        T r2 = T(0);
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) {
+          const T sd = df[k] * w[g * DCAP + k];
+          r2 += sd * sd;
+        }
+        val += osl[g] * kern_value<T>(kind, r2);
+      }
+    }
+    out[(int64_t)r * lda] = val;
+  }
+}
+
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
 template <typename T>
@@ -290,8 +501,70 @@ int assemble_cross_impl(int kind, const T *X, int n, const T *Xs, int ns, int d,
   return launch_status(__func__);
 }
 
+// the additive forms.  One component is the plain kernel (ell (q, 1, d) is ell (q, d)): the existing instantiations, bit for bit
+#define PLMC_REQUIRE_ADD(kind, G)                                                                                     \
+  PLMC_REQUIRE(kind >= 0 && kind <= K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)"); \
+  PLMC_REQUIRE(G >= 1 && G <= MAX_COMP, "need 1 <= components <= plmc_max_components()")
+template <typename T>
+int assemble_add_impl(int kind, const T *X, int n, int d, int G, const T *ell, const T *oscale, const T *noise, T *A,
+                      int64_t lda, int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
+  PLMC_REQUIRE_ADD(kind, G);
+  if (G == 1) return assemble_impl<T>(kind, X, n, d, ell, oscale, noise, A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+  PLMC_REQUIRE(X && ell && noise && A, "null pointer");
+  PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, "need n>0, q>0, 0<d<=plmc_max_dim()");
+  const int64_t n_pad = plmc_pad(n);
+  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
+  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
+  const int m = (int)(n_pad / NB);
+  if (nrows < 0) nrows = m - ib0;
+  if (ncols < 0) ncols = m;
+  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
+  if (nrows == 0 || ncols == 0) return 0;
+  const size_t smem = (2 * NB * (d + 1) + G * d + G) * sizeof(T);
+  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
+  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
+  const dim3 grid(ncols, nrows, q);
+  if (d <= 4)
+    hipLaunchKernelGGL((k_assemble_small_add<T, 4>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A,
+                       lda, strideA, ib0, skip);
+  else if (d <= 8)
+    hipLaunchKernelGGL((k_assemble_small_add<T, 8>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A,
+                       lda, strideA, ib0, skip);
+  else
+    hipLaunchKernelGGL(k_assemble_add<T>, grid, dim3(NTHREADS), smem, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A, lda,
+                       strideA, ib0, skip);
+  return launch_status(__func__);
+}
+
+template <typename T>
+int assemble_cross_add_impl(int kind, const T *X, int n, const T *Xs, int ns, int d, int G, const T *ell, const T *oscale, T *Out,
+                            int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
+  PLMC_REQUIRE_ADD(kind, G);
+  if (G == 1) return assemble_cross_impl<T>(kind, X, n, Xs, ns, d, ell, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
+  PLMC_REQUIRE(X && Xs && ell && Out, "null pointer");
+  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0 && d > 0 && d <= MAX_DIM, "bad sizes");
+  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
+  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
+  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
+#define PLMC_CROSS(DC) \
+  hipLaunchKernelGGL((k_assemble_cross_add<T, DC>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, Xs, ns, d, G, ell, oscale, Out, n_rows, ldo, strideO, col0)
+  if (d <= 4) PLMC_CROSS(4);
+  else if (d <= 8) PLMC_CROSS(8);
+  else if (d <= 16) PLMC_CROSS(16);
+  else PLMC_CROSS(32);
+#undef PLMC_CROSS
+  return launch_status(__func__);
+}
+
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,
                   int ncols, int skip) {
+  if (job.ncomp != 1) {                               // additive kernel (plmc_factorize_add_ex_*)
+    if (elem_bytes == 4)
+      return assemble_add_impl<float>(job.kind, (const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.oscale,
+                                      (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+    return assemble_add_impl<double>(job.kind, (const double *)job.X, job.n, job.d, job.ncomp, (const double *)job.ell, (const double *)job.oscale,
+                                     (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+  }
   if (elem_bytes == 4)
     return assemble_impl<float>(job.kind, (const float *)job.X, job.n, job.d, (const float *)job.ell, (const float *)job.oscale, (const float *)job.noise,
                                 (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
@@ -328,5 +601,26 @@ int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, 
                             int64_t n_rows, int q, void *stream) {
   return plmc::assemble_cross_impl<double>(kind, X, n, Xs, ns, d, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
                                            stream);
+}
+int plmc_max_components(void) { return plmc::MAX_COMP; }
+int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
+                          const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_add_impl<float>(kind, X, n, d, ncomp, ell, oscale, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_add_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale,
+                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_add_impl<double>(kind, X, n, d, ncomp, ell, oscale, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_cross_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell,
+                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
+                                int64_t n_rows, int q, void *stream) {
+  return plmc::assemble_cross_add_impl<float>(kind, X, n, Xs, ns, d, ncomp, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
+                                              stream);
+}
+int plmc_assemble_cross_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell,
+                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
+                                int64_t n_rows, int q, void *stream) {
+  return plmc::assemble_cross_add_impl<double>(kind, X, n, Xs, ns, d, ncomp, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
+                                               stream);
 }
 }

@@ -1453,6 +1453,26 @@ int plmc_factorize_ex_f64(int kind, const double *X, int n, int d, const double 
   const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise};
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
+// The same for an additive kernel (plmc_assemble_add_*): the job carries the component count, the sweep does not look at it
+int plmc_factorize_add_ex_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, const float *noise,
+                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const float *eig_lo, void *stream) {
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)");
+  PLMC_REQUIRE(ncomp >= 1 && ncomp <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()");
+  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise, ncomp};
+  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
+}
+int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, const double *noise,
+                              double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const double *eig_lo, void *stream) {
+  (void)eig_lo;
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)");
+  PLMC_REQUIRE(ncomp >= 1 && ncomp <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()");
+  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise, ncomp};
+  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
+}
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

@@ -225,6 +225,75 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 }
 
 
+// ---- additive kernels (sum of `ncomp` <= MAX_COMP scaled stationary ARD kernels): the two kernels above with the epilogue of
+// kinv_epilogue_add.inc.  One instantiation per element type / split scheme: the input dimension and the component count are run-time
+// loop bounds there.  The single kernel (ncomp = 1) never comes here (kinv_grad_impl).
+template <typename T>
+__device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
+                                                       int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
+                                                       const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
+                                                       int64_t strideK, T *kinv_diag, double *__restrict__ partials) {
+  if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
+#include "kinv_epilogue_add.inc"
+}
+
+template <typename T>
+__global__ __launch_bounds__(NTHREADS, 2) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+                                                                int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
+                                                                const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
+                                                                int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat) {
+  const int m = (int)(n_pad / NB);
+  const int lat = (int)blockIdx.x % nlat;              // tile order of k_kinv_grad
+  int ib, jb;
+  tri_decode((int)blockIdx.x / nlat, ib, jb);
+  __shared__ __align__(16) T smem[tile_smem_elems<T>()];
+  const T *Wl = W + (int64_t)lat * strideW + (int64_t)jb * NB * ldw;
+  Acc<T> acc;
+  acc.zero();
+  tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem);
+  const int tid = threadIdx.x;
+  constexpr bool live = true;
+#include "kinv_epilogue_add.inc"
+}
+
+template <class S>
+__global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int ncomp, int64_t n_pad, const float *__restrict__ alpha,
+                                                                const float *__restrict__ X, int n, int d, const float *__restrict__ ell,
+                                                                const float *__restrict__ oscale, float *Kinv, int64_t ldk, int64_t strideK,
+                                                                float *kinv_diag, double *__restrict__ partials, int nlat,
+                                                                const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
+                                                                int64_t wp_lat_stride, int64_t ws_stride) {
+  constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float);
+  __shared__ __align__(16) unsigned char lds[LDS_BYTES];
+  const int m = (int)(n_pad / NB);
+  // tile order, operand planes and scales: exactly k_kinv_grad_bf3 (see there)
+  const int SJ = (m + 7) / 8, NSB = SJ * (SJ + 1) / 2;
+  const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
+  const int gb = xcd + 8 * (slot >> 5), in = slot & 31;
+  if (gb >= nlat * NSB) return;
+  const int lat = gb / NSB;
+  int sa, sj;
+  tri_decode(gb - lat * NSB, sa, sj);
+  const int ibm = 2 * (4 * sa + (in >> 3)), jb = 8 * sj + (in & 7);
+  if (jb >= m || ibm > jb) return;
+  Acc<float> acc0, acc1;
+  acc0.zero();
+  acc1.zero();
+  if (ws_stride > 1) {
+    ws_stride = (int64_t)wscale[VD_W_TAG + 1] * NB * NB;
+    wp_lat_stride = 2 * ws_stride;
+  }
+  const unsigned short *Pl = Wp + (int64_t)lat * wp_lat_stride + b3_index<S>((int64_t)jb * NB, 0, 0, n_pad);
+  b3_mainloop<S, 2, 0, B3NoPre, true>(acc0, acc1, Pl + (int64_t)ibm * NB * 8, n_pad, Pl + (int64_t)jb * NB * 8, n_pad, (int)(n_pad - (int64_t)jb * NB), lds);
+  float ws = wscale[(int64_t)lat * ws_stride];
+  if (ws_stride > 1 && wscale[(int64_t)lat * ws_stride + VD_W_TAG] != (float)S::NPL) ws = __builtin_nanf("");
+  b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));
+  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+  const int ib = ibm + half;
+  kinv_tile_epilogue_add<float>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
+                                ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials);
+}
+
 // grad[lat][k] = 1/2 * sum over upper tiles of partials, with the 1/ell_k factor for lengthscales.
 // grid (q), 1024 threads = 30 groups of GP = 34 slots; every group walks its tiles with 4 independent
 // accumulators (the loads are latency-bound); fixed summation order throughout.
@@ -264,6 +333,46 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad(const double *__restrict
   }
 }
 
+// The reduction for the additive kernels: the tile's partials are `ncomp` rows of GP slots.  grid (q, ncomp), the thread layout and the
+// summation order of k_reduce_grad.  grad[lat]: [ d/d ell (ncomp x d) | d/d noise | d/d oscale (ncomp) ] -- for one component the
+// layout of k_reduce_grad.  A dimension outside its component (ell = +inf) gets 0.5 * 0 / inf = 0.
+template <typename T>
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__restrict__ partials, int m, int d, int ncomp,
+                                                            const T *__restrict__ ell, double *__restrict__ grad) {
+  __shared__ double red[RED_NT];
+  const int lat = blockIdx.x, g = blockIdx.y;
+  const int ntile = m * m;
+  const int slot = threadIdx.x % GP;
+  const int grp = threadIdx.x / GP;
+  constexpr int NG = RED_NT / GP;
+  const int64_t tstride = (int64_t)ncomp * GP;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if (grp < NG) {
+    const double *base = partials + (int64_t)lat * ntile * tstride + (int64_t)g * GP + slot;
+    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int t = t0 + u * NG;
+        if (t < ntile) {
+          const int ib = t / m, jb = t - ib * m;
+          if (jb >= ib) s[u] += base[(int64_t)t * tstride];
+        }
+      }
+    }
+  }
+  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  if (threadIdx.x < GP) {
+    double tot = 0.0;
+    for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
+    const int k = threadIdx.x;
+    double *gl = grad + (int64_t)lat * (ncomp * (d + 1) + 1);
+    if (k < d) gl[g * d + k] = 0.5 * tot / (double)ell[((int64_t)lat * ncomp + g) * d + k];
+    else if (k == MAX_DIM && g == 0) gl[ncomp * d] = 0.5 * tot;
+    else if (k == MAX_DIM + 1) gl[ncomp * d + 1 + g] = 0.5 * tot;
+  }
+}
+
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -295,7 +404,9 @@ __global__ void k_w_scale(const float *__restrict__ eig_lo, float *__restrict__ 
 template <typename T, class S>
 int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n,
                    int d, const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK,
-                   T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream, const float *Vd = nullptr, int64_t lda_vd = 0) {
+                   T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream, const float *Vd = nullptr, int64_t lda_vd = 0,
+                   int ncomp = 1) {
+  // ncomp > 1: additive kernel, ell (q, ncomp, d), oscale (q, ncomp), `partials` and `grad` ncomp times as wide (plmc_kinv_grad_add_vd_*)
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -316,7 +427,7 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
-      char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * GP * (int64_t)sizeof(double);
+      char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * ncomp * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
       float *wsco = reinterpret_cast<float *>(pb + (int64_t)q * b3_elems<SplitB3>(n_pad, n_pad) * 2);
       hipLaunchKernelGGL((k_w_scale<S>), dim3(1), dim3(q < 64 ? 64 : ((q + 63) / 64) * 64), 0, st, eig_lo, wsco, q, (int)(n < n_pad));
@@ -333,7 +444,10 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   hipLaunchKernelGGL((k_kinv_grad_bf3<S, DC, SP>), gridb, dim3(B3_NT), 0, st, kind, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, \
                      part, q, wp, wsc, wp_lat, ws_lat)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-    if (d <= 4) PLMC_LAUNCH_KB(4, false);
+    if (ncomp > 1)
+      hipLaunchKernelGGL((k_kinv_grad_add_bf3<S>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK,
+                         kinv_diag, part, q, wp, wsc, wp_lat, ws_lat);
+    else if (d <= 4) PLMC_LAUNCH_KB(4, false);
     else if (d <= 8) PLMC_LAUNCH_KB(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KB(16, true); else PLMC_LAUNCH_KB(16, false); }
     else { if (kind == K_SPLINE) PLMC_LAUNCH_KB(32, true); else PLMC_LAUNCH_KB(32, false); }
@@ -344,15 +458,19 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   hipLaunchKernelGGL((k_kinv_grad<T, DC, SP>), grid, block, 0, st, kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, \
                      oscale, Kinv, ldk, strideK, kinv_diag, part, q)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-    if (d <= 4) PLMC_LAUNCH_KG(4, false);
+    if (ncomp > 1)
+      hipLaunchKernelGGL((k_kinv_grad_add<T>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk,
+                         strideK, kinv_diag, part, q);
+    else if (d <= 4) PLMC_LAUNCH_KG(4, false);
     else if (d <= 8) PLMC_LAUNCH_KG(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KG(16, true); else PLMC_LAUNCH_KG(16, false); }
     else { if (kind == K_SPLINE) PLMC_LAUNCH_KG(32, true); else PLMC_LAUNCH_KG(32, false); }
 #undef PLMC_LAUNCH_KG
   }
   {
-    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * GP * sizeof(double) / 2);
-    hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
+    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * ncomp * GP * sizeof(double) / 2);
+    if (ncomp > 1) hipLaunchKernelGGL(k_reduce_grad_add<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
+    else hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
   }
   return launch_status(__func__);
 }
@@ -375,17 +493,17 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
 static int kinv_grad_f32_any(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                              const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                              float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo,
-                             void *stream, const float *Vd = nullptr) {
+                             void *stream, const float *Vd = nullptr, int ncomp = 1) {
   const int split = plmc::knobs().split;
   if (split == 0)
     return plmc::kinv_grad_impl<float, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                             nullptr, stream);
+                                             nullptr, stream, nullptr, 0, ncomp);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
     return plmc::kinv_grad_impl<float, plmc::SplitH2>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                      partials, q, eig_lo, stream, Vd, ldw);
+                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp);
   return plmc::kinv_grad_impl<float, plmc::SplitB3>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                    partials, q, nullptr, stream, Vd, ldw);
+                                                    partials, q, nullptr, stream, Vd, ldw, ncomp);
 }
 int plmc_kinv_grad_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                        const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
@@ -414,6 +532,29 @@ int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
   return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
                                             strideK, kinv_diag, partials, q, nullptr, stream);
 }
+// additive kernels: plmc_kinv_grad_vd_* with a component table (include/plmc.h)
+#define PLMC_REQUIRE_ADD(kind, G)                                                                                     \
+  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)"); \
+  PLMC_REQUIRE(G >= 1 && G <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()")
+int plmc_kinv_grad_add_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
+                              const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, double *grad,
+                              float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
+                              const float *eig_lo, const float *Vd, void *stream) {
+  PLMC_REQUIRE_ADD(kind, ncomp);
+  return kinv_grad_f32_any(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd,
+                           ncomp);
+}
+int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
+                              const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, double *grad,
+                              double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
+                              const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  PLMC_REQUIRE_ADD(kind, ncomp);
+  return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
+                                            strideK, kinv_diag, partials, q, nullptr, stream, nullptr, 0, ncomp);
+}
+#undef PLMC_REQUIRE_ADD
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,

@@ -22,9 +22,10 @@ class Workspace:
     """Caller-owned device buffers for q latent GPs on n points with naug augmented columns.
     Layout documented in include/plmc.h."""
 
-    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False):
+    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False, ncomp=1):
         L = _hip.lib()
         self.n, self.q, self.naug, self.dtype, self.device = n, q, naug, dtype, device
+        self.ncomp = ncomp               # components of an additive kernel: the gradient kernel writes one row of partial sums per tile and component
         self.with_inverse = bool(with_inverse)
         # keep_planes (fp32, with the inverse factor): the sweep keeps the 16-bit planes of every group's solved rows, so that new
         # augmented columns can be forward-substituted on the split engine (plmc_potrs_aug_kept): the eval-mode cache
@@ -55,7 +56,7 @@ class Workspace:
             self.alpha = torch.empty(q, self.n_pad, dtype=dtype, device=device)
             # per-tile partial sums of the gradient kernel; the 16-bit planes of W it multiplies are left in Vd by the sweep
             # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none
-            nbytes = int(L.cdll.plmc_grad_partials_bytes(self.n_pad, q))
+            nbytes = int(L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
             self.partials = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
 
 
@@ -77,13 +78,14 @@ def _drop_all():
     _ws_cache.clear()
 
 
-def get_workspace(n, q, naug, dtype, device, need_grad):
-    key = (n, q, naug, dtype, device.index, bool(need_grad))
+def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1):
+    ncomp = ncomp if need_grad else 1                   # (only the partial sums of the gradient kernel depend on it)
+    key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp)
     ws = _ws_cache.get(key)
     if ws is None:
         if len(_ws_cache) > 3:
             _drop_all()
-        ws = Workspace(n, q, naug, dtype, device, need_grad)
+        ws = Workspace(n, q, naug, dtype, device, need_grad, ncomp=ncomp)
         _ws_cache[key] = ws
     _release(ws)       # a gradient kernel of the previous evaluation may still be reading this workspace on the gradient stream
     return ws
@@ -118,6 +120,47 @@ def _contig(t, dtype=None):
     return t.contiguous()
 
 
+# ---- the kernel's hyper-parameters.  Every function below takes `ell`, `oscale` either as (q, d), (q) | None -- one ARD kernel per
+# latent -- or as the COMPONENT TABLE of an additive kernel, ell (q, G, d) with +inf (1 / ell = 0) on the dimensions a component
+# ignores and oscale (q, G) | None (include/plmc.h, "Additive kernels"; additive.py builds it).  The table goes to the `_add` entry
+# points, which take G in front of ell; everything else (workspaces, pivot checks, streams, caches) does not look at the kernel.
+_ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
+        "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd"}
+
+
+def n_components(ell):
+    return ell.shape[1] if ell.dim() == 3 else 1
+
+
+def grad_table_width(ell):
+    """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)]."""
+    return ell[0].numel() + 1 + n_components(ell)
+
+
+def _check_kernel_shape(L, ell):
+    d = ell.shape[-1]
+    if d > L.cdll.plmc_max_dim():
+        raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
+    if n_components(ell) > L.cdll.plmc_max_components():
+        raise ValueError("%d additive components exceed plmc_max_components()=%d" % (n_components(ell), L.cdll.plmc_max_components()))
+
+
+def _kernel_call(L, base, dt, head, ell, tail):
+    """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table."""
+    if ell.dim() == 3:
+        L.call(_ADD[base], dt, *head, ell.shape[1], _hip.ptr(ell), *tail)
+    else:
+        L.call(base, dt, *head, _hip.ptr(ell), *tail)
+
+
+def _split_grad_table(g, ell_shape, os_shape):
+    """Views (d/d ell, d/d noise, d/d oscale | None) of a gradient table (q, grad_table_width)."""
+    ne = 1
+    for s_ in ell_shape[1:]:
+        ne *= s_
+    return g[:, :ne].reshape(ell_shape), g[:, ne], (None if os_shape is None else g[:, ne + 1:].reshape(os_shape))
+
+
 def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
     """Assemble Khat (+ rhs / cross-covariance columns) and run the blocked Cholesky.
     rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info)."""
@@ -130,20 +173,20 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
     # queues the others beside that group's chain (same kernels, same data: bit-identical; PLMC_FUSED_ASSEMBLE=0: two calls)
     fused = os.environ.get("PLMC_FUSED_ASSEMBLE", "1") != "0"
     if not fused:
-        L.call("plmc_assemble", dt, k, _hip.ptr(X), n, d, _hip.ptr(ell), _hip.ptr(oscale), _hip.ptr(noise),
-               _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
+        _kernel_call(L, "plmc_assemble", dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise),
+                     _hip.ptr(ws.A), ws.lda, ws.strideA, q, st))
     nrhs = 0 if rhs is None else rhs.shape[1]
     if ws.naug_pad > 0:
         L.call("plmc_write_rhs", dt, _hip.ptr(rhs), nrhs, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
     if Xs is not None:
-        L.call("plmc_assemble_cross", dt, k, _hip.ptr(X), n, _hip.ptr(Xs), Xs.shape[0], d, _hip.ptr(ell),
-               _hip.ptr(oscale), _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + nrhs, ws.n_pad, q, st)
+        _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(X), n, _hip.ptr(Xs), Xs.shape[0], d), ell,
+                     (_hip.ptr(oscale), _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + nrhs, ws.n_pad, q, st))
     # eig_lo = the noise variances: lambda_min(K + s2 I) >= s2 -- the bound the two-plane fp16 split of the bulk fp32 products
     # scales its operands with (include/plmc.h, plmc_potrf_ex_*); ignored by the fp64 entry point
     flags = (1 | (4 if ws.keep_planes else 0)) if ws.with_inverse else 0
     if fused:
-        L.call("plmc_factorize_ex", dt, k, _hip.ptr(X), n, d, _hip.ptr(ell), _hip.ptr(oscale), _hip.ptr(noise), _hip.ptr(ws.A), ws.n_pad,
-               ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st)
+        _kernel_call(L, "plmc_factorize_ex", dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise), _hip.ptr(ws.A), ws.n_pad,
+                     ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st))
     else:
         L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
                _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st)
@@ -171,7 +214,8 @@ class ExactLatentLogProb(torch.autograd.Function):
     analytic gradient computed in the same pass.
 
     forward(X (n,d), ell (q,d), oscale (q)|None, noise (q), y (q,n), kind) -> (q,)
-    forward(..., kind, table) with table (q, d+2) float64: the hyper-parameter gradients are written into `table` and
+    ell (q,G,d), oscale (q,G)|None: the component table of an additive kernel, same value and gradients (d/d ell (q,G,d), d/d oscale (q,G)).
+    forward(..., kind, table) with table (q, grad_table_width(ell)) float64: the hyper-parameter gradients are written into `table` and
     NOT returned by this node's backward -- the two-node form exact_latent_log_prob builds when a gradient stream
     exists (see _HyperGrad).
     """
@@ -185,13 +229,13 @@ class ExactLatentLogProb(torch.autograd.Function):
             raise TypeError("projectedlmc hot path supports float32 and float64 tensors")
         q, n = y.shape
         d = X.shape[1]
-        if d > L.cdll.plmc_max_dim():
-            raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
+        _check_kernel_shape(L, ell)
+        G = n_components(ell)
         need_grad = any(ctx.needs_input_grad[1:5]) or table is not None
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, need_grad)
+        ws = get_workspace(n, q, 1, dt, dev, need_grad, G)
         st = _hip.stream_ptr(dev)
-        grad = table if table is not None else (torch.empty(q, d + 2, dtype=torch.float64, device=dev) if need_grad else None)
+        grad = table if table is not None else (torch.empty(q, grad_table_width(ell), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
 
         def enqueue(noise_eff):
@@ -213,9 +257,9 @@ class ExactLatentLogProb(torch.autograd.Function):
                     for t in (grad, Xc, ellc, osc, noise_eff):
                         if t is not None:
                             t.record_stream(gs)
-                L.call("plmc_kinv_grad_vd", dt, _hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
-                       _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(grad),
-                       None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst)
+                _kernel_call(L, "plmc_kinv_grad_vd", dt, (_hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
+                             _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad),
+                             None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst))
                 if gs is not None:
                     ws.pending = torch.cuda.Event()
                     ws.pending.record(gs)
@@ -233,15 +277,15 @@ class ExactLatentLogProb(torch.autograd.Function):
             if check and info.failed():
                 def attempt(jit):
                     nonlocal ws
-                    ws = get_workspace(n, q, 1, dt, dev, need_grad)      # waits for the failed attempt's gradient kernel
+                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G)   # waits for the failed attempt's gradient kernel
                     return enqueue(nzc + jit)
 
                 logp = walk(dt, info, attempt)[1]
         if need_grad:
             ctx.save_for_backward(grad, ws.alpha[:, :n].clone())
         ctx.grad_ready = getattr(ws, "pending", None) if need_grad else None
-        ctx.d = d
-        ctx.has_os = oscale is not None
+        ctx.ell_shape = ell.shape
+        ctx.os_shape = None if oscale is None else oscale.shape
         ctx.table_out = table is not None
         return logp.to(dt)
 
@@ -253,11 +297,7 @@ class ExactLatentLogProb(torch.autograd.Function):
             return None, None, None, None, -(gout[:, None].to(dt) * alpha), None, None
         if ctx.grad_ready is not None:
             torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
-        d = ctx.d
-        g64 = gout.to(torch.float64)
-        g_ell = g64[:, None] * grad[:, :d]
-        g_noise = g64 * grad[:, d]
-        g_os = g64 * grad[:, d + 1] if ctx.has_os else None
+        g_ell, g_noise, g_os = _split_grad_table(gout.to(torch.float64)[:, None] * grad, ctx.ell_shape, ctx.os_shape)
         g_y = -(gout[:, None].to(dt) * alpha)
         return None, g_ell, g_os, g_noise, g_y, None, None
 
@@ -273,16 +313,16 @@ class _HyperGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ell, oscale, noise, table, zero):
         ctx.save_for_backward(table)
-        ctx.d = ell.shape[1]
-        ctx.has_os = oscale is not None
+        ctx.ell_shape = ell.shape
+        ctx.os_shape = None if oscale is None else oscale.shape
         return zero.detach()
 
     @staticmethod
     def backward(ctx, gout):
         (table,) = ctx.saved_tensors
-        d = ctx.d
         g = (table * gout[:, None]).to(gout.dtype)          # fp64 product, one cast; the three gradients are views
-        return g[:, :d], (g[:, d + 1] if ctx.has_os else None), g[:, d], None, None
+        g_ell, g_noise, g_os = _split_grad_table(g, ctx.ell_shape, ctx.os_shape)
+        return g_ell, g_os, g_noise, None, None
 
 
 _zeros = {}
@@ -302,14 +342,14 @@ def prepare_hyper_grad(ell, oscale, noise):
     gs = grad_stream(ell.device) if (hyper and ell.is_cuda) else None
     if gs is None:
         return None
-    q, d = ell.shape
+    q = ell.shape[0]
     key = (ell.device.index, ell.dtype, q)
     zero = _zeros.get(key)
     if zero is None:
         zero = _zeros[key] = torch.zeros(q, dtype=ell.dtype, device=ell.device)
         torch.cuda.current_stream(ell.device).synchronize()
     h = HyperGradHandle()
-    h.table = torch.empty(q, d + 2, dtype=torch.float64, device=ell.device)
+    h.table = torch.empty(q, grad_table_width(ell), dtype=torch.float64, device=ell.device)
     with torch.cuda.stream(gs):
         h.hz = _HyperGrad.apply(ell, oscale, noise, h.table, zero)
     return h
@@ -336,18 +376,19 @@ def exact_loo(kind, X, ell, oscale, noise, y):
     q, n = y.shape
     d = X.shape[1]
     Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-    ws = get_workspace(n, q, 1, dt, dev, True)
+    _check_kernel_shape(L, ellc)
+    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc))
     st = _hip.stream_ptr(dev)
     factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
     L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
            _hip.ptr(ws.quad), q, st)
     L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z),
            _hip.ptr(ws.alpha), q, st)
-    grad = torch.empty(q, d + 2, dtype=torch.float64, device=dev)
+    grad = torch.empty(q, grad_table_width(ellc), dtype=torch.float64, device=dev)
     kd = torch.empty(q, ws.n_pad, dtype=dt, device=dev)
-    L.call("plmc_kinv_grad_vd", dt, _hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
-           _hip.ptr(Xc), n, d, _hip.ptr(ellc), _hip.ptr(osc), _hip.ptr(grad), None, 0, 0, _hip.ptr(kd),
-           _hip.ptr(ws.partials), q, _hip.ptr(nzc), _hip.ptr(ws.Vd), st)
+    _kernel_call(L, "plmc_kinv_grad_vd", dt, (_hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
+                 _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad), None, 0, 0, _hip.ptr(kd),
+                 _hip.ptr(ws.partials), q, _hip.ptr(nzc), _hip.ptr(ws.Vd), st))
     sigma2 = 1.0 / kd[:, :n]
     return sigma2, ws.alpha[:, :n] * sigma2
 
@@ -394,6 +435,7 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     q, n = y.shape
     ns = Xs.shape[0]
     Xc, Xsc, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xs, ell, oscale, noise))
+    _check_kernel_shape(L, ellc)
     yc = _contig(y).reshape(q, 1, n)
     st = _hip.stream_ptr(dev)
     mode = settings.prediction_cache.value() if cache is not None else "off"
@@ -419,8 +461,8 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
             cache.hits += 1
             k = _hip.KIND[kind]
             L.call("plmc_write_rhs", dt, _hip.ptr(yc), 1, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
-            L.call("plmc_assemble_cross", dt, k, _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, Xc.shape[1], _hip.ptr(ellc), _hip.ptr(osc),
-                   _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + 1, ws.n_pad, q, st)
+            _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, Xc.shape[1]), ellc, (_hip.ptr(osc),
+                         _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + 1, ws.n_pad, q, st))
             if ws.keep_planes:
                 L.call("plmc_potrs_aug_kept", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, 1 + ns, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q,
                        _hip.ptr(nzc), st)
@@ -443,7 +485,7 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
         cov = Kss - gemm_tn(V, V)                                   # V^T V on the library's tile engine (plmc_gemm_tn)
         return mean, cov
     from .kernels import prior_diagonal
-    var = prior_diagonal(kind, Xsc, osc, q) - vsq                      # k(x*, x*) = 1 for the stationary kinds
+    var = prior_diagonal(kind, Xsc, osc, q) - vsq                      # k(x*, x*) = 1 for the stationary kinds (additive: sum_g os_g)
     return mean, var
 
 
@@ -464,13 +506,13 @@ def mix_posterior(mean_lat, var_lat, Ht, eps=0.0):
 
 
 def dense_cross(kind, X1, X2, ell, oscale):
-    """Dense k(X1, X2) per latent via the cross-assembly kernel: (q, n1, n2)."""
+    """Dense k(X1, X2) per latent via the cross-assembly kernel: (q, n1, n2).  ell, oscale: (q, d), (q) or a component table."""
     L = _hip.lib()
     dt, dev = X1.dtype, X1.device
     q = ell.shape[0]
     n1, n2, d = X1.shape[0], X2.shape[0], X1.shape[1]
     out = torch.empty(q, n1, n2, dtype=dt, device=dev)
-    L.call("plmc_assemble_cross", dt, _hip.KIND[kind], _hip.ptr(X1.contiguous()), n1, _hip.ptr(X2.contiguous()), n2, d,
-           _hip.ptr(ell.contiguous()), _hip.ptr(None if oscale is None else oscale.contiguous()), _hip.ptr(out),
-           n2, n1 * n2, 0, n1, q, _hip.stream_ptr(dev))
+    _kernel_call(L, "plmc_assemble_cross", dt, (_hip.KIND[kind], _hip.ptr(X1.contiguous()), n1, _hip.ptr(X2.contiguous()), n2, d),
+                 ell.contiguous(), (_hip.ptr(None if oscale is None else oscale.contiguous()), _hip.ptr(out),
+                 n2, n1 * n2, 0, n1, q, _hip.stream_ptr(dev)))
     return out

@@ -1,14 +1,17 @@
 """Additive sub-kernel decompositions, `decomp=[[0,1],[1,2]]` -> k(x) = s1 k1(x0,x1) + s2 k2(x1,x2)
 (reference: handle_covar_, projected_lmc.py:131-167).
 
-HIP path: a sum of G scaled ARD kernels on subsets of the input dimensions is the dense LMC
-covariance with one task (p = 1, B_g = [[1]]) whose g-th "latent" has an infinite lengthscale on the
-dimensions it ignores (1/ell = 0), so assembly, factorisation and all gradients reuse csrc/lmc.hip.
-A batch of q functions (the reference builds the decomposition with batch_shape=[n_funcs], projected_lmc.py:151-167:
-batched exact GPs, the latent processes of the projected model) is q such problems, one factorisation each."""
+HIP path: the sum of G scaled ARD kernels on subsets of the input dimensions is a kernel kind of the batched exact engine
+like any other.  Calling the module returns an ordinary `LazyKernel` whose hyper-parameters are a COMPONENT TABLE -- lengthscales
+(q, G, d) with an infinite lengthscale (1 / ell = 0 exactly, `LazyKernel.inv_ell`) on the dimensions a component ignores, output
+scales (q, G) -- for batch_shape [1] and [n_funcs] alike (the reference builds the decomposition with batch_shape=[n_funcs],
+projected_lmc.py:151-167: batched exact GPs, the latent processes of the projected model).  The assembly, cross-assembly and
+gradient kernels evaluate the G components per element (include/plmc.h, "Additive kernels"); the sweep, the pivot checks, the
+prediction cache, `full_cov` and latent sharding do not look at the kernel and serve it unchanged.  A sub-kernel owns len(group)
+lengthscales: autograd gathers the active slots of the table's gradient back into them (index_copy below)."""
 import torch
 
-from .kernels import Kernel, ScaleKernel, LazyLmcKernel
+from .kernels import Kernel, ScaleKernel, LazyKernel
 
 
 class AdditiveKernel(Kernel):
@@ -22,8 +25,8 @@ class AdditiveKernel(Kernel):
     def select(self, x):
         return x
 
-    def forward(self, x1, x2=None, **params):
-        d = x1.shape[-1]
+    def table(self, d):
+        """(kind, ell (batch, G, d), oscale (batch, G)) from the sub-kernels' parameters; needs no device."""
         kinds, ells, oss = [], [], []
         nb = max(int((k.base_kernel if isinstance(k, ScaleKernel) else k).batch_shape.numel()) for k in self.kernels)
         for k in self.kernels:
@@ -38,77 +41,8 @@ class AdditiveKernel(Kernel):
             oss.append(os_g.expand(nb))
         if len(set(kinds)) != 1:
             raise NotImplementedError("all sub-kernels of a decomposition must be of the same type")
-        G = len(ells)
-        ell, osc = torch.stack(ells, 1), torch.stack(oss, 1)                   # (batch, G, d), (batch, G)
-        B = torch.ones(G, 1, 1, dtype=ell.dtype, device=ell.device)
-        if nb == 1:
-            return LazyAdditiveKernel(kinds[0], x1, ell[0], osc[0], B)
-        return LazyBatchedAdditiveKernel([LazyAdditiveKernel(kinds[0], x1, ell[i], osc[i], B) for i in range(nb)])
+        return kinds[0], torch.stack(ells, 1), torch.stack(oss, 1)
 
-
-class LazyAdditiveKernel(LazyLmcKernel):
-    """LazyLmcKernel with p = 1 and the single-output hooks (noise instead of task noise)."""
-
-    def add_noise(self, noise):
-        return LazyAdditiveKernel(self.kind, self.x, self.ell, self.oscale, self.B,
-                                  noise.reshape(1, 1) if self.task_noise is None else self.task_noise + noise.reshape(1, 1))
-
-    @property
-    def x1(self):
-        return self.x
-
-    def log_prob_batch(self, y):
-        return self.log_prob_flat(y.reshape(-1)).reshape(1)
-
-    def posterior(self, y, xs):
-        from . import _lmc_engine
-        mean, var = _lmc_engine.lmc_posterior(self.kind, self.x, self.ell.detach(), self.oscale.detach(), self.B,
-                                              self.task_noise.detach(), y.reshape(-1), xs)
-        return mean.reshape(1, -1), var.reshape(1, -1)
-
-
-class LazyBatchedAdditiveKernel:
-    """q additive kernels on the same inputs (batch_shape = [q]): the hooks of the single-output form, looped --
-    every latent is its own dense factorisation (one per latent, as the blocked sweep batches independent matrices;
-    the Kronecker-sum assembly kernel evaluates one sum of sub-kernels per launch)."""
-
-    def __init__(self, parts):
-        self.parts = parts
-
-    @property
-    def kind(self):
-        return self.parts[0].kind
-
-    @property
-    def x1(self):
-        return self.parts[0].x
-
-    @property
-    def ell(self):
-        return self.parts[0].ell
-
-    @property
-    def shape(self):
-        n = self.parts[0].x.shape[-2]
-        return torch.Size([len(self.parts), n, n])
-
-    def add_noise(self, noise):
-        noise = noise.reshape(-1)
-        return LazyBatchedAdditiveKernel([p_.add_noise(noise[i if noise.numel() > 1 else 0]) for i, p_ in enumerate(self.parts)])
-
-    def diagonal(self, *a, **k):
-        return torch.stack([p_.diagonal() for p_ in self.parts])
-
-    def log_prob_batch(self, y):
-        y = y.reshape(len(self.parts), -1)
-        return torch.cat([p_.log_prob_batch(y[i]) for i, p_ in enumerate(self.parts)])
-
-    def posterior(self, y, xs):
-        y = y.reshape(len(self.parts), -1)
-        out = [p_.posterior(y[i], xs) for i, p_ in enumerate(self.parts)]
-        return torch.cat([o[0] for o in out], 0), torch.cat([o[1] for o in out], 0)
-
-    def evaluate(self):
-        return torch.stack([p_.evaluate() for p_ in self.parts])
-
-    to_dense = evaluate
+    def forward(self, x1, x2=None, **params):
+        kind, ell, osc = self.table(x1.shape[-1])
+        return LazyKernel(kind, x1, x1 if x2 is None else x2, ell, osc, torch.Size([ell.shape[0]]))

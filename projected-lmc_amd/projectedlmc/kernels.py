@@ -99,6 +99,8 @@ def prior_diagonal(kind, x, oscale, q):
         dg = (1 + x ** 2 + x ** 3 / 3).prod(dim=-1).reshape(1, -1).expand(q, -1)
     else:
         dg = torch.ones(q, x.shape[-2], dtype=x.dtype, device=x.device)
+    if oscale is not None and oscale.dim() == 2:              # additive kernel: k(x, x) = sum_g os_g
+        oscale = oscale.sum(-1)
     return dg if oscale is None else dg * oscale.reshape(-1, 1)
 
 
@@ -127,7 +129,9 @@ class ScaleKernel(Kernel):
 
 class LazyKernel:
     """Un-evaluated batched covariance os * k(x1, x2; ell) (+ noise * I once a likelihood was
-    applied).  The hot path never materialises it."""
+    applied).  The hot path never materialises it.
+    ell (q, d), oscale (q) | None: one ARD kernel per latent.  ell (q, G, d), oscale (q, G): the component table of an additive
+    kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise
@@ -148,6 +152,11 @@ class LazyKernel:
     @property
     def device(self):
         return self.x1.device
+
+    @property
+    def inv_ell(self):
+        """1 / ell: exactly 0 on the slots of an additive component's table that are outside its group of dimensions."""
+        return 1.0 / self.ell
 
     def add_noise(self, noise):
         return LazyKernel(self.kind, self.x1, self.x2, self.ell, self.oscale, self.batch_shape,
