@@ -351,6 +351,60 @@ int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t 
                               double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
 
 /*
+ * Spectral-mixture kernel [gpytorch-knowledge: SpectralMixtureKernel; the reference's tidal study, realdata_experiments.py:130-140, runs
+ * every model with it] on the batched exact engine:
+ *     Khat_i = sum_{m < nmix} w[i][m] exp(-2 pi^2 sum_k s[i][m][k]^2 tau_k^2) prod_k cos(2 pi mu[i][m][k] tau_k) + noise[i] I,   tau = x - x',
+ *     1 <= nmix <= plmc_sm_max_mixtures(),  1 <= d <= plmc_sm_max_dim().  Exceeding a limit is an argument error (plmc_last_error()).
+ * Table, per latent i:  scales s and means mu (q x nmix x d, contiguous), weights w (q x nmix) or NULL (all ones).  A dimension a
+ *   component ignores carries s = mu = 0: its factor is exactly 1 and its gradients are exactly 0.  noise: q.
+ * Every entry point takes the arguments of its `_add` form with (kind, ..., ncomp, ell, oscale, ...) replaced by
+ * (..., nmix, scales, means, weights, ...) and does what that form does:
+ *   plmc_assemble_sm_*        plmc_assemble_add_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_sm_*  plmc_assemble_cross_add_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_sm_ex_*    plmc_factorize_add_ex_*    (assembly overlapped with the sweep; bit-identical to plmc_assemble_sm_* followed
+ *                                                         by plmc_potrf_ex_*)
+ *   plmc_kinv_grad_sm_vd_*    plmc_kinv_grad_add_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ * The carrier's phase mu tau is reduced in revolutions before the cosine (difference and product with their rounding residuals), so
+ * the fp32 assembly is within 32 d 2^-24 sum_m w_m of the fp64 formula at the fp32 inputs per element, at any phase.
+ * The fp16 split scales of the sweep take eig_lo as for every other kernel; |K_ij| <= sum_m w_m + noise, the diagonal, here too.
+ * Gradient table of plmc_kinv_grad_sm_vd_* (double), 2 nmix d + 1 + nmix entries per latent:
+ *     grad[latent] = [ d logp / d scales: nmix x d | d / d means: nmix x d | d / d noise | d / d weights: nmix ]
+ *   finite also where a cosine factor is exactly 0 (the product's derivative is formed without a division).
+ *   plmc_kinv_grad_sm_vd_f32 with d > 1 forms K^-1 with the fp32 matrix instructions whatever PLMC_SPLIT says (the knob and eig_lo
+ *   are not looked at; no planes of W are needed); d = 1 follows the knob like every other kernel.
+ * Scratch.  `Vd`: the scratch of the sweep, sized as for plmc_potrf_ex_* / plmc_factorize_ex_* (plmc_vd_blocks_for(n_pad, lda, elem
+ *   bytes), resp. plmc_vd_blocks_keep) -- the kernel does not change it.  `partials`: plmc_sm_grad_partials_bytes(n_pad, q, nmix, elem
+ *   bytes) bytes, one row of partial sums per tile and component; a function of its arguments only, never of a dev knob.  The fp32 split
+ *   engine takes the planes of W from the Vd of the sweep that produced W (with_inverse on an lda >= 2 n_pad layout) and refuses a call
+ *   without them; fp64 and PLMC_SPLIT=0 need no planes.
+ */
+int plmc_sm_max_mixtures(void);               /* most components of a spectral-mixture kernel (8) */
+int plmc_sm_max_dim(void);                    /* largest input dimension of a spectral-mixture kernel (8) */
+int64_t plmc_sm_grad_partials_bytes(int64_t n_pad, int q, int nmix, int elem_bytes);
+int plmc_assemble_sm_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                         const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_sm_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                         const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means,
+                               const float *weights, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream);
+int plmc_assemble_cross_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means,
+                               const double *weights, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream);
+int plmc_factorize_sm_ex_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                             const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                             int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                             const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                             int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_sm_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                             int nmix, const float *scales, const float *means, const float *weights, double *grad, float *Kinv, int64_t ldk,
+                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                             int nmix, const double *scales, const double *means, const double *weights, double *grad, double *Kinv, int64_t ldk,
+                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

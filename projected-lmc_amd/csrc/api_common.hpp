@@ -11,6 +11,8 @@ namespace plmc {
 
 constexpr int MAX_DIM = 32;          // largest input dimension handled by the fused kernels
 constexpr int MAX_COMP = 4;          // most components of an additive kernel (plmc_max_components())
+constexpr int SM_MAX_MIX = 8;        // most components of a spectral-mixture kernel (plmc_sm_max_mixtures())
+constexpr int SM_MAX_DIM = 8;        // largest input dimension of a spectral-mixture kernel (plmc_sm_max_dim())
 
 char *err_buf();                     // thread-local, defined in api.hip
 
@@ -30,6 +32,12 @@ inline int launch_status(const char *fn) {
 
 #define PLMC_REQUIRE(cond, msg) \
   do { if (!(cond)) return plmc::fail(__func__, msg); } while (0)
+
+// limits of a spectral-mixture table (plmc_*_sm_*): M components on d input dimensions, `means` its second plane
+#define PLMC_REQUIRE_SM(M, d, means)                                                                         \
+  PLMC_REQUIRE((M) >= 1 && (M) <= plmc::SM_MAX_MIX, "need 1 <= mixtures <= plmc_sm_max_mixtures()"); \
+  PLMC_REQUIRE((d) > 0 && (d) <= plmc::SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");              \
+  PLMC_REQUIRE((means) != nullptr, "null pointer")
 
 // kernel classes known to the optional profiler (api.hip)
 enum ProfKernel { PK_ASSEMBLE, PK_WRITE_RHS, PK_CROSS, PK_DIAG, PK_PANEL, PK_TRAIL, PK_WDIAG, PK_TRTRI, PK_EXTRACT,
@@ -65,10 +73,13 @@ const Knobs &knobs();
 // Covariance assembly handed to the sweep (plmc_factorize_ex_*): the sweep queues the rows of its first group on the caller's stream and
 // the rest on a helper stream beside the first group's chain, instead of the caller assembling the whole matrix in front of the sweep
 // ncomp > 1: an additive kernel (plmc_factorize_add_ex_*), ell (q, ncomp, d) and oscale (q, ncomp)
+// means != null: a spectral-mixture kernel (plmc_factorize_sm_ex_*) of ncomp components, ell = its scales and means (q, ncomp, d),
+// oscale = its weights (q, ncomp) or null; `kind` is not looked at
 struct AssembleJob {
   int kind, n, d;
   const void *X, *ell, *oscale, *noise;
   int ncomp = 1;
+  const void *means = nullptr;
 };
 // block rows ib0 .. ib0 + nrows - 1 of the covariance matrices (assemble.hip), the first ncols block columns (< 0: all) without the
 // leading skip x skip block triangle; elem_bytes 4 / 8

@@ -227,9 +227,11 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross(int kind, const T *
 // its own d lengthscales; ell_g[k] = +inf (1 / ell = 0) takes dimension k out of component g.  The inputs are staged RAW, once: the
 // differences x - x' are formed once per element and scaled per component (one rounding each), so a component costs d multiplies,
 // d multiply-adds and one kernel profile.  Same tiling, padding and row-range interface as the kernels above.
-template <typename T, int DCAP, int KIND>
-__device__ __forceinline__ void assemble_tile_add(const T *xi, const T *xj, int ldu, const T *w, const T *osl, int G, T nz, T *Al, int64_t lda,
-                                                  int ib, int jb, int n, bool edge) {
+// The tile walk is shared by every kernel that is a table of components (additive, spectral mixture): `value(xr, xc)` is the noise-free
+// covariance of one row against a pair of columns, from their raw coordinates.
+template <typename T, int DCAP, class F>
+__device__ __forceinline__ void assemble_tile_table(const T *xi, const T *xj, int ldu, const F value, T nz, T *Al, int64_t lda,
+                                                    int ib, int jb, int n, bool edge) {
   typedef Pair<T> T2;
   const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
   const int c0 = tx * 4;
@@ -247,23 +249,7 @@ __device__ __forceinline__ void assemble_tile_add(const T *xi, const T *xj, int 
     for (int k = 0; k < DCAP; ++k) xr[k] = xi[r * ldu + k];
     T2 v[2];
 #pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-      T2 df[DCAP];
-#pragma unroll
-      for (int k = 0; k < DCAP; ++k) df[k] = xr[k] - x2[pp][k];
-      T2 sum = {T(0), T(0)};
-#pragma unroll 1
-      for (int g = 0; g < G; ++g) {
-        T2 r2 = {T(0), T(0)};
-#pragma unroll
-        for (int k = 0; k < DCAP; ++k) {
-          const T2 sd = df[k] * w[g * DCAP + k];
-          r2 += sd * sd;
-        }
-        sum += osl[g] * kern_value_pair<T>(KIND, r2);
-      }
-      v[pp] = sum;
-    }
+    for (int pp = 0; pp < 2; ++pp) v[pp] = value(xr, x2[pp]);
     T o[4] = {v[0].x, v[0].y, v[1].x, v[1].y};
     if (edge) {
 #pragma unroll
@@ -286,16 +272,117 @@ __device__ __forceinline__ void assemble_tile_add(const T *xi, const T *xj, int 
   }
 }
 
-// d <= 8 (DCAP in {4, 8}); ell: (q, G, d), oscale: (q, G) or null
-template <typename T, int DCAP>
-__global__ __launch_bounds__(NTHREADS) void k_assemble_small_add(int kind, const T *__restrict__ X, int n, int d, int G,
-                                                                  const T *__restrict__ ell, const T *__restrict__ oscale,
-                                                                  const T *__restrict__ noise, T *__restrict__ A,
-                                                                  int64_t lda, int64_t strideA, int ib0, int skip) {
+// The additive table: per latent ell (G, d), oscale (G) | null.  In LDS: w = 1 / ell [G][DCAP] (0 beyond d), os [G].
+template <typename T, int DCAP, int KIND> struct AddPairValue {
+  const T *w, *osl;
+  int G;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    typedef Pair<T> T2;
+    T2 df[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) df[k] = xr[k] - xc[k];
+    T2 sum = {T(0), T(0)};
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      T2 r2 = {T(0), T(0)};
+#pragma unroll
+      for (int k = 0; k < DCAP; ++k) {
+        const T2 sd = df[k] * w[g * DCAP + k];
+        r2 += sd * sd;
+      }
+      sum += osl[g] * kern_value_pair<T>(KIND, r2);
+    }
+    return sum;
+  }
+};
+template <typename T, int DCAP> struct AddTable {
+  static constexpr int LDS = MAX_COMP * DCAP + MAX_COMP;
+  int kind, G;
+  const T *ell, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < G * DCAP) {
+      const int g = tid / DCAP, k = tid % DCAP;
+      par[tid] = k < d ? T(1) / ell[((int64_t)lat * G + g) * d + k] : T(0);
+    }
+    if (tid < G) par[MAX_COMP * DCAP + tid] = oscale ? oscale[(int64_t)lat * G + tid] : T(1);
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    const T *w = par, *osl = par + MAX_COMP * DCAP;
+    if (kind == K_RBF) assemble_tile_table<T, DCAP>(xi, xj, ldu, AddPairValue<T, DCAP, K_RBF>{w, osl, G}, nz, Al, lda, ib, jb, n, edge);
+    else if (kind == K_MATERN12) assemble_tile_table<T, DCAP>(xi, xj, ldu, AddPairValue<T, DCAP, K_MATERN12>{w, osl, G}, nz, Al, lda, ib, jb, n, edge);
+    else if (kind == K_MATERN32) assemble_tile_table<T, DCAP>(xi, xj, ldu, AddPairValue<T, DCAP, K_MATERN32>{w, osl, G}, nz, Al, lda, ib, jb, n, edge);
+    else assemble_tile_table<T, DCAP>(xi, xj, ldu, AddPairValue<T, DCAP, K_MATERN52>{w, osl, G}, nz, Al, lda, ib, jb, n, edge);
+  }
+  // one value of the cross kernel: xa a row of raw coordinates in LDS, xs the thread's test point
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    const T *w = par, *osl = par + MAX_COMP * DCAP;
+    T df[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) df[k] = xa[k] - xs[k];
+    T val = T(0);
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      T r2 = T(0);
+#pragma unroll
+      for (int k = 0; k < DCAP; ++k) {
+        const T sd = df[k] * w[g * DCAP + k];
+        r2 += sd * sd;
+      }
+      val += osl[g] * kern_value<T>(kind, r2);
+    }
+    return val;
+  }
+};
+
+// The spectral-mixture table (covariance.hpp): per latent scales, means (M, d), weights (M) | null.  In LDS: sc, mu [M][DCAP] (0 beyond
+// d: that factor is exactly 1), wt [M].
+template <typename T, int DCAP> struct SmPairValue {
+  const T *sc, *mu, *wt;
+  int M;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    T b0[DCAP], b1[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) { b0[k] = xc[k].x; b1[k] = xc[k].y; }
+    return Pair<T>{sm_value<T, DCAP>(xr, b0, sc, mu, wt, M), sm_value<T, DCAP>(xr, b1, sc, mu, wt, M)};
+  }
+};
+template <typename T, int DCAP> struct SmTable {
+  static constexpr int LDS = SM_MAX_MIX * (2 * DCAP + 1);
+  int M;
+  const T *scales, *means, *weights;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < M * DCAP) {
+      const int g = tid / DCAP, k = tid % DCAP;
+      par[tid] = k < d ? scales[((int64_t)lat * M + g) * d + k] : T(0);
+      par[SM_MAX_MIX * DCAP + tid] = k < d ? means[((int64_t)lat * M + g) * d + k] : T(0);
+    }
+    if (tid < M) par[2 * SM_MAX_MIX * DCAP + tid] = weights ? weights[(int64_t)lat * M + tid] : T(1);
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, SmPairValue<T, DCAP>{par, par + SM_MAX_MIX * DCAP, par + 2 * SM_MAX_MIX * DCAP, M}, nz, Al, lda,
+                                 ib, jb, n, edge);
+  }
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T a[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) a[k] = xa[k];
+    return sm_value<T, DCAP>(a, xs, par, par + SM_MAX_MIX * DCAP, par + 2 * SM_MAX_MIX * DCAP, M);
+  }
+};
+
+// d <= 8 (DCAP in {4, 8}; spectral mixture also 1); P: AddTable / SmTable
+template <typename T, int DCAP, class P>
+__global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
+                                                                    const T *__restrict__ noise, T *__restrict__ A,
+                                                                    int64_t lda, int64_t strideA, int ib0, int skip) {
   const int jb = blockIdx.x, ib = ib0 + blockIdx.y, lat = blockIdx.z;
   if (jb < ib || (ib < skip && jb < skip)) return;
   constexpr int ldu = DCAP + 1;
-  __shared__ T xi[NB * ldu], xj[NB * ldu], w[MAX_COMP * DCAP], osl[MAX_COMP];
+  __shared__ T xi[NB * ldu], xj[NB * ldu], par[P::LDS];
   const int tid = threadIdx.x;
   for (int e = tid; e < NB * DCAP; e += NTHREADS) {      // unused dimensions: zeros (they add 0 to every distance)
     const int r = e / DCAP, k = e % DCAP;
@@ -303,19 +390,12 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_small_add(int kind, const
     xi[r * ldu + k] = (k < d && gi < n) ? X[(int64_t)gi * d + k] : T(0);
     xj[r * ldu + k] = (k < d && gj < n) ? X[(int64_t)gj * d + k] : T(0);
   }
-  if (tid < G * DCAP) {
-    const int g = tid / DCAP, k = tid % DCAP;
-    w[tid] = k < d ? T(1) / ell[((int64_t)lat * G + g) * d + k] : T(0);
-  }
-  if (tid < G) osl[tid] = oscale ? oscale[(int64_t)lat * G + tid] : T(1);
+  prm.stage(lat, d, par);
   __syncthreads();
   const T nz = noise[lat];
   T *Al = A + (int64_t)lat * strideA;
   const bool edge = ib == jb || (jb + 1) * NB > n;
-  if (kind == K_RBF) assemble_tile_add<T, DCAP, K_RBF>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
-  else if (kind == K_MATERN12) assemble_tile_add<T, DCAP, K_MATERN12>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
-  else if (kind == K_MATERN32) assemble_tile_add<T, DCAP, K_MATERN32>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
-  else assemble_tile_add<T, DCAP, K_MATERN52>(xi, xj, ldu, w, osl, G, nz, Al, lda, ib, jb, n, edge);
+  prm.tile(xi, xj, ldu, par, nz, Al, lda, ib, jb, n, edge);
 }
 
 // any d <= MAX_DIM: the thread layout of k_assemble; dynamic LDS: xi, xj [128][d + 1], w [G][d], os [G]
@@ -384,15 +464,14 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_add(int kind, const T *__
   }
 }
 
-// Out[i][col0 + j] = sum_g os_g k(x_i, xs_j; ell_g): the workgroup shape of k_assemble_cross, raw coordinates, the differences scaled per component
-template <typename T, int DCAP>
-__global__ __launch_bounds__(NTHREADS) void k_assemble_cross_add(int kind, const T *__restrict__ X, int n,
-                                                                  const T *__restrict__ Xs, int ns, int d, int G,
-                                                                  const T *__restrict__ ell, const T *__restrict__ oscale,
-                                                                  T *__restrict__ A, int64_t n_rows, int64_t lda,
-                                                                  int64_t strideA, int64_t col0) {
+// Out[i][col0 + j] = the table's covariance of x_i and xs_j: the workgroup shape of k_assemble_cross, raw coordinates
+template <typename T, int DCAP, class P>
+__global__ __launch_bounds__(NTHREADS) void k_assemble_cross_table(const P prm, const T *__restrict__ X, int n,
+                                                                    const T *__restrict__ Xs, int ns, int d,
+                                                                    T *__restrict__ A, int64_t n_rows, int64_t lda,
+                                                                    int64_t strideA, int64_t col0) {
   __shared__ T xi[CROSS_ROWS][DCAP + 1];
-  __shared__ T w[MAX_COMP * DCAP], osl[MAX_COMP];
+  __shared__ T par[P::LDS];
   const int lat = blockIdx.z;
   const int j = blockIdx.x * NTHREADS + threadIdx.x;
   const int64_t i0 = (int64_t)blockIdx.y * CROSS_ROWS;
@@ -400,11 +479,7 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross_add(int kind, const
     const int r = e / DCAP, k = e % DCAP;
     xi[r][k] = (k < d && i0 + r < n) ? X[(i0 + r) * d + k] : T(0);
   }
-  if ((int)threadIdx.x < G * DCAP) {
-    const int g = threadIdx.x / DCAP, k = threadIdx.x % DCAP;
-    w[threadIdx.x] = k < d ? T(1) / ell[((int64_t)lat * G + g) * d + k] : T(0);
-  }
-  if ((int)threadIdx.x < G) osl[threadIdx.x] = oscale ? oscale[(int64_t)lat * G + threadIdx.x] : T(1);
+  prm.stage(lat, d, par);
   T xs[DCAP];
 #pragma unroll
   for (int k = 0; k < DCAP; ++k) xs[k] = (k < d && j < ns) ? Xs[(int64_t)j * d + k] : T(0);
@@ -414,23 +489,7 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross_add(int kind, const
 #pragma unroll 1
   for (int r = 0; r < CROSS_ROWS; ++r) {
     if (i0 + r >= n_rows) break;
-    T val = T(0);
-    if (i0 + r < n) {
-      T df[DCAP];
-#pragma unroll
-      for (int k = 0; k < DCAP; ++k) df[k] = xi[r][k] - xs[k];
-#pragma unroll 1
-      for (int g = 0; g < G; ++g) {
-        T r2 = T(0);
-#pragma unroll
-        for (int k = 0; k < DCAP; ++k) {
-          const T sd = df[k] * w[g * DCAP + k];
-          r2 += sd * sd;
-        }
-        val += osl[g] * kern_value<T>(kind, r2);
-      }
-    }
-    out[(int64_t)r * lda] = val;
+    out[(int64_t)r * lda] = i0 + r < n ? prm.value(xi[r], xs, par) : T(0);
   }
 }
 
@@ -525,11 +584,11 @@ int assemble_add_impl(int kind, const T *X, int n, int d, int G, const T *ell, c
   ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
   const dim3 grid(ncols, nrows, q);
   if (d <= 4)
-    hipLaunchKernelGGL((k_assemble_small_add<T, 4>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A,
-                       lda, strideA, ib0, skip);
+    hipLaunchKernelGGL((k_assemble_small_table<T, 4, AddTable<T, 4>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, 4>{kind, G, ell, oscale},
+                       X, n, d, noise, A, lda, strideA, ib0, skip);
   else if (d <= 8)
-    hipLaunchKernelGGL((k_assemble_small_add<T, 8>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A,
-                       lda, strideA, ib0, skip);
+    hipLaunchKernelGGL((k_assemble_small_table<T, 8, AddTable<T, 8>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, 8>{kind, G, ell, oscale},
+                       X, n, d, noise, A, lda, strideA, ib0, skip);
   else
     hipLaunchKernelGGL(k_assemble_add<T>, grid, dim3(NTHREADS), smem, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A, lda,
                        strideA, ib0, skip);
@@ -547,7 +606,8 @@ int assemble_cross_add_impl(int kind, const T *X, int n, const T *Xs, int ns, in
   ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
   const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
 #define PLMC_CROSS(DC) \
-  hipLaunchKernelGGL((k_assemble_cross_add<T, DC>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, Xs, ns, d, G, ell, oscale, Out, n_rows, ldo, strideO, col0)
+  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, AddTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, DC>{kind, G, ell, oscale}, \
+                     X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
   if (d <= 4) PLMC_CROSS(4);
   else if (d <= 8) PLMC_CROSS(8);
   else if (d <= 16) PLMC_CROSS(16);
@@ -556,8 +616,62 @@ int assemble_cross_add_impl(int kind, const T *X, int n, const T *Xs, int ns, in
   return launch_status(__func__);
 }
 
+// the spectral-mixture forms (include/plmc.h, "Spectral-mixture kernel"): the table kernels above with SmTable
+template <typename T>
+int assemble_sm_impl(const T *X, int n, int d, int M, const T *scales, const T *means, const T *weights, const T *noise, T *A,
+                     int64_t lda, int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
+  PLMC_REQUIRE_SM(M, d, means);
+  PLMC_REQUIRE(X && scales && noise && A, "null pointer");
+  PLMC_REQUIRE(n > 0 && q > 0, "need n>0, q>0");
+  const int64_t n_pad = plmc_pad(n);
+  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
+  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
+  const int m = (int)(n_pad / NB);
+  if (nrows < 0) nrows = m - ib0;
+  if (ncols < 0) ncols = m;
+  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
+  if (nrows == 0 || ncols == 0) return 0;
+  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
+  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
+  const dim3 grid(ncols, nrows, q);
+#define PLMC_SM(DC)                                                                                                                         \
+  hipLaunchKernelGGL((k_assemble_small_table<T, DC, SmTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                        \
+                     SmTable<T, DC>{M, scales, means, weights}, X, n, d, noise, A, lda, strideA, ib0, skip)
+  if (d == 1) PLMC_SM(1);
+  else if (d <= 4) PLMC_SM(4);
+  else PLMC_SM(8);
+#undef PLMC_SM
+  return launch_status(__func__);
+}
+
+template <typename T>
+int assemble_cross_sm_impl(const T *X, int n, const T *Xs, int ns, int d, int M, const T *scales, const T *means, const T *weights, T *Out,
+                           int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
+  PLMC_REQUIRE_SM(M, d, means);
+  PLMC_REQUIRE(X && Xs && scales && Out, "null pointer");
+  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0, "bad sizes");
+  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
+  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
+  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
+#define PLMC_SM(DC)                                                                                                                         \
+  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, SmTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                        \
+                     SmTable<T, DC>{M, scales, means, weights}, X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
+  if (d == 1) PLMC_SM(1);
+  else if (d <= 4) PLMC_SM(4);
+  else PLMC_SM(8);
+#undef PLMC_SM
+  return launch_status(__func__);
+}
+
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,
                   int ncols, int skip) {
+  if (job.means) {                                    // spectral mixture (plmc_factorize_sm_ex_*)
+    if (elem_bytes == 4)
+      return assemble_sm_impl<float>((const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.means,
+                                     (const float *)job.oscale, (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+    return assemble_sm_impl<double>((const double *)job.X, job.n, job.d, job.ncomp, (const double *)job.ell, (const double *)job.means,
+                                    (const double *)job.oscale, (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+  }
   if (job.ncomp != 1) {                               // additive kernel (plmc_factorize_add_ex_*)
     if (elem_bytes == 4)
       return assemble_add_impl<float>(job.kind, (const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.oscale,
@@ -603,6 +717,26 @@ int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, 
                                            stream);
 }
 int plmc_max_components(void) { return plmc::MAX_COMP; }
+int plmc_sm_max_mixtures(void) { return plmc::SM_MAX_MIX; }
+int plmc_sm_max_dim(void) { return plmc::SM_MAX_DIM; }
+int plmc_assemble_sm_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                         const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_sm_impl<float>(X, n, d, nmix, scales, means, weights, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_sm_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                         const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_sm_impl<double>(X, n, d, nmix, scales, means, weights, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_cross_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means,
+                               const float *weights, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream) {
+  return plmc::assemble_cross_sm_impl<float>(X, n, Xs, ns, d, nmix, scales, means, weights, Out, ldo, strideO, col0, n_rows, q, stream);
+}
+int plmc_assemble_cross_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means,
+                               const double *weights, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream) {
+  return plmc::assemble_cross_sm_impl<double>(X, n, Xs, ns, d, nmix, scales, means, weights, Out, ldo, strideO, col0, n_rows, q, stream);
+}
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
   return plmc::assemble_add_impl<float>(kind, X, n, d, ncomp, ell, oscale, noise, A, lda, strideA, q, stream);

@@ -129,6 +129,45 @@ template <typename T> __device__ __forceinline__ Pair<T> kern_value_pair(int kin
   const Pair<T> s = T(2.23606797749979) * r;
   return (T(1) + s + T(5.0 / 3.0) * r2) * Pair<T>{dexp(-s.x), dexp(-s.y)};
 }
+
+// ---- spectral mixture [gpytorch-knowledge: SpectralMixtureKernel.forward]:
+//     k(x, x') = sum_m w_m exp(-2 pi^2 sum_k s_mk^2 tau_k^2) prod_k cos(2 pi mu_mk tau_k),   tau = x - x'.
+// The carrier's phase mu tau is hundreds to thousands of revolutions at the sizes this library is built for (mu up to 0.5 / the
+// smallest spacing), so it is reduced IN REVOLUTIONS before the cosine: tau = a - b with its rounding residual (TwoSum), t = mu tau
+// with its FMA residual, f = t - rint(t) (exact) with the residuals added back; |f| <= 1/2 + a few ulp carries an absolute error of a
+// few 2^-25 whatever the phase was ("Spectral mixture: the phase in fp32").
+template <typename T> __device__ __forceinline__ T sm_phase(T a, T b, T mu) {
+  const T tau = a - b;
+  const T bv = tau - a;
+  const T te = (a - (tau - bv)) - (b + bv);               // a - b = tau + te exactly
+  const T t = mu * tau;
+  const T tr = __builtin_fma(mu, tau, -t);                // mu tau = t + tr exactly
+  return (t - __builtin_rint(t)) + __builtin_fma(mu, te, tr);
+}
+// cos / sin of 2 pi f.  Assembly: the library's cospi (fp32: ~1 ulp); gradient epilogue (fp32): the hardware forms, which take revolutions
+__device__ __forceinline__ float  sm_cos(float f) { return cospif(2.0f * f); }
+__device__ __forceinline__ double sm_cos(double f) { return cospi(2.0 * f); }
+__device__ __forceinline__ void sm_sincos_fast(float f, float &s, float &c) { s = __builtin_amdgcn_sinf(f); c = __builtin_amdgcn_cosf(f); }
+__device__ __forceinline__ void sm_sincos_fast(double f, double &s, double &c) { sincospi(2.0 * f, &s, &c); }
+constexpr double SM_2PI2 = 19.739208802178716;             // 2 pi^2
+constexpr double SM_2PI = 6.283185307179586;
+// one covariance value (unit noise-free): rows of DCAP raw coordinates a, b; sc, mu [M][DCAP] (0 beyond d: factor exactly 1), wt [M]
+template <typename T, int DCAP>
+__device__ __forceinline__ T sm_value(const T (&a)[DCAP], const T (&b)[DCAP], const T *sc, const T *mu, const T *wt, int M) {
+  T sum = T(0);
+#pragma unroll 1
+  for (int m = 0; m < M; ++m) {
+    T e = T(0), c = T(1);
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      const T st = sc[m * DCAP + k] * (a[k] - b[k]);
+      e += st * st;
+      c *= sm_cos(sm_phase(a[k], b[k], mu[m * DCAP + k]));
+    }
+    sum += wt[m] * (dexp(T(-SM_2PI2) * e) * c);
+  }
+  return sum;
+}
 #undef dexp
 #undef dsqrt
 

@@ -1473,6 +1473,24 @@ int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp
   const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise, ncomp};
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
+// The same for a spectral-mixture kernel (plmc_assemble_sm_*): the job carries the table
+int plmc_factorize_sm_ex_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                             const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                             int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE_SM(nmix, d, means);
+  const plmc::AssembleJob job{0, n, d, X, scales, weights, noise, nmix, means};
+  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
+}
+int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                             const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                             int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
+  (void)eig_lo;
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE_SM(nmix, d, means);
+  const plmc::AssembleJob job{0, n, d, X, scales, weights, noise, nmix, means};
+  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
+}
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

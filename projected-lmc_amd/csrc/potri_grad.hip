@@ -228,20 +228,28 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // ---- additive kernels (sum of `ncomp` <= MAX_COMP scaled stationary ARD kernels): the two kernels above with the epilogue of
 // kinv_epilogue_add.inc.  One instantiation per element type / split scheme: the input dimension and the component count are run-time
 // loop bounds there.  The single kernel (ncomp = 1) never comes here (kinv_grad_impl).
-template <typename T>
+// SMDC != 0: the same kernels for a spectral-mixture kernel of up to SMDC input dimensions (kinv_epilogue_sm.inc): ncomp = its components,
+// ell = its scales, oscale = its weights, `means` its means; `kind` is not looked at.
+template <typename T, int SMDC>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                        const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
-                                                       int64_t strideK, T *kinv_diag, double *__restrict__ partials) {
+                                                       int64_t strideK, T *kinv_diag, double *__restrict__ partials, const T *__restrict__ means) {
   if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
+  if constexpr (SMDC == 0) {
 #include "kinv_epilogue_add.inc"
+  } else {
+    constexpr int DC = SMDC;
+#include "kinv_epilogue_sm.inc"
+  }
 }
 
-template <typename T>
-__global__ __launch_bounds__(NTHREADS, 2) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+template <typename T, int SMDC = 0>
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && SMDC > 0 ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
-                                                                int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat) {
+                                                                int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
+                                                                const T *__restrict__ means) {
   const int m = (int)(n_pad / NB);
   const int lat = (int)blockIdx.x % nlat;              // tile order of k_kinv_grad
   int ib, jb;
@@ -253,16 +261,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_kinv_grad_add(int kind, int nco
   tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem);
   const int tid = threadIdx.x;
   constexpr bool live = true;
+  if constexpr (SMDC == 0) {
 #include "kinv_epilogue_add.inc"
+  } else {
+    constexpr int DC = SMDC;
+#include "kinv_epilogue_sm.inc"
+  }
 }
 
-template <class S>
+template <class S, int SMDC = 0>
 __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int ncomp, int64_t n_pad, const float *__restrict__ alpha,
                                                                 const float *__restrict__ X, int n, int d, const float *__restrict__ ell,
                                                                 const float *__restrict__ oscale, float *Kinv, int64_t ldk, int64_t strideK,
                                                                 float *kinv_diag, double *__restrict__ partials, int nlat,
                                                                 const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
-                                                                int64_t wp_lat_stride, int64_t ws_stride) {
+                                                                int64_t wp_lat_stride, int64_t ws_stride, const float *__restrict__ means) {
   constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float);
   __shared__ __align__(16) unsigned char lds[LDS_BYTES];
   const int m = (int)(n_pad / NB);
@@ -290,8 +303,8 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int nc
   b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));
   const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
   const int ib = ibm + half;
-  kinv_tile_epilogue_add<float>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
-                                ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials);
+  kinv_tile_epilogue_add<float, SMDC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
+                                      ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
 }
 
 // grad[lat][k] = 1/2 * sum over upper tiles of partials, with the 1/ell_k factor for lengthscales.
@@ -336,7 +349,8 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad(const double *__restrict
 // The reduction for the additive kernels: the tile's partials are `ncomp` rows of GP slots.  grid (q, ncomp), the thread layout and the
 // summation order of k_reduce_grad.  grad[lat]: [ d/d ell (ncomp x d) | d/d noise | d/d oscale (ncomp) ] -- for one component the
 // layout of k_reduce_grad.  A dimension outside its component (ell = +inf) gets 0.5 * 0 / inf = 0.
-template <typename T>
+// SM: the rows of kinv_epilogue_sm.inc, grad[lat]: [ d/d scales (ncomp x d) | d/d means (ncomp x d) | d/d noise | d/d weights (ncomp) ]
+template <typename T, bool SM = false>
 __global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__restrict__ partials, int m, int d, int ncomp,
                                                             const T *__restrict__ ell, double *__restrict__ grad) {
   __shared__ double red[RED_NT];
@@ -366,6 +380,14 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__rest
     double tot = 0.0;
     for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
     const int k = threadIdx.x;
+    if constexpr (SM) {
+      double *gl = grad + (int64_t)lat * (ncomp * (2 * d + 1) + 1);
+      if (k < d) gl[g * d + k] = -2.0 * SM_2PI2 * 0.5 * tot;
+      else if (k >= SM_MAX_DIM && k < SM_MAX_DIM + d) gl[(ncomp + g) * d + k - SM_MAX_DIM] = -SM_2PI * 0.5 * tot;
+      else if (k == MAX_DIM && g == 0) gl[2 * ncomp * d] = 0.5 * tot;
+      else if (k == MAX_DIM + 1) gl[2 * ncomp * d + 1 + g] = 0.5 * tot;
+      return;
+    }
     double *gl = grad + (int64_t)lat * (ncomp * (d + 1) + 1);
     if (k < d) gl[g * d + k] = 0.5 * tot / (double)ell[((int64_t)lat * ncomp + g) * d + k];
     else if (k == MAX_DIM && g == 0) gl[ncomp * d] = 0.5 * tot;
@@ -405,8 +427,10 @@ template <typename T, class S>
 int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n,
                    int d, const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK,
                    T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream, const float *Vd = nullptr, int64_t lda_vd = 0,
-                   int ncomp = 1) {
+                   int ncomp = 1, const T *means = nullptr) {
   // ncomp > 1: additive kernel, ell (q, ncomp, d), oscale (q, ncomp), `partials` and `grad` ncomp times as wide (plmc_kinv_grad_add_vd_*)
+  // means: spectral mixture of ncomp components, ell = its scales, oscale = its weights (plmc_kinv_grad_sm_vd_*)
+  PLMC_REQUIRE(!means || d <= SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -427,6 +451,7 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
+      PLMC_REQUIRE(!means, "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * ncomp * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
       float *wsco = reinterpret_cast<float *>(pb + (int64_t)q * b3_elems<SplitB3>(n_pad, n_pad) * 2);
@@ -444,9 +469,12 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   hipLaunchKernelGGL((k_kinv_grad_bf3<S, DC, SP>), gridb, dim3(B3_NT), 0, st, kind, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, \
                      part, q, wp, wsc, wp_lat, ws_lat)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-    if (ncomp > 1)
-      hipLaunchKernelGGL((k_kinv_grad_add_bf3<S>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK,
-                         kinv_diag, part, q, wp, wsc, wp_lat, ws_lat);
+#define PLMC_LAUNCH_SB(DC) \
+  hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
+                     kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)means)
+    if (means) PLMC_LAUNCH_SB(1);                        // (d = 1 only: kinv_grad_f32_any)
+    else if (ncomp > 1) PLMC_LAUNCH_SB(0);
+#undef PLMC_LAUNCH_SB
     else if (d <= 4) PLMC_LAUNCH_KB(4, false);
     else if (d <= 8) PLMC_LAUNCH_KB(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KB(16, true); else PLMC_LAUNCH_KB(16, false); }
@@ -458,9 +486,12 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   hipLaunchKernelGGL((k_kinv_grad<T, DC, SP>), grid, block, 0, st, kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, \
                      oscale, Kinv, ldk, strideK, kinv_diag, part, q)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-    if (ncomp > 1)
-      hipLaunchKernelGGL((k_kinv_grad_add<T>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk,
-                         strideK, kinv_diag, part, q);
+#define PLMC_LAUNCH_SG(DC) \
+  hipLaunchKernelGGL((k_kinv_grad_add<T, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
+                     strideK, kinv_diag, part, q, means)
+    if (means) { if (d == 1) PLMC_LAUNCH_SG(1); else if (d <= 4) PLMC_LAUNCH_SG(4); else PLMC_LAUNCH_SG(8); }
+    else if (ncomp > 1) PLMC_LAUNCH_SG(0);
+#undef PLMC_LAUNCH_SG
     else if (d <= 4) PLMC_LAUNCH_KG(4, false);
     else if (d <= 8) PLMC_LAUNCH_KG(8, false);
     else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KG(16, true); else PLMC_LAUNCH_KG(16, false); }
@@ -469,7 +500,8 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   }
   {
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * ncomp * GP * sizeof(double) / 2);
-    if (ncomp > 1) hipLaunchKernelGGL(k_reduce_grad_add<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
+    if (means) hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
+    else if (ncomp > 1) hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
     else hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
   }
   return launch_status(__func__);
@@ -493,17 +525,20 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
 static int kinv_grad_f32_any(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                              const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                              float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo,
-                             void *stream, const float *Vd = nullptr, int ncomp = 1) {
+                             void *stream, const float *Vd = nullptr, int ncomp = 1, const float *means = nullptr) {
   const int split = plmc::knobs().split;
-  if (split == 0)
+  // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
+  // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
+  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.
+  if (split == 0 || (means && d > 1))
     return plmc::kinv_grad_impl<float, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                             nullptr, stream, nullptr, 0, ncomp);
+                                             nullptr, stream, nullptr, 0, ncomp, means);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
     return plmc::kinv_grad_impl<float, plmc::SplitH2>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp);
+                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp, means);
   return plmc::kinv_grad_impl<float, plmc::SplitB3>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                    partials, q, nullptr, stream, Vd, ldw, ncomp);
+                                                    partials, q, nullptr, stream, Vd, ldw, ncomp, means);
 }
 int plmc_kinv_grad_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                        const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
@@ -555,6 +590,27 @@ int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t 
                                             strideK, kinv_diag, partials, q, nullptr, stream, nullptr, 0, ncomp);
 }
 #undef PLMC_REQUIRE_ADD
+// spectral-mixture kernel: plmc_kinv_grad_vd_* with the table (scales, means, weights) (include/plmc.h)
+int64_t plmc_sm_grad_partials_bytes(int64_t n_pad, int q, int nmix, int elem_bytes) {
+  (void)elem_bytes;                                   // one row of fp64 partial sums per tile and component, whatever the element type
+  return plmc_grad_partials_bytes(n_pad, q * nmix);
+}
+int plmc_kinv_grad_sm_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                             int nmix, const float *scales, const float *means, const float *weights, double *grad, float *Kinv, int64_t ldk,
+                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
+  PLMC_REQUIRE_SM(nmix, d, means);
+  return kinv_grad_f32_any(0, W, n_pad, ldw, strideW, alpha, X, n, d, scales, weights, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream,
+                           Vd, nmix, means);
+}
+int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                             int nmix, const double *scales, const double *means, const double *weights, double *grad, double *Kinv, int64_t ldk,
+                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  PLMC_REQUIRE_SM(nmix, d, means);
+  return plmc::kinv_grad_impl<double, void>(0, W, n_pad, ldw, strideW, alpha, X, n, d, scales, weights, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                                            nullptr, stream, nullptr, 0, nmix, means);
+}
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,

@@ -22,7 +22,7 @@ class Workspace:
     """Caller-owned device buffers for q latent GPs on n points with naug augmented columns.
     Layout documented in include/plmc.h."""
 
-    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False, ncomp=1):
+    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False, ncomp=1, sm=False):
         L = _hip.lib()
         self.n, self.q, self.naug, self.dtype, self.device = n, q, naug, dtype, device
         self.ncomp = ncomp               # components of an additive kernel: the gradient kernel writes one row of partial sums per tile and component
@@ -56,7 +56,9 @@ class Workspace:
             self.alpha = torch.empty(q, self.n_pad, dtype=dtype, device=device)
             # per-tile partial sums of the gradient kernel; the 16-bit planes of W it multiplies are left in Vd by the sweep
             # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none
-            nbytes = int(L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
+            # (a spectral-mixture table: the library's own size call for it, include/plmc.h "Spectral-mixture kernel")
+            nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(self.n_pad, q, ncomp, esz) if sm
+                         else L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
             self.partials = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
 
 
@@ -78,14 +80,15 @@ def _drop_all():
     _ws_cache.clear()
 
 
-def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1):
+def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1, sm=False):
     ncomp = ncomp if need_grad else 1                   # (only the partial sums of the gradient kernel depend on it)
-    key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp)
+    sm = bool(sm) and bool(need_grad)
+    key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp, sm)
     ws = _ws_cache.get(key)
     if ws is None:
         if len(_ws_cache) > 3:
             _drop_all()
-        ws = Workspace(n, q, naug, dtype, device, need_grad, ncomp=ncomp)
+        ws = Workspace(n, q, naug, dtype, device, need_grad, ncomp=ncomp, sm=sm)
         _ws_cache[key] = ws
     _release(ws)       # a gradient kernel of the previous evaluation may still be reading this workspace on the gradient stream
     return ws
@@ -124,16 +127,31 @@ def _contig(t, dtype=None):
 # latent -- or as the COMPONENT TABLE of an additive kernel, ell (q, G, d) with +inf (1 / ell = 0) on the dimensions a component
 # ignores and oscale (q, G) | None (include/plmc.h, "Additive kernels"; additive.py builds it).  The table goes to the `_add` entry
 # points, which take G in front of ell; everything else (workspaces, pivot checks, streams, caches) does not look at the kernel.
+# Kind "sm" (kernels.SpectralMixtureKernel): `ell` is the two planes of its table stacked, (q, 2, M, d) = [scales | means], `oscale` its
+# weights (q, M) | None; it goes to the `_sm` entry points, which take no kind and (M, scales, means) in the place of (G, ell)
+# (include/plmc.h, "Spectral-mixture kernel").  The gradient table [d scales | d means | d noise | d weights] splits like the others.
+_SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
+       "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd"}
 
 
+def is_sm(ell):
+    return ell.dim() == 4
+
+
 def n_components(ell):
-    return ell.shape[1] if ell.dim() == 3 else 1
+    return ell.shape[2] if ell.dim() == 4 else (ell.shape[1] if ell.dim() == 3 else 1)
+
+
+def kind_code(kind):
+    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code."""
+    return None if kind == "sm" else _hip.KIND[kind]
 
 
 def grad_table_width(ell):
-    """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)]."""
+    """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)];
+    spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights]."""
     return ell[0].numel() + 1 + n_components(ell)
 
 
@@ -141,13 +159,27 @@ def _check_kernel_shape(L, ell):
     d = ell.shape[-1]
     if d > L.cdll.plmc_max_dim():
         raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
-    if n_components(ell) > L.cdll.plmc_max_components():
+    if is_sm(ell):
+        if d > L.cdll.plmc_sm_max_dim() or n_components(ell) > L.cdll.plmc_sm_max_mixtures():
+            raise ValueError("spectral mixture with %d components on %d dimensions exceeds plmc_sm_max_mixtures()=%d / plmc_sm_max_dim()=%d"
+                             % (n_components(ell), d, L.cdll.plmc_sm_max_mixtures(), L.cdll.plmc_sm_max_dim()))
+    elif n_components(ell) > L.cdll.plmc_max_components():
         raise ValueError("%d additive components exceed plmc_max_components()=%d" % (n_components(ell), L.cdll.plmc_max_components()))
 
 
-def _kernel_call(L, base, dt, head, ell, tail):
-    """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table."""
-    if ell.dim() == 3:
+def _kernel_call(L, base, dt, head, ell, tail, stream=None):
+    """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
+    form (*head[1:], M, scales, means, *tail).  `stream`: the side stream the call is queued on, if not the current one."""
+    if ell.dim() == 4:
+        planes = getattr(ell, "_sm_planes", None)            # split once per table: the 3-4 calls of a step share the two copies
+        if planes is None:
+            planes = ell._sm_planes = (ell[:, 0].contiguous(), ell[:, 1].contiguous())
+        scales, means = planes
+        if stream is not None:
+            scales.record_stream(stream)
+            means.record_stream(stream)
+        L.call(_SM[base], dt, *head[1:], ell.shape[2], _hip.ptr(scales), _hip.ptr(means), *tail)
+    elif ell.dim() == 3:
         L.call(_ADD[base], dt, *head, ell.shape[1], _hip.ptr(ell), *tail)
     else:
         L.call(base, dt, *head, _hip.ptr(ell), *tail)
@@ -167,7 +199,7 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
     L = _hip.lib()
     dt, dev = ws.dtype, ws.device
     st = _hip.stream_ptr(dev)
-    k = _hip.KIND[kind]
+    k = kind_code(kind)
     q, n, d = ws.q, ws.n, X.shape[1]
     # round 4: assembly and sweep as ONE library call (plmc_factorize_ex_*): the sweep writes the rows of its first group itself and
     # queues the others beside that group's chain (same kernels, same data: bit-identical; PLMC_FUSED_ASSEMBLE=0: two calls)
@@ -233,7 +265,7 @@ class ExactLatentLogProb(torch.autograd.Function):
         G = n_components(ell)
         need_grad = any(ctx.needs_input_grad[1:5]) or table is not None
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, need_grad, G)
+        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell))
         st = _hip.stream_ptr(dev)
         grad = table if table is not None else (torch.empty(q, grad_table_width(ell), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
@@ -257,9 +289,9 @@ class ExactLatentLogProb(torch.autograd.Function):
                     for t in (grad, Xc, ellc, osc, noise_eff):
                         if t is not None:
                             t.record_stream(gs)
-                _kernel_call(L, "plmc_kinv_grad_vd", dt, (_hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
+                _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
                              _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad),
-                             None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst))
+                             None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst), stream=gs)
                 if gs is not None:
                     ws.pending = torch.cuda.Event()
                     ws.pending.record(gs)
@@ -277,7 +309,7 @@ class ExactLatentLogProb(torch.autograd.Function):
             if check and info.failed():
                 def attempt(jit):
                     nonlocal ws
-                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G)   # waits for the failed attempt's gradient kernel
+                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell))   # waits for the failed attempt's gradient kernel
                     return enqueue(nzc + jit)
 
                 logp = walk(dt, info, attempt)[1]
@@ -377,7 +409,7 @@ def exact_loo(kind, X, ell, oscale, noise, y):
     d = X.shape[1]
     Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
     _check_kernel_shape(L, ellc)
-    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc))
+    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc), is_sm(ellc))
     st = _hip.stream_ptr(dev)
     factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
     L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
@@ -386,7 +418,7 @@ def exact_loo(kind, X, ell, oscale, noise, y):
            _hip.ptr(ws.alpha), q, st)
     grad = torch.empty(q, grad_table_width(ellc), dtype=torch.float64, device=dev)
     kd = torch.empty(q, ws.n_pad, dtype=dt, device=dev)
-    _kernel_call(L, "plmc_kinv_grad_vd", dt, (_hip.KIND[kind], _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
+    _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
                  _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad), None, 0, 0, _hip.ptr(kd),
                  _hip.ptr(ws.partials), q, _hip.ptr(nzc), _hip.ptr(ws.Vd), st))
     sigma2 = 1.0 / kd[:, :n]
@@ -459,7 +491,7 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
             # new right-hand sides into the factorised buffer: y (column 0 shares its tile with the first test points, so it
             # is rewritten raw as well), K*^T behind it; then the forward substitution of those columns only
             cache.hits += 1
-            k = _hip.KIND[kind]
+            k = kind_code(kind)
             L.call("plmc_write_rhs", dt, _hip.ptr(yc), 1, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
             _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, Xc.shape[1]), ellc, (_hip.ptr(osc),
                          _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + 1, ws.n_pad, q, st))
@@ -512,7 +544,7 @@ def dense_cross(kind, X1, X2, ell, oscale):
     q = ell.shape[0]
     n1, n2, d = X1.shape[0], X2.shape[0], X1.shape[1]
     out = torch.empty(q, n1, n2, dtype=dt, device=dev)
-    _kernel_call(L, "plmc_assemble_cross", dt, (_hip.KIND[kind], _hip.ptr(X1.contiguous()), n1, _hip.ptr(X2.contiguous()), n2, d),
+    _kernel_call(L, "plmc_assemble_cross", dt, (kind_code(kind), _hip.ptr(X1.contiguous()), n1, _hip.ptr(X2.contiguous()), n2, d),
                  ell.contiguous(), (_hip.ptr(None if oscale is None else oscale.contiguous()), _hip.ptr(out),
                  n2, n1 * n2, 0, n1, q, _hip.stream_ptr(dev)))
     return out

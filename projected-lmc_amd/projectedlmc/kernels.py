@@ -93,8 +93,88 @@ class SplineKernel(Kernel):
         return torch.ones(q, d, dtype=like.dtype, device=like.device)
 
 
+class SpectralMixtureKernel(Kernel):
+    """Spectral-mixture kernel [gpytorch-knowledge: SpectralMixtureKernel; realdata_experiments.py:130-140 runs the tidal study with it]:
+        k(x, x') = sum_m w_m exp(-2 pi^2 sum_k s_mk^2 tau_k^2) prod_k cos(2 pi mu_mk tau_k),   tau = x - x'.
+    gpytorch's parameter names and shapes, so state dicts line up: raw_mixture_weights (*batch, M), raw_mixture_means and
+    raw_mixture_scales (*batch, M, 1, d), zero-initialised, Positive constraints.  No lengthscale.  On the HIP path it is kernel kind
+    "sm" of the batched exact engine (include/plmc.h, "Spectral-mixture kernel"); SGPR, the dense LMC / ICM and the variational models
+    refuse it."""
+    has_lengthscale = False
+    kind = "sm"
+    is_stationary = True
+
+    def __init__(self, num_mixtures=None, ard_num_dims=1, batch_shape=torch.Size(), active_dims=None, mixture_scales_prior=None,
+                 mixture_scales_constraint=None, mixture_means_prior=None, mixture_means_constraint=None,
+                 mixture_weights_prior=None, mixture_weights_constraint=None, **kwargs):
+        if num_mixtures is None:
+            raise RuntimeError("num_mixtures is a required argument")
+        kwargs.pop("lengthscale_prior", None)                 # (handle_covar_ passes one to every kernel; this one has no lengthscale)
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, active_dims=active_dims, **kwargs)
+        self.num_mixtures = int(num_mixtures)
+        M, d = self.num_mixtures, 1 if ard_num_dims is None else int(ard_num_dims)
+        self.register_parameter("raw_mixture_weights", torch.nn.Parameter(torch.zeros(*self.batch_shape, M)))
+        self.register_parameter("raw_mixture_means", torch.nn.Parameter(torch.zeros(*self.batch_shape, M, 1, d)))
+        self.register_parameter("raw_mixture_scales", torch.nn.Parameter(torch.zeros(*self.batch_shape, M, 1, d)))
+        self.raw_mixture_weights_constraint = mixture_weights_constraint or Positive()
+        self.raw_mixture_means_constraint = mixture_means_constraint or Positive()
+        self.raw_mixture_scales_constraint = mixture_scales_constraint or Positive()
+
+    def _get(self, name):
+        return getattr(self, "raw_%s_constraint" % name).transform(getattr(self, "raw_" + name))
+
+    def _set(self, name, value):
+        raw = getattr(self, "raw_" + name)
+        value = torch.as_tensor(value, dtype=raw.dtype, device=raw.device)
+        with torch.no_grad():
+            raw.copy_(getattr(self, "raw_%s_constraint" % name).inverse_transform(value).expand_as(raw))
+
+    mixture_weights = property(lambda self: self._get("mixture_weights"), lambda self, v: self._set("mixture_weights", v))
+    mixture_means = property(lambda self: self._get("mixture_means"), lambda self, v: self._set("mixture_means", v))
+    mixture_scales = property(lambda self: self._get("mixture_scales"), lambda self, v: self._set("mixture_scales", v))
+
+    def initialize_from_data(self, train_x, train_y, **kwargs):
+        """[gpytorch-knowledge: SpectralMixtureKernel.initialize_from_data] per input dimension: scales = 1 / |N(0, max_dist^2)|, means ~
+        U(0, 0.5 / min_dist) with zero gaps between sorted inputs taken as 1e10, weights = std(y) / M."""
+        with torch.no_grad():
+            if train_x.dim() == 1:
+                train_x = train_x.unsqueeze(-1)
+            train_x = self.select(train_x)
+            srt = train_x.sort(dim=-2)[0]
+            max_dist = srt[..., -1, :] - srt[..., 0, :]
+            gaps = srt[..., 1:, :] - srt[..., :-1, :]
+            gaps = torch.where(gaps.eq(0.0), torch.full_like(gaps, 1.0e10), gaps)
+            min_dist = gaps.sort(dim=-2)[0][..., 0, :]
+            raw = self.raw_mixture_scales
+            like = dict(dtype=raw.dtype, device=raw.device)
+            max_dist, min_dist = max_dist.to(**like), min_dist.to(**like)
+            self.mixture_scales = (torch.randn_like(raw) * max_dist).abs().reciprocal()
+            self.mixture_means = torch.rand_like(self.raw_mixture_means) * (0.5 / min_dist)
+            self.mixture_weights = train_y.std().to(**like) / self.num_mixtures
+
+    def _pieces(self, d, like=None):
+        M = self.num_mixtures
+        scales = self.mixture_scales.reshape(-1, M, self.mixture_scales.shape[-1])
+        means = self.mixture_means.reshape(-1, M, self.mixture_means.shape[-1])
+        if scales.shape[-1] != d:
+            scales, means = scales.expand(-1, M, d), means.expand(-1, M, d)
+        return self.kind, torch.stack([scales, means], 1), self.mixture_weights.reshape(-1, M)
+
+
+def refuse_sm(kernel, model):
+    """The spectral-mixture kernel runs on the batched exact engine only: name the model that cannot take it."""
+    k = kernel
+    while k is not None and not isinstance(k, SpectralMixtureKernel):
+        k = getattr(k, "base_kernel", None)
+    if k is not None or (isinstance(kernel, type) and issubclass(kernel, SpectralMixtureKernel)):
+        raise NotImplementedError("%s does not take a SpectralMixtureKernel: it is served by the batched exact engine only "
+                                  "(ExactGPModel without inducing points, ProjectedGPModel)" % model)
+
+
 def prior_diagonal(kind, x, oscale, q):
     """k(x, x) per latent, (q, n): 1 for the stationary kinds, prod_k (1 + x_k^2 + x_k^3 / 3) for the spline kernel."""
+    if kind == "sm" and oscale is None:                        # unit weights: k(x, x) = M needs the table, not known here
+        raise ValueError("prior_diagonal: a spectral mixture needs its weights")
     if kind == "spline":
         dg = (1 + x ** 2 + x ** 3 / 3).prod(dim=-1).reshape(1, -1).expand(q, -1)
     else:
@@ -123,7 +203,9 @@ class ScaleKernel(Kernel):
             self.raw_outputscale.copy_(self.raw_outputscale_constraint.inverse_transform(value).expand_as(self.raw_outputscale))
 
     def _pieces(self, d, like=None):
-        kind, ell, _ = self.base_kernel._pieces(d, like if like is not None else self.raw_outputscale)
+        kind, ell, inner = self.base_kernel._pieces(d, like if like is not None else self.raw_outputscale)
+        if kind == "sm":                                       # the output scale folds into the mixture weights (q, M)
+            return kind, ell, self.outputscale.reshape(-1, 1) * inner
         return kind, ell, self.outputscale.reshape(-1)
 
 
@@ -131,7 +213,9 @@ class LazyKernel:
     """Un-evaluated batched covariance os * k(x1, x2; ell) (+ noise * I once a likelihood was
     applied).  The hot path never materialises it.
     ell (q, d), oscale (q) | None: one ARD kernel per latent.  ell (q, G, d), oscale (q, G): the component table of an additive
-    kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there."""
+    kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there.
+    kind "sm": ell (q, 2, M, d) holds the scales and the means of a spectral mixture, oscale (q, M) its weights (`scales`, `means`,
+    `weights`)."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise
@@ -152,6 +236,10 @@ class LazyKernel:
     @property
     def device(self):
         return self.x1.device
+
+    scales = property(lambda self: self.ell[:, 0] if self.kind == "sm" else None)
+    means = property(lambda self: self.ell[:, 1] if self.kind == "sm" else None)
+    weights = property(lambda self: self.oscale if self.kind == "sm" else None)
 
     @property
     def inv_ell(self):

@@ -55,6 +55,7 @@ def handle_covar_(kernel, dim, decomp=None, n_funcs=1, prior_scales=None, prior_
                 raise ValueError('Provided prior scales were of the wrong shape')
 
     if len(decomp) > 1:
+        _k.refuse_sm(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         # k(x) = sum_g s_g k_g(x[idx_g]): every sub-kernel gets an output scale (:159-162)
         from .additive import AdditiveKernel
         subs = []
@@ -271,6 +272,7 @@ class ExactGPModel(ExactGP):
                                           prior_width=prior_width, outputscales=outputscales, n_funcs=n_tasks,
                                           ker_kwargs=ker_kwargs)
         if n_inducing_points is not None:
+            _k.refuse_sm(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             from .sgpr import InducingPointKernel
             self.covar_module = InducingPointKernel(self.covar_module, torch.randn(n_inducing_points, self.dim),
                                                     likelihood)

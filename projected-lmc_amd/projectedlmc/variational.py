@@ -203,6 +203,7 @@ class VariationalMultitaskGPModel(torch.nn.Module):
                  outputscales=False, decomp=None, distrib=CholeskyVariationalDistribution, var_strat=VariationalStrategy,
                  ker_kwargs=None, **kwargs):
         super().__init__()
+        _k.refuse_sm(kernel_type, "VariationalMultitaskGPModel")
         if ker_kwargs is None:
             ker_kwargs = {}
         if train_x.ndimension() == 1:
