@@ -405,6 +405,55 @@ int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_
                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
 
 /*
+ * Periodic kernel [gpytorch-knowledge: PeriodicKernel.forward, v1.11, unverified offline] on the batched exact engine:
+ *     Khat_i = os[i] exp(-2 sum_k sin^2(pi tau_k / p[i][k]) / ell[i][k]) + noise[i] I,   tau = x - x'   (the lengthscale is not squared),
+ *     1 <= d <= plmc_per_max_dim().  Exceeding the limit or a null `period` is an argument error (plmc_last_error()); nothing is launched.
+ * Table, per latent i:  lengthscales ell and periods p (q x d each, contiguous), output scale os (q) or NULL (all ones).  noise: q.
+ * Every entry point takes the arguments of its plain form with (kind, ..., ell, oscale, ...) replaced by (..., ell, period, oscale, ...)
+ * and does what that form does:
+ *   plmc_assemble_per_*        plmc_assemble_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_per_*  plmc_assemble_cross_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_per_ex_*    plmc_factorize_ex_*    (assembly overlapped with the sweep; bit-identical to plmc_assemble_per_* followed
+ *                                                      by plmc_potrf_ex_*)
+ *   plmc_kinv_grad_per_vd_*    plmc_kinv_grad_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ * The phase tau / p is reduced in revolutions before the sine (difference and product with their rounding residuals, 1 / p as two
+ * terms), so the fp32 assembly is within 24 d 2^-24 os (1 + 1 / min_k ell_k) of the fp64 formula at the fp32 inputs per element, at any
+ * phase below 2^20 revolutions.  |K_ij| <= os + noise, the diagonal.
+ * Gradient table of plmc_kinv_grad_per_vd_* (double), 2 d + 2 entries per latent:
+ *     grad[latent] = [ d logp / d ell: d | d / d period: d | d / d noise | d / d os ]
+ *   The diagonal (tau = 0) contributes to noise and os only; an off-diagonal sine that is exactly 0 gives exactly 0.
+ *   plmc_kinv_grad_per_vd_f32 with d > 1 forms K^-1 with the fp32 matrix instructions whatever PLMC_SPLIT says (the knob and eig_lo
+ *   are not looked at; no planes of W are needed); d = 1 follows the knob like every other kernel.
+ * Scratch.  `Vd`: as for plmc_kinv_grad_vd_*.  `partials`: plmc_per_grad_partials_bytes(n_pad, q, elem bytes) bytes, one row of partial
+ *   sums per tile; a function of its arguments only, never of a dev knob.  The fp32 split engine takes the planes of W from the Vd of
+ *   the sweep that produced W and refuses a call without them; fp64 and PLMC_SPLIT=0 need no planes.
+ */
+int plmc_per_max_dim(void);                   /* largest input dimension of a periodic kernel (8) */
+int64_t plmc_per_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes);
+int plmc_assemble_per_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                          float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_per_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                          double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period,
+                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_assemble_cross_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
+                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_factorize_per_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_per_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                              double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_per_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              const float *ell, const float *period, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              const double *ell, const double *period, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

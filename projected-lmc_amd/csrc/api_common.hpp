@@ -13,6 +13,7 @@ constexpr int MAX_DIM = 32;          // largest input dimension handled by the f
 constexpr int MAX_COMP = 4;          // most components of an additive kernel (plmc_max_components())
 constexpr int SM_MAX_MIX = 8;        // most components of a spectral-mixture kernel (plmc_sm_max_mixtures())
 constexpr int SM_MAX_DIM = 8;        // largest input dimension of a spectral-mixture kernel (plmc_sm_max_dim())
+constexpr int PER_MAX_DIM = 8;       // largest input dimension of a periodic kernel (plmc_per_max_dim())
 
 char *err_buf();                     // thread-local, defined in api.hip
 
@@ -38,6 +39,11 @@ inline int launch_status(const char *fn) {
   PLMC_REQUIRE((M) >= 1 && (M) <= plmc::SM_MAX_MIX, "need 1 <= mixtures <= plmc_sm_max_mixtures()"); \
   PLMC_REQUIRE((d) > 0 && (d) <= plmc::SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");              \
   PLMC_REQUIRE((means) != nullptr, "null pointer")
+
+// limits of a periodic table (plmc_*_per_*): d input dimensions, `period` its second row
+#define PLMC_REQUIRE_PER(d, period)                                                                  \
+  PLMC_REQUIRE((d) > 0 && (d) <= plmc::PER_MAX_DIM, "need 0 < d <= plmc_per_max_dim()");    \
+  PLMC_REQUIRE((period) != nullptr, "null pointer")
 
 // kernel classes known to the optional profiler (api.hip)
 enum ProfKernel { PK_ASSEMBLE, PK_WRITE_RHS, PK_CROSS, PK_DIAG, PK_PANEL, PK_TRAIL, PK_WDIAG, PK_TRTRI, PK_EXTRACT,
@@ -75,11 +81,13 @@ const Knobs &knobs();
 // ncomp > 1: an additive kernel (plmc_factorize_add_ex_*), ell (q, ncomp, d) and oscale (q, ncomp)
 // means != null: a spectral-mixture kernel (plmc_factorize_sm_ex_*) of ncomp components, ell = its scales and means (q, ncomp, d),
 // oscale = its weights (q, ncomp) or null; `kind` is not looked at
+// per: a periodic kernel (plmc_factorize_per_ex_*), ell = its lengthscales and means = its periods (q, d), oscale (q) or null
 struct AssembleJob {
   int kind, n, d;
   const void *X, *ell, *oscale, *noise;
   int ncomp = 1;
   const void *means = nullptr;
+  bool per = false;
 };
 // block rows ib0 .. ib0 + nrows - 1 of the covariance matrices (assemble.hip), the first ncols block columns (< 0: all) without the
 // leading skip x skip block triangle; elem_bytes 4 / 8

@@ -374,7 +374,46 @@ template <typename T, int DCAP> struct SmTable {
   }
 };
 
-// d <= 8 (DCAP in {4, 8}; spectral mixture also 1); P: AddTable / SmTable
+// The periodic table (covariance.hpp): per latent lengthscales, periods (d), output scale | null.  In LDS: ip = 1 / p, its residual ipr,
+// w = 1 / ell [DCAP] each (0 beyond d: that dimension adds exactly 0 to the exponent), os.
+template <typename T, int DCAP> struct PerPairValue {
+  const T *ip, *ipr, *w;
+  T os;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    T b0[DCAP], b1[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) { b0[k] = xc[k].x; b1[k] = xc[k].y; }
+    return Pair<T>{os * per_value<T, DCAP>(xr, b0, ip, ipr, w), os * per_value<T, DCAP>(xr, b1, ip, ipr, w)};
+  }
+};
+template <typename T, int DCAP> struct PerTable {
+  static constexpr int LDS = 3 * DCAP + 1;
+  const T *ell, *period, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < DCAP) {
+      T ip = T(0), ipr = T(0);
+      if (tid < d) per_inv_period(period[(int64_t)lat * d + tid], ip, ipr);
+      par[tid] = ip;
+      par[DCAP + tid] = ipr;
+      par[2 * DCAP + tid] = tid < d ? T(1) / ell[(int64_t)lat * d + tid] : T(0);
+    }
+    if (tid == 0) par[3 * DCAP] = oscale ? oscale[lat] : T(1);
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, PerPairValue<T, DCAP>{par, par + DCAP, par + 2 * DCAP, par[3 * DCAP]}, nz, Al, lda, ib, jb, n,
+                                 edge);
+  }
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T a[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) a[k] = xa[k];
+    return par[3 * DCAP] * per_value<T, DCAP>(a, xs, par, par + DCAP, par + 2 * DCAP);
+  }
+};
+
+// d <= 8 (DCAP in {4, 8}; spectral mixture and periodic also 1); P: AddTable / SmTable / PerTable
 template <typename T, int DCAP, class P>
 __global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
                                                                     const T *__restrict__ noise, T *__restrict__ A,
@@ -663,8 +702,62 @@ int assemble_cross_sm_impl(const T *X, int n, const T *Xs, int ns, int d, int M,
   return launch_status(__func__);
 }
 
+// the periodic forms (include/plmc.h, "Periodic kernel"): the table kernels above with PerTable
+template <typename T>
+int assemble_per_impl(const T *X, int n, int d, const T *ell, const T *period, const T *oscale, const T *noise, T *A, int64_t lda,
+                      int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
+  PLMC_REQUIRE_PER(d, period);
+  PLMC_REQUIRE(X && ell && noise && A, "null pointer");
+  PLMC_REQUIRE(n > 0 && q > 0, "need n>0, q>0");
+  const int64_t n_pad = plmc_pad(n);
+  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
+  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
+  const int m = (int)(n_pad / NB);
+  if (nrows < 0) nrows = m - ib0;
+  if (ncols < 0) ncols = m;
+  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
+  if (nrows == 0 || ncols == 0) return 0;
+  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
+  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
+  const dim3 grid(ncols, nrows, q);
+#define PLMC_PER(DC)                                                                                                                        \
+  hipLaunchKernelGGL((k_assemble_small_table<T, DC, PerTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                       \
+                     PerTable<T, DC>{ell, period, oscale}, X, n, d, noise, A, lda, strideA, ib0, skip)
+  if (d == 1) PLMC_PER(1);
+  else if (d <= 4) PLMC_PER(4);
+  else PLMC_PER(8);
+#undef PLMC_PER
+  return launch_status(__func__);
+}
+
+template <typename T>
+int assemble_cross_per_impl(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *period, const T *oscale, T *Out,
+                            int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
+  PLMC_REQUIRE_PER(d, period);
+  PLMC_REQUIRE(X && Xs && ell && Out, "null pointer");
+  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0, "bad sizes");
+  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
+  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
+  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
+#define PLMC_PER(DC)                                                                                                                        \
+  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, PerTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                       \
+                     PerTable<T, DC>{ell, period, oscale}, X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
+  if (d == 1) PLMC_PER(1);
+  else if (d <= 4) PLMC_PER(4);
+  else PLMC_PER(8);
+#undef PLMC_PER
+  return launch_status(__func__);
+}
+
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,
                   int ncols, int skip) {
+  if (job.per) {                                      // periodic (plmc_factorize_per_ex_*)
+    if (elem_bytes == 4)
+      return assemble_per_impl<float>((const float *)job.X, job.n, job.d, (const float *)job.ell, (const float *)job.means,
+                                      (const float *)job.oscale, (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+    return assemble_per_impl<double>((const double *)job.X, job.n, job.d, (const double *)job.ell, (const double *)job.means,
+                                     (const double *)job.oscale, (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+  }
   if (job.means) {                                    // spectral mixture (plmc_factorize_sm_ex_*)
     if (elem_bytes == 4)
       return assemble_sm_impl<float>((const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.means,
@@ -736,6 +829,25 @@ int plmc_assemble_cross_sm_f64(const double *X, int n, const double *Xs, int ns,
                                const double *weights, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
                                void *stream) {
   return plmc::assemble_cross_sm_impl<double>(X, n, Xs, ns, d, nmix, scales, means, weights, Out, ldo, strideO, col0, n_rows, q, stream);
+}
+int plmc_per_max_dim(void) { return plmc::PER_MAX_DIM; }
+int plmc_assemble_per_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                          float *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_per_impl<float>(X, n, d, ell, period, oscale, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_per_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                          double *A, int64_t lda, int64_t strideA, int q, void *stream) {
+  return plmc::assemble_per_impl<double>(X, n, d, ell, period, oscale, noise, A, lda, strideA, q, stream);
+}
+int plmc_assemble_cross_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period,
+                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream) {
+  return plmc::assemble_cross_per_impl<float>(X, n, Xs, ns, d, ell, period, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
+}
+int plmc_assemble_cross_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
+                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream) {
+  return plmc::assemble_cross_per_impl<double>(X, n, Xs, ns, d, ell, period, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {

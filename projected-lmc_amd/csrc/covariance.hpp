@@ -168,6 +168,48 @@ __device__ __forceinline__ T sm_value(const T (&a)[DCAP], const T (&b)[DCAP], co
   }
   return sum;
 }
+
+// ---- periodic [gpytorch-knowledge: PeriodicKernel.forward, v1.11, unverified offline]:
+//     k(x, x') = exp(-2 sum_k sin^2(pi (x_k - x'_k) / p_k) / ell_k)            (the lengthscale is not squared).
+// The phase f_k = tau_k / p_k is reduced in revolutions like the spectral mixture's (sm_phase) with the inverse period as the frequency.
+// 1 / p is staged as TWO terms, ip = fl(1 / p) and ipr = fl(fl(1 - ip p) ip) ~ 1 / p - ip (the FMA's 1 - ip p is exact), so that the
+// rounding of 1 / p does not cost f 2^-24 revolutions: tau ipr, at most f 2^-24, is added to the reduced phase.  sin^2(pi f) has period 1
+// in f, sin(2 pi f) too, so the reduction to |f| <= 1/2 changes neither ("Periodic kernel: the phase in fp32").
+template <typename T> __device__ __forceinline__ void per_inv_period(T p, T &ip, T &ipr) {
+  ip = T(1) / p;
+  ipr = __builtin_fma(-ip, p, T(1)) * ip;
+}
+template <typename T> __device__ __forceinline__ T per_phase(T a, T b, T ip, T ipr) {
+  return sm_phase(a, b, ip) + (a - b) * ipr;
+}
+// sin(pi f).  Assembly: the library's sinpi (fp32: ~1 ulp)
+__device__ __forceinline__ float  per_sinpi(float f) { return sinpif(f); }
+__device__ __forceinline__ double per_sinpi(double f) { return sinpi(f); }
+// gradient epilogue: s2 = sin(2 pi f) and omc = 1 - cos(2 pi f) = 2 sin^2(pi f), the latter from sin(pi f) (no cancellation at small f).
+// fp32: the hardware sine, which takes revolutions
+__device__ __forceinline__ void per_sin_fast(float f, float &s2, float &omc) {
+  const float s1 = __builtin_amdgcn_sinf(0.5f * f);
+  s2 = __builtin_amdgcn_sinf(f);
+  omc = 2.0f * s1 * s1;
+}
+__device__ __forceinline__ void per_sin_fast(double f, double &s2, double &omc) {
+  double s1, c1;
+  sincospi(f, &s1, &c1);
+  s2 = 2.0 * s1 * c1;
+  omc = 2.0 * s1 * s1;
+}
+// one covariance value (unit output scale): rows of DCAP raw coordinates a, b; ip, ipr, w = 1 / ell [DCAP] (all 0 beyond d: that
+// dimension adds exactly 0 to the exponent)
+template <typename T, int DCAP>
+__device__ __forceinline__ T per_value(const T (&a)[DCAP], const T (&b)[DCAP], const T *ip, const T *ipr, const T *w) {
+  T e = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    const T s = per_sinpi(per_phase(a[k], b[k], ip[k], ipr[k]));
+    e += (s * s) * w[k];
+  }
+  return dexp(T(-2) * e);
+}
 #undef dexp
 #undef dsqrt
 

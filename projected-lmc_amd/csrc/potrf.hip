@@ -1491,6 +1491,24 @@ int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const doub
   const plmc::AssembleJob job{0, n, d, X, scales, weights, noise, nmix, means};
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
+// The same for a periodic kernel (plmc_assemble_per_*): the job carries the lengthscales and the periods
+int plmc_factorize_per_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const float *eig_lo, void *stream) {
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE_PER(d, period);
+  const plmc::AssembleJob job{0, n, d, X, ell, oscale, noise, 1, period, true};
+  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
+}
+int plmc_factorize_per_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                              double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const double *eig_lo, void *stream) {
+  (void)eig_lo;
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE_PER(d, period);
+  const plmc::AssembleJob job{0, n, d, X, ell, oscale, noise, 1, period, true};
+  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
+}
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

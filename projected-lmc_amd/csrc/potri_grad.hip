@@ -230,13 +230,18 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // loop bounds there.  The single kernel (ncomp = 1) never comes here (kinv_grad_impl).
 // SMDC != 0: the same kernels for a spectral-mixture kernel of up to SMDC input dimensions (kinv_epilogue_sm.inc): ncomp = its components,
 // ell = its scales, oscale = its weights, `means` its means; `kind` is not looked at.
-template <typename T, int SMDC>
+// PERDC != 0: the same kernels for a periodic kernel of up to PERDC input dimensions (kinv_epilogue_per.inc): ell = its lengthscales,
+// `means` its periods, oscale (q) or null; `kind` and ncomp (1) are not looked at.
+template <typename T, int SMDC, int PERDC = 0>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                        const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                        int64_t strideK, T *kinv_diag, double *__restrict__ partials, const T *__restrict__ means) {
   if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
-  if constexpr (SMDC == 0) {
+  if constexpr (PERDC != 0) {
+    constexpr int DC = PERDC;
+#include "kinv_epilogue_per.inc"
+  } else if constexpr (SMDC == 0) {
 #include "kinv_epilogue_add.inc"
   } else {
     constexpr int DC = SMDC;
@@ -244,8 +249,8 @@ __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *sme
   }
 }
 
-template <typename T, int SMDC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && SMDC > 0 ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+template <typename T, int SMDC = 0, int PERDC = 0>
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (SMDC > 0 || PERDC > 1) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
@@ -261,7 +266,10 @@ __global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && SMDC > 0 ? 1 : 2)) voi
   tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem);
   const int tid = threadIdx.x;
   constexpr bool live = true;
-  if constexpr (SMDC == 0) {
+  if constexpr (PERDC != 0) {
+    constexpr int DC = PERDC;
+#include "kinv_epilogue_per.inc"
+  } else if constexpr (SMDC == 0) {
 #include "kinv_epilogue_add.inc"
   } else {
     constexpr int DC = SMDC;
@@ -269,7 +277,7 @@ __global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && SMDC > 0 ? 1 : 2)) voi
   }
 }
 
-template <class S, int SMDC = 0>
+template <class S, int SMDC = 0, int PERDC = 0>
 __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int ncomp, int64_t n_pad, const float *__restrict__ alpha,
                                                                 const float *__restrict__ X, int n, int d, const float *__restrict__ ell,
                                                                 const float *__restrict__ oscale, float *Kinv, int64_t ldk, int64_t strideK,
@@ -303,8 +311,8 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int nc
   b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));
   const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
   const int ib = ibm + half;
-  kinv_tile_epilogue_add<float, SMDC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
-                                      ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
+  kinv_tile_epilogue_add<float, SMDC, PERDC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
+                                             ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
 }
 
 // grad[lat][k] = 1/2 * sum over upper tiles of partials, with the 1/ell_k factor for lengthscales.
@@ -395,6 +403,50 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__rest
   }
 }
 
+// The reduction for the periodic kernel: one row of GP slots per tile (kinv_epilogue_per.inc), the thread layout and the summation
+// order of k_reduce_grad.  grad[lat]: [ d/d ell (d) | d/d period (d) | d/d noise | d/d oscale ], with the factors the epilogue left out.
+template <typename T>
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_per(const double *__restrict__ partials, int m, int d, const T *__restrict__ ell,
+                                                            const T *__restrict__ period, double *__restrict__ grad) {
+  __shared__ double red[RED_NT];
+  const int lat = blockIdx.x;
+  const int ntile = m * m;
+  const int slot = threadIdx.x % GP;
+  const int grp = threadIdx.x / GP;
+  constexpr int NG = RED_NT / GP;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if (grp < NG) {
+    const double *base = partials + (int64_t)lat * ntile * GP + slot;
+    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int t = t0 + u * NG;
+        if (t < ntile) {
+          const int ib = t / m, jb = t - ib * m;
+          if (jb >= ib) s[u] += base[(int64_t)t * GP];
+        }
+      }
+    }
+  }
+  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+  __syncthreads();
+  if (threadIdx.x < GP) {
+    double tot = 0.0;
+    for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
+    const int k = threadIdx.x;
+    double *gl = grad + (int64_t)lat * (2 * d + 2);
+    if (k < d) {
+      const double l = (double)ell[(int64_t)lat * d + k];
+      gl[k] = 0.5 * tot / (l * l);
+    } else if (k >= PER_MAX_DIM && k < PER_MAX_DIM + d) {
+      const int kk = k - PER_MAX_DIM;
+      const double l = (double)ell[(int64_t)lat * d + kk], p = (double)period[(int64_t)lat * d + kk];
+      gl[d + kk] = 0.5 * tot * SM_2PI / (l * p * p);
+    } else if (k == MAX_DIM) gl[2 * d] = 0.5 * tot;
+    else if (k == MAX_DIM + 1) gl[2 * d + 1] = 0.5 * tot;
+  }
+}
+
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -427,10 +479,12 @@ template <typename T, class S>
 int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n,
                    int d, const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK,
                    T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream, const float *Vd = nullptr, int64_t lda_vd = 0,
-                   int ncomp = 1, const T *means = nullptr) {
+                   int ncomp = 1, const T *means = nullptr, bool per = false) {
   // ncomp > 1: additive kernel, ell (q, ncomp, d), oscale (q, ncomp), `partials` and `grad` ncomp times as wide (plmc_kinv_grad_add_vd_*)
   // means: spectral mixture of ncomp components, ell = its scales, oscale = its weights (plmc_kinv_grad_sm_vd_*)
+  // per: periodic kernel, ell = its lengthscales, means = its periods (q, d), oscale (q) or null, ncomp = 1 (plmc_kinv_grad_per_vd_*)
   PLMC_REQUIRE(!means || d <= SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");
+  PLMC_REQUIRE(!per || (means && ncomp == 1 && d <= PER_MAX_DIM), "need 0 < d <= plmc_per_max_dim()");
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -451,6 +505,7 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
+      PLMC_REQUIRE(!per, "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
       PLMC_REQUIRE(!means, "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * ncomp * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
@@ -472,7 +527,10 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
 #define PLMC_LAUNCH_SB(DC) \
   hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
                      kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)means)
-    if (means) PLMC_LAUNCH_SB(1);                        // (d = 1 only: kinv_grad_f32_any)
+    if (per)                                             // (d = 1 only: kinv_grad_f32_any)
+      hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, 0, 1>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK,
+                         kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)means);
+    else if (means) PLMC_LAUNCH_SB(1);                   // (d = 1 only: kinv_grad_f32_any)
     else if (ncomp > 1) PLMC_LAUNCH_SB(0);
 #undef PLMC_LAUNCH_SB
     else if (d <= 4) PLMC_LAUNCH_KB(4, false);
@@ -489,7 +547,12 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
 #define PLMC_LAUNCH_SG(DC) \
   hipLaunchKernelGGL((k_kinv_grad_add<T, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
                      strideK, kinv_diag, part, q, means)
-    if (means) { if (d == 1) PLMC_LAUNCH_SG(1); else if (d <= 4) PLMC_LAUNCH_SG(4); else PLMC_LAUNCH_SG(8); }
+#define PLMC_LAUNCH_PG(DC) \
+  hipLaunchKernelGGL((k_kinv_grad_add<T, 0, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
+                     strideK, kinv_diag, part, q, means)
+    if (per) { if (d == 1) PLMC_LAUNCH_PG(1); else if (d <= 4) PLMC_LAUNCH_PG(4); else PLMC_LAUNCH_PG(8); }
+#undef PLMC_LAUNCH_PG
+    else if (means) { if (d == 1) PLMC_LAUNCH_SG(1); else if (d <= 4) PLMC_LAUNCH_SG(4); else PLMC_LAUNCH_SG(8); }
     else if (ncomp > 1) PLMC_LAUNCH_SG(0);
 #undef PLMC_LAUNCH_SG
     else if (d <= 4) PLMC_LAUNCH_KG(4, false);
@@ -500,7 +563,8 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
   }
   {
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * ncomp * GP * sizeof(double) / 2);
-    if (means) hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
+    if (per) hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, means, grad);
+    else if (means) hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
     else if (ncomp > 1) hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
     else hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
   }
@@ -525,20 +589,21 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
 static int kinv_grad_f32_any(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                              const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                              float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo,
-                             void *stream, const float *Vd = nullptr, int ncomp = 1, const float *means = nullptr) {
+                             void *stream, const float *Vd = nullptr, int ncomp = 1, const float *means = nullptr, bool per = false) {
   const int split = plmc::knobs().split;
   // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
   // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
-  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.
+  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel (`per`, means = its
+  // periods) keeps d sines, cosine complements and 2 d sums live and follows the same rule.
   if (split == 0 || (means && d > 1))
     return plmc::kinv_grad_impl<float, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                             nullptr, stream, nullptr, 0, ncomp, means);
+                                             nullptr, stream, nullptr, 0, ncomp, means, per);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
     return plmc::kinv_grad_impl<float, plmc::SplitH2>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp, means);
+                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp, means, per);
   return plmc::kinv_grad_impl<float, plmc::SplitB3>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                    partials, q, nullptr, stream, Vd, ldw, ncomp, means);
+                                                    partials, q, nullptr, stream, Vd, ldw, ncomp, means, per);
 }
 int plmc_kinv_grad_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                        const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
@@ -610,6 +675,27 @@ int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_
   PLMC_REQUIRE_SM(nmix, d, means);
   return plmc::kinv_grad_impl<double, void>(0, W, n_pad, ldw, strideW, alpha, X, n, d, scales, weights, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
                                             nullptr, stream, nullptr, 0, nmix, means);
+}
+// periodic kernel: plmc_kinv_grad_vd_* with the table (lengthscales, periods, output scale) (include/plmc.h)
+int64_t plmc_per_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
+  (void)elem_bytes;                                   // one row of fp64 partial sums per tile, whatever the element type
+  return plmc_grad_partials_bytes(n_pad, q);
+}
+int plmc_kinv_grad_per_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              const float *ell, const float *period, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
+  PLMC_REQUIRE_PER(d, period);
+  return kinv_grad_f32_any(0, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream,
+                           Vd, 1, period, true);
+}
+int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              const double *ell, const double *period, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  PLMC_REQUIRE_PER(d, period);
+  return plmc::kinv_grad_impl<double, void>(0, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                                            nullptr, stream, nullptr, 0, 1, period, true);
 }
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,

@@ -22,7 +22,7 @@ class Workspace:
     """Caller-owned device buffers for q latent GPs on n points with naug augmented columns.
     Layout documented in include/plmc.h."""
 
-    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False, ncomp=1, sm=False):
+    def __init__(self, n, q, naug, dtype, device, with_inverse=True, keep_planes=False, ncomp=1, sm=False, per=False):
         L = _hip.lib()
         self.n, self.q, self.naug, self.dtype, self.device = n, q, naug, dtype, device
         self.ncomp = ncomp               # components of an additive kernel: the gradient kernel writes one row of partial sums per tile and component
@@ -57,7 +57,9 @@ class Workspace:
             # per-tile partial sums of the gradient kernel; the 16-bit planes of W it multiplies are left in Vd by the sweep
             # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none
             # (a spectral-mixture table: the library's own size call for it, include/plmc.h "Spectral-mixture kernel")
+            # (a periodic table likewise: "Periodic kernel")
             nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(self.n_pad, q, ncomp, esz) if sm
+                         else L.cdll.plmc_per_grad_partials_bytes(self.n_pad, q, esz) if per
                          else L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
             self.partials = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
 
@@ -80,15 +82,16 @@ def _drop_all():
     _ws_cache.clear()
 
 
-def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1, sm=False):
+def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1, sm=False, per=False):
     ncomp = ncomp if need_grad else 1                   # (only the partial sums of the gradient kernel depend on it)
     sm = bool(sm) and bool(need_grad)
-    key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp, sm)
+    per = bool(per) and bool(need_grad)
+    key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp, sm, per)
     ws = _ws_cache.get(key)
     if ws is None:
         if len(_ws_cache) > 3:
             _drop_all()
-        ws = Workspace(n, q, naug, dtype, device, need_grad, ncomp=ncomp, sm=sm)
+        ws = Workspace(n, q, naug, dtype, device, need_grad, ncomp=ncomp, sm=sm, per=per)
         _ws_cache[key] = ws
     _release(ws)       # a gradient kernel of the previous evaluation may still be reading this workspace on the gradient stream
     return ws
@@ -130,6 +133,13 @@ def _contig(t, dtype=None):
 # Kind "sm" (kernels.SpectralMixtureKernel): `ell` is the two planes of its table stacked, (q, 2, M, d) = [scales | means], `oscale` its
 # weights (q, M) | None; it goes to the `_sm` entry points, which take no kind and (M, scales, means) in the place of (G, ell)
 # (include/plmc.h, "Spectral-mixture kernel").  The gradient table [d scales | d means | d noise | d weights] splits like the others.
+# Kind "periodic" (kernels.PeriodicKernel): `ell` is the two rows of its table stacked, (q, 2, d) = [lengthscales | periods], `oscale`
+# (q) | None; it goes to the `_per` entry points, which take no kind and (ell, period) in the place of ell (include/plmc.h, "Periodic
+# kernel").  Its table has the rank of an additive one, so the functions that size things take the kind beside it.  The gradient table
+# [d lengthscales | d periods | d noise | d oscale] splits like the others.
+PER = "periodic"
+_PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
+        "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
@@ -140,26 +150,35 @@ def is_sm(ell):
     return ell.dim() == 4
 
 
-def n_components(ell):
+def n_components(ell, kind=None):
+    if kind == PER:
+        return 1
     return ell.shape[2] if ell.dim() == 4 else (ell.shape[1] if ell.dim() == 3 else 1)
 
 
 def kind_code(kind):
-    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code."""
-    return None if kind == "sm" else _hip.KIND[kind]
+    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic kernel
+    likewise: its name stands in the code's place and sends _kernel_call to them."""
+    return None if kind == "sm" else (PER if kind == PER else _hip.KIND[kind])
 
 
-def grad_table_width(ell):
+def grad_table_width(ell, kind=None):
     """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)];
-    spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights]."""
-    return ell[0].numel() + 1 + n_components(ell)
+    spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights];
+    periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale]."""
+    return ell[0].numel() + 1 + n_components(ell, kind)
 
 
-def _check_kernel_shape(L, ell):
+def _check_kernel_shape(L, ell, kind=None):
     d = ell.shape[-1]
     if d > L.cdll.plmc_max_dim():
         raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
-    if is_sm(ell):
+    if kind == PER:
+        if ell.dim() != 3 or ell.shape[1] != 2:
+            raise ValueError("a periodic kernel's table is (q, 2, d) = [lengthscales | periods]")
+        if d > L.cdll.plmc_per_max_dim():
+            raise ValueError("periodic kernel on %d dimensions exceeds plmc_per_max_dim()=%d" % (d, L.cdll.plmc_per_max_dim()))
+    elif is_sm(ell):
         if d > L.cdll.plmc_sm_max_dim() or n_components(ell) > L.cdll.plmc_sm_max_mixtures():
             raise ValueError("spectral mixture with %d components on %d dimensions exceeds plmc_sm_max_mixtures()=%d / plmc_sm_max_dim()=%d"
                              % (n_components(ell), d, L.cdll.plmc_sm_max_mixtures(), L.cdll.plmc_sm_max_dim()))
@@ -169,8 +188,17 @@ def _check_kernel_shape(L, ell):
 
 def _kernel_call(L, base, dt, head, ell, tail, stream=None):
     """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
-    form (*head[1:], M, scales, means, *tail).  `stream`: the side stream the call is queued on, if not the current one."""
-    if ell.dim() == 4:
+    form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER.
+    `stream`: the side stream the call is queued on, if not the current one."""
+    if isinstance(head[0], str) and head[0] == PER:
+        rows = getattr(ell, "_per_rows", None)               # split once per table, as the spectral mixture's planes below
+        if rows is None:
+            rows = ell._per_rows = (ell[:, 0].contiguous(), ell[:, 1].contiguous())
+        if stream is not None:
+            rows[0].record_stream(stream)
+            rows[1].record_stream(stream)
+        L.call(_PER[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), *tail)
+    elif ell.dim() == 4:
         planes = getattr(ell, "_sm_planes", None)            # split once per table: the 3-4 calls of a step share the two copies
         if planes is None:
             planes = ell._sm_planes = (ell[:, 0].contiguous(), ell[:, 1].contiguous())
@@ -261,13 +289,13 @@ class ExactLatentLogProb(torch.autograd.Function):
             raise TypeError("projectedlmc hot path supports float32 and float64 tensors")
         q, n = y.shape
         d = X.shape[1]
-        _check_kernel_shape(L, ell)
-        G = n_components(ell)
+        _check_kernel_shape(L, ell, kind)
+        G = n_components(ell, kind)
         need_grad = any(ctx.needs_input_grad[1:5]) or table is not None
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell))
+        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), kind == PER)
         st = _hip.stream_ptr(dev)
-        grad = table if table is not None else (torch.empty(q, grad_table_width(ell), dtype=torch.float64, device=dev) if need_grad else None)
+        grad = table if table is not None else (torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
 
         def enqueue(noise_eff):
@@ -309,7 +337,7 @@ class ExactLatentLogProb(torch.autograd.Function):
             if check and info.failed():
                 def attempt(jit):
                     nonlocal ws
-                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell))   # waits for the failed attempt's gradient kernel
+                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), kind == PER)   # waits for the failed attempt's gradient kernel
                     return enqueue(nzc + jit)
 
                 logp = walk(dt, info, attempt)[1]
@@ -364,7 +392,7 @@ class HyperGradHandle:
     __slots__ = ("table", "hz")
 
 
-def prepare_hyper_grad(ell, oscale, noise):
+def prepare_hyper_grad(ell, oscale, noise, kind=None):
     """Create the hyper-parameter gradient node (_HyperGrad) NOW and return a handle for exact_latent_log_prob, or
     None when there is nothing to do (no gradient stream, nothing requires grad, host tensors).
     Autograd runs backward nodes in reverse creation order, and the caller's stream is made to wait for the gradient
@@ -381,7 +409,7 @@ def prepare_hyper_grad(ell, oscale, noise):
         zero = _zeros[key] = torch.zeros(q, dtype=ell.dtype, device=ell.device)
         torch.cuda.current_stream(ell.device).synchronize()
     h = HyperGradHandle()
-    h.table = torch.empty(q, grad_table_width(ell), dtype=torch.float64, device=ell.device)
+    h.table = torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=ell.device)
     with torch.cuda.stream(gs):
         h.hz = _HyperGrad.apply(ell, oscale, noise, h.table, zero)
     return h
@@ -389,7 +417,7 @@ def prepare_hyper_grad(ell, oscale, noise):
 
 def exact_latent_log_prob(kind, X, ell, oscale, noise, y, hyper=None):
     if hyper is None:
-        hyper = prepare_hyper_grad(ell, oscale, noise)
+        hyper = prepare_hyper_grad(ell, oscale, noise, kind)
     if hyper is None:
         return ExactLatentLogProb.apply(X, ell, oscale, noise, y, kind)
     det = lambda t: None if t is None else t.detach()
@@ -408,15 +436,15 @@ def exact_loo(kind, X, ell, oscale, noise, y):
     q, n = y.shape
     d = X.shape[1]
     Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-    _check_kernel_shape(L, ellc)
-    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc), is_sm(ellc))
+    _check_kernel_shape(L, ellc, kind)
+    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), kind == PER)
     st = _hip.stream_ptr(dev)
     factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
     L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
            _hip.ptr(ws.quad), q, st)
     L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z),
            _hip.ptr(ws.alpha), q, st)
-    grad = torch.empty(q, grad_table_width(ellc), dtype=torch.float64, device=dev)
+    grad = torch.empty(q, grad_table_width(ellc, kind), dtype=torch.float64, device=dev)
     kd = torch.empty(q, ws.n_pad, dtype=dt, device=dev)
     _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
                  _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad), None, 0, 0, _hip.ptr(kd),
@@ -467,7 +495,7 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     q, n = y.shape
     ns = Xs.shape[0]
     Xc, Xsc, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xs, ell, oscale, noise))
-    _check_kernel_shape(L, ellc)
+    _check_kernel_shape(L, ellc, kind)
     yc = _contig(y).reshape(q, 1, n)
     st = _hip.stream_ptr(dev)
     mode = settings.prediction_cache.value() if cache is not None else "off"

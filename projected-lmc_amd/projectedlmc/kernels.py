@@ -161,6 +161,57 @@ class SpectralMixtureKernel(Kernel):
         return self.kind, torch.stack([scales, means], 1), self.mixture_weights.reshape(-1, M)
 
 
+class PeriodicKernel(Kernel):
+    """Periodic kernel [gpytorch-knowledge: PeriodicKernel.forward, v1.11, unverified offline]:
+        k(x, x') = exp(-2 sum_k sin^2(pi (x_k - x'_k) / p_k) / ell_k)            (the lengthscale is not squared).
+    gpytorch's parameter names and shapes, so state dicts line up: raw_lengthscale and raw_period_length (*batch, 1, d),
+    zero-initialised, Positive constraints.  On the HIP path it is kernel kind "periodic" of the batched exact engine (include/plmc.h,
+    "Periodic kernel"); the additive kernel, SGPR, the dense LMC / ICM and the variational models refuse it."""
+    has_lengthscale = True
+    kind = "periodic"
+    is_stationary = True
+
+    def __init__(self, ard_num_dims=None, batch_shape=torch.Size(), active_dims=None, period_length_prior=None,
+                 period_length_constraint=None, lengthscale_prior=None, lengthscale_constraint=None, **kwargs):
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, active_dims=active_dims,
+                         lengthscale_prior=lengthscale_prior, lengthscale_constraint=lengthscale_constraint, **kwargs)
+        nd = 1 if ard_num_dims is None else int(ard_num_dims)
+        self.period_length_prior = period_length_prior
+        self.register_parameter("raw_period_length", torch.nn.Parameter(torch.zeros(*self.batch_shape, 1, nd)))
+        self.raw_period_length_constraint = period_length_constraint or Positive()
+
+    @property
+    def period_length(self):
+        return self.raw_period_length_constraint.transform(self.raw_period_length)
+
+    @period_length.setter
+    def period_length(self, value):
+        value = torch.as_tensor(value, dtype=self.raw_period_length.dtype, device=self.raw_period_length.device)
+        with torch.no_grad():
+            self.raw_period_length.copy_(self.raw_period_length_constraint.inverse_transform(value).expand_as(self.raw_period_length))
+
+    def _pieces(self, d, like=None):
+        """The table (q, 2, d) = [lengthscale | period] and no output scale."""
+        period = self.period_length.reshape(-1, self.period_length.shape[-1])
+        if period.shape[-1] != d:
+            period = period.expand(period.shape[0], d)
+        return self.kind, torch.stack([self._ell(d, like), period], 1), None
+
+
+def _refuse(cls, name, kernel, model):
+    k = kernel
+    while k is not None and not isinstance(k, cls):
+        k = getattr(k, "base_kernel", None)
+    if k is not None or (isinstance(kernel, type) and issubclass(kernel, cls)):
+        raise NotImplementedError("%s does not take a %s: it is served by the batched exact engine only "
+                                  "(ExactGPModel without inducing points, ProjectedGPModel)" % (model, name))
+
+
+def refuse_periodic(kernel, model):
+    """The periodic kernel runs on the batched exact engine only: name the model that cannot take it."""
+    _refuse(PeriodicKernel, "PeriodicKernel", kernel, model)
+
+
 def refuse_sm(kernel, model):
     """The spectral-mixture kernel runs on the batched exact engine only: name the model that cannot take it."""
     k = kernel
@@ -215,7 +266,7 @@ class LazyKernel:
     ell (q, d), oscale (q) | None: one ARD kernel per latent.  ell (q, G, d), oscale (q, G): the component table of an additive
     kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there.
     kind "sm": ell (q, 2, M, d) holds the scales and the means of a spectral mixture, oscale (q, M) its weights (`scales`, `means`,
-    `weights`)."""
+    `weights`).  kind "periodic": ell (q, 2, d) holds the lengthscales and the periods, oscale (q) | None."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise

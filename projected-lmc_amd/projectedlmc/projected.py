@@ -496,7 +496,7 @@ class ProjectedLMCmll(ExactMarginalLogLikelihood):
             sel = (lambda t: t) if ids is None else (lambda t: t[ids])   # this rank's latents only
             ell_s, nz_s = sel(c.ell), sel(c.noise.reshape(-1))
             osc = None if c.oscale is None else sel(c.oscale)
-            hyper = _engine.prepare_hyper_grad(ell_s, osc, nz_s)
+            hyper = _engine.prepare_hyper_grad(ell_s, osc, nz_s, c.kind)
         proj_target = model.project_data(target)                         # q x n
         if exact:
             # the latent means are zero (ZeroMean is enforced at construction): nothing to subtract
