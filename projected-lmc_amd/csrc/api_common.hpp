@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "gemm_core.hpp"
+#include "covariance.hpp"
 
 namespace plmc {
 
@@ -33,17 +34,6 @@ inline int launch_status(const char *fn) {
 
 #define PLMC_REQUIRE(cond, msg) \
   do { if (!(cond)) return plmc::fail(__func__, msg); } while (0)
-
-// limits of a spectral-mixture table (plmc_*_sm_*): M components on d input dimensions, `means` its second plane
-#define PLMC_REQUIRE_SM(M, d, means)                                                                         \
-  PLMC_REQUIRE((M) >= 1 && (M) <= plmc::SM_MAX_MIX, "need 1 <= mixtures <= plmc_sm_max_mixtures()"); \
-  PLMC_REQUIRE((d) > 0 && (d) <= plmc::SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");              \
-  PLMC_REQUIRE((means) != nullptr, "null pointer")
-
-// limits of a periodic table (plmc_*_per_*): d input dimensions, `period` its second row
-#define PLMC_REQUIRE_PER(d, period)                                                                  \
-  PLMC_REQUIRE((d) > 0 && (d) <= plmc::PER_MAX_DIM, "need 0 < d <= plmc_per_max_dim()");    \
-  PLMC_REQUIRE((period) != nullptr, "null pointer")
 
 // kernel classes known to the optional profiler (api.hip)
 enum ProfKernel { PK_ASSEMBLE, PK_WRITE_RHS, PK_CROSS, PK_DIAG, PK_PANEL, PK_TRAIL, PK_WDIAG, PK_TRTRI, PK_EXTRACT,
@@ -76,18 +66,51 @@ struct Knobs {
 };
 const Knobs &knobs();
 
-// Covariance assembly handed to the sweep (plmc_factorize_ex_*): the sweep queues the rows of its first group on the caller's stream and
-// the rest on a helper stream beside the first group's chain, instead of the caller assembling the whole matrix in front of the sweep
-// ncomp > 1: an additive kernel (plmc_factorize_add_ex_*), ell (q, ncomp, d) and oscale (q, ncomp)
-// means != null: a spectral-mixture kernel (plmc_factorize_sm_ex_*) of ncomp components, ell = its scales and means (q, ncomp, d),
-// oscale = its weights (q, ncomp) or null; `kind` is not looked at
-// per: a periodic kernel (plmc_factorize_per_ex_*), ell = its lengthscales and means = its periods (q, d), oscale (q) or null
+// One covariance table: what a kernel family hands to the host layer, and the ONE place a family is declared to it.  Only the extern "C"
+// wrappers build one (from their flat arguments); assemble_impl, assemble_cross_impl, the sweep's AssembleJob and kinv_grad_impl take it.
+//   PLAIN  one ARD kernel of `kind` (covariance.hpp): ell (q, d), oscale (q) | null
+//   ADD    ncomp <= MAX_COMP stationary kernels of `kind` summed: ell (q, ncomp, d), oscale (q, ncomp) | null
+//   SM     spectral mixture of ncomp components: ell = its scales, second = its means (q, ncomp, d), oscale = its weights (q, ncomp) | null
+//   PER    periodic: ell = its lengthscales, second = its periods (q, d), oscale (q) | null
+// `kind` is not looked at for SM and PER; the pointers are of the call's element type.
+enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER };
+struct CovTable {
+  CovFamily family;
+  int kind, d, ncomp;
+  const void *ell, *second, *oscale;
+  static CovTable plain(int kind, int d, const void *ell, const void *oscale) { return {COV_PLAIN, kind, d, 1, ell, nullptr, oscale}; }
+  static CovTable add(int kind, int d, int ncomp, const void *ell, const void *oscale) { return {COV_ADD, kind, d, ncomp, ell, nullptr, oscale}; }
+  static CovTable sm(int d, int nmix, const void *scales, const void *means, const void *weights) { return {COV_SM, 0, d, nmix, scales, means, weights}; }
+  static CovTable per(int d, const void *ell, const void *period, const void *oscale) { return {COV_PER, 0, d, 1, ell, period, oscale}; }
+  // the family's limits: the message of the first one missed, or null
+  const char *check() const {
+    if (family == COV_ADD) {
+      if (kind < 0 || kind > K_MATERN52) return "additive kernels take the stationary kinds only (no spline kernel)";
+      if (ncomp < 1 || ncomp > MAX_COMP) return "need 1 <= components <= plmc_max_components()";
+    } else if (family == COV_SM) {
+      if (ncomp < 1 || ncomp > SM_MAX_MIX) return "need 1 <= mixtures <= plmc_sm_max_mixtures()";
+      if (d <= 0 || d > SM_MAX_DIM) return "need 0 < d <= plmc_sm_max_dim()";
+    } else if (family == COV_PER) {
+      if (d <= 0 || d > PER_MAX_DIM) return "need 0 < d <= plmc_per_max_dim()";
+    }
+    return (family == COV_SM || family == COV_PER) && !second ? "null pointer" : nullptr;
+  }
+  // the family whose kernels run: an additive table of one component IS the plain kernel (ell (q, 1, d) is ell (q, d)) and takes the
+  // plain instantiations, bit for bit
+  CovFamily route() const { return family == COV_ADD && ncomp == 1 ? COV_PLAIN : family; }
+  // rows of GP partial-sum slots per tile that the K^-1 + gradient kernels write (potri_grad.hip)
+  int partials_rows() const { return family == COV_ADD || family == COV_SM ? ncomp : 1; }
+};
+#define PLMC_REQUIRE_TABLE(t) \
+  do { if (const char *why_ = (t).check()) return plmc::fail(__func__, why_); } while (0)
+
+// Covariance assembly handed to the sweep (plmc_factorize*_ex_*): the sweep queues the rows of its first group on the caller's stream and
+// the rest on a helper stream beside the first group's chain, instead of the caller assembling the whole matrix in front of the sweep.
+// The sweep does not look at the table.
 struct AssembleJob {
-  int kind, n, d;
-  const void *X, *ell, *oscale, *noise;
-  int ncomp = 1;
-  const void *means = nullptr;
-  bool per = false;
+  CovTable table;
+  int n;
+  const void *X, *noise;
 };
 // block rows ib0 .. ib0 + nrows - 1 of the covariance matrices (assemble.hip), the first ncols block columns (< 0: all) without the
 // leading skip x skip block triangle; elem_bytes 4 / 8

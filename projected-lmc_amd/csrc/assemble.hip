@@ -532,14 +532,32 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross_table(const P prm, 
   }
 }
 
+// One launch of a table kernel: P<T, DC> is AddTable / SmTable / PerTable, `args` what follows the table in the kernel's signature
+template <typename T, int DC, template <typename, int> class P, class... Args>
+void launch_small_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... args) {
+  hipLaunchKernelGGL((k_assemble_small_table<T, DC, P<T, DC>>), grid, dim3(NTHREADS), 0, st, prm, args...);
+}
+template <typename T, int DC, template <typename, int> class P, class... Args>
+void launch_cross_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... args) {
+  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, P<T, DC>>), grid, dim3(NTHREADS), 0, st, prm, args...);
+}
+// the device-side tables of a descriptor
+template <typename T, int DC> AddTable<T, DC> add_table(const CovTable &t) { return {t.kind, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
+template <typename T, int DC> SmTable<T, DC> sm_table(const CovTable &t) { return {t.ncomp, (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
+template <typename T, int DC> PerTable<T, DC> per_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
+
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
 template <typename T>
-int assemble_impl(int kind, const T *X, int n, int d, const T *ell, const T *oscale, const T *noise, T *A,
-                  int64_t lda, int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
+int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, int64_t lda, int64_t strideA, int q, void *stream,
+                  int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
+  PLMC_REQUIRE_TABLE(t);
+  const int kind = t.kind, d = t.d;
+  const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
+  const bool small_only = t.family == COV_SM || t.family == COV_PER;       // d <= 8 by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
-  PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, "need n>0, q>0, 0<d<=plmc_max_dim()");
+  PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
   const int64_t n_pad = plmc_pad(n);
   PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
   PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
@@ -548,18 +566,39 @@ int assemble_impl(int kind, const T *X, int n, int d, const T *ell, const T *osc
   if (ncols < 0) ncols = m;
   PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
   if (nrows == 0 || ncols == 0) return 0;
-  size_t smem = 2 * NB * (d + 1) * sizeof(T);
   const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;   // upper tiles of these rows
-  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
-  if (d <= 4 && kind != K_SPLINE)              // the spline kernel is evaluated by the general kernel (not a function of r2)
-    hipLaunchKernelGGL((k_assemble_small<T, 4>), dim3(ncols, nrows, q), dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d,
-                       ell, oscale, noise, A, lda, strideA, ib0, skip);
-  else if (d <= 8 && kind != K_SPLINE)
-    hipLaunchKernelGGL((k_assemble_small<T, 8>), dim3(ncols, nrows, q), dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, d,
-                       ell, oscale, noise, A, lda, strideA, ib0, skip);
-  else
-    hipLaunchKernelGGL(k_assemble<T>, dim3(ncols, nrows, q), dim3(NTHREADS), smem, (hipStream_t)stream, kind, X, n, d, ell,
-                       oscale, noise, A, lda, strideA, ib0, skip);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(PK_ASSEMBLE, st, 0.0, q * tiles * NB * NB * sizeof(T));
+  const dim3 grid(ncols, nrows, q);
+  const auto table = [&](const auto &prm) { launch_small_table(grid, st, prm, X, n, d, noise, A, lda, strideA, ib0, skip); };
+  switch (t.route()) {
+    case COV_PLAIN:
+      if (d <= 4 && kind != K_SPLINE)            // the spline kernel is evaluated by the general kernel (not a function of r2)
+        hipLaunchKernelGGL((k_assemble_small<T, 4>), grid, dim3(NTHREADS), 0, st, kind, X, n, d, ell, oscale, noise, A, lda, strideA, ib0, skip);
+      else if (d <= 8 && kind != K_SPLINE)
+        hipLaunchKernelGGL((k_assemble_small<T, 8>), grid, dim3(NTHREADS), 0, st, kind, X, n, d, ell, oscale, noise, A, lda, strideA, ib0, skip);
+      else
+        hipLaunchKernelGGL(k_assemble<T>, grid, dim3(NTHREADS), 2 * NB * (d + 1) * sizeof(T), st, kind, X, n, d, ell, oscale, noise, A, lda,
+                           strideA, ib0, skip);
+      break;
+    case COV_ADD:
+      if (d <= 4) table(add_table<T, 4>(t));
+      else if (d <= 8) table(add_table<T, 8>(t));
+      else
+        hipLaunchKernelGGL(k_assemble_add<T>, grid, dim3(NTHREADS), (2 * NB * (d + 1) + t.ncomp * d + t.ncomp) * sizeof(T), st, kind, X, n, d,
+                           t.ncomp, ell, oscale, noise, A, lda, strideA, ib0, skip);
+      break;
+    case COV_SM:
+      if (d == 1) table(sm_table<T, 1>(t));
+      else if (d <= 4) table(sm_table<T, 4>(t));
+      else table(sm_table<T, 8>(t));
+      break;
+    case COV_PER:
+      if (d == 1) table(per_table<T, 1>(t));
+      else if (d <= 4) table(per_table<T, 4>(t));
+      else table(per_table<T, 8>(t));
+      break;
+  }
   return launch_status(__func__);
 }
 
@@ -581,213 +620,70 @@ int write_rhs_impl(const T *rhs, int nrhs, int n, T *A, int64_t lda, int64_t str
 }
 
 template <typename T>
-int assemble_cross_impl(int kind, const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *oscale, T *Out,
-                        int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
+int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int ns, T *Out, int64_t ldo, int64_t strideO, int64_t col0,
+                        int64_t n_rows, int q, void *stream) {
+  PLMC_REQUIRE_TABLE(t);
+  const int kind = t.kind, d = t.d;
+  const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && Xs && ell && Out, "null pointer");
   PLMC_REQUIRE(n > 0 && ns > 0 && q > 0 && d > 0 && d <= MAX_DIM, "bad sizes");
   PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
-  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(PK_CROSS, st, 0.0, q * (double)n_rows * ns * sizeof(T));
   const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
-#define PLMC_CROSS(DC) \
-  hipLaunchKernelGGL((k_assemble_cross<T, DC>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, kind, X, n, Xs, ns, d, ell, oscale, Out, n_rows, ldo, strideO, col0)
-  if (d <= 4) PLMC_CROSS(4);
-  else if (d <= 8) PLMC_CROSS(8);
-  else if (d <= 16) PLMC_CROSS(16);
-  else PLMC_CROSS(32);
-#undef PLMC_CROSS
-  return launch_status(__func__);
-}
-
-// the additive forms.  One component is the plain kernel (ell (q, 1, d) is ell (q, d)): the existing instantiations, bit for bit
-#define PLMC_REQUIRE_ADD(kind, G)                                                                                     \
-  PLMC_REQUIRE(kind >= 0 && kind <= K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)"); \
-  PLMC_REQUIRE(G >= 1 && G <= MAX_COMP, "need 1 <= components <= plmc_max_components()")
-template <typename T>
-int assemble_add_impl(int kind, const T *X, int n, int d, int G, const T *ell, const T *oscale, const T *noise, T *A,
-                      int64_t lda, int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
-  PLMC_REQUIRE_ADD(kind, G);
-  if (G == 1) return assemble_impl<T>(kind, X, n, d, ell, oscale, noise, A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-  PLMC_REQUIRE(X && ell && noise && A, "null pointer");
-  PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, "need n>0, q>0, 0<d<=plmc_max_dim()");
-  const int64_t n_pad = plmc_pad(n);
-  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
-  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
-  const int m = (int)(n_pad / NB);
-  if (nrows < 0) nrows = m - ib0;
-  if (ncols < 0) ncols = m;
-  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
-  if (nrows == 0 || ncols == 0) return 0;
-  const size_t smem = (2 * NB * (d + 1) + G * d + G) * sizeof(T);
-  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
-  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
-  const dim3 grid(ncols, nrows, q);
-  if (d <= 4)
-    hipLaunchKernelGGL((k_assemble_small_table<T, 4, AddTable<T, 4>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, 4>{kind, G, ell, oscale},
-                       X, n, d, noise, A, lda, strideA, ib0, skip);
-  else if (d <= 8)
-    hipLaunchKernelGGL((k_assemble_small_table<T, 8, AddTable<T, 8>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, 8>{kind, G, ell, oscale},
-                       X, n, d, noise, A, lda, strideA, ib0, skip);
-  else
-    hipLaunchKernelGGL(k_assemble_add<T>, grid, dim3(NTHREADS), smem, (hipStream_t)stream, kind, X, n, d, G, ell, oscale, noise, A, lda,
-                       strideA, ib0, skip);
-  return launch_status(__func__);
-}
-
-template <typename T>
-int assemble_cross_add_impl(int kind, const T *X, int n, const T *Xs, int ns, int d, int G, const T *ell, const T *oscale, T *Out,
-                            int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
-  PLMC_REQUIRE_ADD(kind, G);
-  if (G == 1) return assemble_cross_impl<T>(kind, X, n, Xs, ns, d, ell, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
-  PLMC_REQUIRE(X && Xs && ell && Out, "null pointer");
-  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0 && d > 0 && d <= MAX_DIM, "bad sizes");
-  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
-  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
-  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
-#define PLMC_CROSS(DC) \
-  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, AddTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream, AddTable<T, DC>{kind, G, ell, oscale}, \
-                     X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
-  if (d <= 4) PLMC_CROSS(4);
-  else if (d <= 8) PLMC_CROSS(8);
-  else if (d <= 16) PLMC_CROSS(16);
-  else PLMC_CROSS(32);
-#undef PLMC_CROSS
-  return launch_status(__func__);
-}
-
-// the spectral-mixture forms (include/plmc.h, "Spectral-mixture kernel"): the table kernels above with SmTable
-template <typename T>
-int assemble_sm_impl(const T *X, int n, int d, int M, const T *scales, const T *means, const T *weights, const T *noise, T *A,
-                     int64_t lda, int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
-  PLMC_REQUIRE_SM(M, d, means);
-  PLMC_REQUIRE(X && scales && noise && A, "null pointer");
-  PLMC_REQUIRE(n > 0 && q > 0, "need n>0, q>0");
-  const int64_t n_pad = plmc_pad(n);
-  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
-  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
-  const int m = (int)(n_pad / NB);
-  if (nrows < 0) nrows = m - ib0;
-  if (ncols < 0) ncols = m;
-  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
-  if (nrows == 0 || ncols == 0) return 0;
-  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
-  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
-  const dim3 grid(ncols, nrows, q);
-#define PLMC_SM(DC)                                                                                                                         \
-  hipLaunchKernelGGL((k_assemble_small_table<T, DC, SmTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                        \
-                     SmTable<T, DC>{M, scales, means, weights}, X, n, d, noise, A, lda, strideA, ib0, skip)
-  if (d == 1) PLMC_SM(1);
-  else if (d <= 4) PLMC_SM(4);
-  else PLMC_SM(8);
-#undef PLMC_SM
-  return launch_status(__func__);
-}
-
-template <typename T>
-int assemble_cross_sm_impl(const T *X, int n, const T *Xs, int ns, int d, int M, const T *scales, const T *means, const T *weights, T *Out,
-                           int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
-  PLMC_REQUIRE_SM(M, d, means);
-  PLMC_REQUIRE(X && Xs && scales && Out, "null pointer");
-  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0, "bad sizes");
-  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
-  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
-  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
-#define PLMC_SM(DC)                                                                                                                         \
-  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, SmTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                        \
-                     SmTable<T, DC>{M, scales, means, weights}, X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
-  if (d == 1) PLMC_SM(1);
-  else if (d <= 4) PLMC_SM(4);
-  else PLMC_SM(8);
-#undef PLMC_SM
-  return launch_status(__func__);
-}
-
-// the periodic forms (include/plmc.h, "Periodic kernel"): the table kernels above with PerTable
-template <typename T>
-int assemble_per_impl(const T *X, int n, int d, const T *ell, const T *period, const T *oscale, const T *noise, T *A, int64_t lda,
-                      int64_t strideA, int q, void *stream, int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
-  PLMC_REQUIRE_PER(d, period);
-  PLMC_REQUIRE(X && ell && noise && A, "null pointer");
-  PLMC_REQUIRE(n > 0 && q > 0, "need n>0, q>0");
-  const int64_t n_pad = plmc_pad(n);
-  PLMC_REQUIRE(lda >= n_pad && lda % NB == 0, "lda must be a multiple of NB and >= n_pad");
-  PLMC_REQUIRE(strideA >= n_pad * lda || q == 1, "strideA too small");
-  const int m = (int)(n_pad / NB);
-  if (nrows < 0) nrows = m - ib0;
-  if (ncols < 0) ncols = m;
-  PLMC_REQUIRE(ib0 >= 0 && nrows >= 0 && ib0 + nrows <= m && ncols <= m && skip >= 0, "row / column range outside the matrix");
-  if (nrows == 0 || ncols == 0) return 0;
-  const double tiles = (double)nrows * (m - ib0) - (double)nrows * (nrows - 1) / 2.0;
-  ProfScope ps(PK_ASSEMBLE, (hipStream_t)stream, 0.0, q * tiles * NB * NB * sizeof(T));
-  const dim3 grid(ncols, nrows, q);
-#define PLMC_PER(DC)                                                                                                                        \
-  hipLaunchKernelGGL((k_assemble_small_table<T, DC, PerTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                       \
-                     PerTable<T, DC>{ell, period, oscale}, X, n, d, noise, A, lda, strideA, ib0, skip)
-  if (d == 1) PLMC_PER(1);
-  else if (d <= 4) PLMC_PER(4);
-  else PLMC_PER(8);
-#undef PLMC_PER
-  return launch_status(__func__);
-}
-
-template <typename T>
-int assemble_cross_per_impl(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *period, const T *oscale, T *Out,
-                            int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {
-  PLMC_REQUIRE_PER(d, period);
-  PLMC_REQUIRE(X && Xs && ell && Out, "null pointer");
-  PLMC_REQUIRE(n > 0 && ns > 0 && q > 0, "bad sizes");
-  PLMC_REQUIRE(n_rows >= n && col0 >= 0 && col0 + ns <= ldo, "cross block exceeds the output buffer");
-  ProfScope ps(PK_CROSS, (hipStream_t)stream, 0.0, q * (double)n_rows * ns * sizeof(T));
-  const dim3 grid((ns + NTHREADS - 1) / NTHREADS, (unsigned)((n_rows + CROSS_ROWS - 1) / CROSS_ROWS), q);
-#define PLMC_PER(DC)                                                                                                                        \
-  hipLaunchKernelGGL((k_assemble_cross_table<T, DC, PerTable<T, DC>>), grid, dim3(NTHREADS), 0, (hipStream_t)stream,                       \
-                     PerTable<T, DC>{ell, period, oscale}, X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0)
-  if (d == 1) PLMC_PER(1);
-  else if (d <= 4) PLMC_PER(4);
-  else PLMC_PER(8);
-#undef PLMC_PER
+  const auto table = [&](const auto &prm) { launch_cross_table(grid, st, prm, X, n, Xs, ns, d, Out, n_rows, ldo, strideO, col0); };
+  const auto plain = [&](auto dc) {
+    hipLaunchKernelGGL((k_assemble_cross<T, decltype(dc)::value>), grid, dim3(NTHREADS), 0, st, kind, X, n, Xs, ns, d, ell, oscale, Out, n_rows, ldo,
+                       strideO, col0);
+  };
+  switch (t.route()) {
+    case COV_PLAIN:
+      if (d <= 4) plain(std::integral_constant<int, 4>());
+      else if (d <= 8) plain(std::integral_constant<int, 8>());
+      else if (d <= 16) plain(std::integral_constant<int, 16>());
+      else plain(std::integral_constant<int, 32>());
+      break;
+    case COV_ADD:
+      if (d <= 4) table(add_table<T, 4>(t));
+      else if (d <= 8) table(add_table<T, 8>(t));
+      else if (d <= 16) table(add_table<T, 16>(t));
+      else table(add_table<T, 32>(t));
+      break;
+    case COV_SM:
+      if (d == 1) table(sm_table<T, 1>(t));
+      else if (d <= 4) table(sm_table<T, 4>(t));
+      else table(sm_table<T, 8>(t));
+      break;
+    case COV_PER:
+      if (d == 1) table(per_table<T, 1>(t));
+      else if (d <= 4) table(per_table<T, 4>(t));
+      else table(per_table<T, 8>(t));
+      break;
+  }
   return launch_status(__func__);
 }
 
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,
                   int ncols, int skip) {
-  if (job.per) {                                      // periodic (plmc_factorize_per_ex_*)
-    if (elem_bytes == 4)
-      return assemble_per_impl<float>((const float *)job.X, job.n, job.d, (const float *)job.ell, (const float *)job.means,
-                                      (const float *)job.oscale, (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-    return assemble_per_impl<double>((const double *)job.X, job.n, job.d, (const double *)job.ell, (const double *)job.means,
-                                     (const double *)job.oscale, (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-  }
-  if (job.means) {                                    // spectral mixture (plmc_factorize_sm_ex_*)
-    if (elem_bytes == 4)
-      return assemble_sm_impl<float>((const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.means,
-                                     (const float *)job.oscale, (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-    return assemble_sm_impl<double>((const double *)job.X, job.n, job.d, job.ncomp, (const double *)job.ell, (const double *)job.means,
-                                    (const double *)job.oscale, (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-  }
-  if (job.ncomp != 1) {                               // additive kernel (plmc_factorize_add_ex_*)
-    if (elem_bytes == 4)
-      return assemble_add_impl<float>(job.kind, (const float *)job.X, job.n, job.d, job.ncomp, (const float *)job.ell, (const float *)job.oscale,
-                                      (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-    return assemble_add_impl<double>(job.kind, (const double *)job.X, job.n, job.d, job.ncomp, (const double *)job.ell, (const double *)job.oscale,
-                                     (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-  }
   if (elem_bytes == 4)
-    return assemble_impl<float>(job.kind, (const float *)job.X, job.n, job.d, (const float *)job.ell, (const float *)job.oscale, (const float *)job.noise,
-                                (float *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
-  return assemble_impl<double>(job.kind, (const double *)job.X, job.n, job.d, (const double *)job.ell, (const double *)job.oscale,
-                               (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows, ncols, skip);
+    return assemble_impl<float>(job.table, (const float *)job.X, job.n, (const float *)job.noise, (float *)A, lda, strideA, q, stream, ib0, nrows,
+                                ncols, skip);
+  return assemble_impl<double>(job.table, (const double *)job.X, job.n, (const double *)job.noise, (double *)A, lda, strideA, q, stream, ib0, nrows,
+                               ncols, skip);
 }
 }  // namespace plmc
 
+// the only place the covariance tables of this file are built from flat arguments
 extern "C" {
+using plmc::CovTable;
 int plmc_assemble_f32(int kind, const float *X, int n, int d, const float *ell, const float *oscale,
                       const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<float>(kind, X, n, d, ell, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<float>(CovTable::plain(kind, d, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale,
                       const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<double>(kind, X, n, d, ell, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<double>(CovTable::plain(kind, d, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_write_rhs_f32(const float *rhs, int nrhs, int n, float *A, int64_t lda, int64_t strideA, int c0,
                        int clear_cols, int q, void *stream) {
@@ -800,73 +696,69 @@ int plmc_write_rhs_f64(const double *rhs, int nrhs, int n, double *A, int64_t ld
 int plmc_assemble_cross_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, const float *ell,
                             const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
                             int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<float>(kind, X, n, Xs, ns, d, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
-                                          stream);
+  return plmc::assemble_cross_impl<float>(CovTable::plain(kind, d, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, const double *ell,
                             const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
                             int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<double>(kind, X, n, Xs, ns, d, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
-                                           stream);
+  return plmc::assemble_cross_impl<double>(CovTable::plain(kind, d, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_max_components(void) { return plmc::MAX_COMP; }
 int plmc_sm_max_mixtures(void) { return plmc::SM_MAX_MIX; }
 int plmc_sm_max_dim(void) { return plmc::SM_MAX_DIM; }
 int plmc_assemble_sm_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
                          const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_sm_impl<float>(X, n, d, nmix, scales, means, weights, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<float>(CovTable::sm(d, nmix, scales, means, weights), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_sm_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_sm_impl<double>(X, n, d, nmix, scales, means, weights, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<double>(CovTable::sm(d, nmix, scales, means, weights), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_cross_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means,
                                const float *weights, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
                                void *stream) {
-  return plmc::assemble_cross_sm_impl<float>(X, n, Xs, ns, d, nmix, scales, means, weights, Out, ldo, strideO, col0, n_rows, q, stream);
+  return plmc::assemble_cross_impl<float>(CovTable::sm(d, nmix, scales, means, weights), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_cross_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means,
                                const double *weights, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
                                void *stream) {
-  return plmc::assemble_cross_sm_impl<double>(X, n, Xs, ns, d, nmix, scales, means, weights, Out, ldo, strideO, col0, n_rows, q, stream);
+  return plmc::assemble_cross_impl<double>(CovTable::sm(d, nmix, scales, means, weights), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_per_max_dim(void) { return plmc::PER_MAX_DIM; }
 int plmc_assemble_per_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
                           float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_per_impl<float>(X, n, d, ell, period, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<float>(CovTable::per(d, ell, period, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_per_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
                           double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_per_impl<double>(X, n, d, ell, period, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<double>(CovTable::per(d, ell, period, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_cross_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period,
                                 const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
                                 void *stream) {
-  return plmc::assemble_cross_per_impl<float>(X, n, Xs, ns, d, ell, period, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
+  return plmc::assemble_cross_impl<float>(CovTable::per(d, ell, period, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_cross_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
                                 const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
                                 void *stream) {
-  return plmc::assemble_cross_per_impl<double>(X, n, Xs, ns, d, ell, period, oscale, Out, ldo, strideO, col0, n_rows, q, stream);
+  return plmc::assemble_cross_impl<double>(CovTable::per(d, ell, period, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_add_impl<float>(kind, X, n, d, ncomp, ell, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_add_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale,
                           const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_add_impl<double>(kind, X, n, d, ncomp, ell, oscale, noise, A, lda, strideA, q, stream);
+  return plmc::assemble_impl<double>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
 }
 int plmc_assemble_cross_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell,
                                 const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
                                 int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_add_impl<float>(kind, X, n, Xs, ns, d, ncomp, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
-                                              stream);
+  return plmc::assemble_cross_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 int plmc_assemble_cross_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell,
                                 const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
                                 int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_add_impl<double>(kind, X, n, Xs, ns, d, ncomp, ell, oscale, Out, ldo, strideO, col0, n_rows, q,
-                                               stream);
+  return plmc::assemble_cross_impl<double>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
 }

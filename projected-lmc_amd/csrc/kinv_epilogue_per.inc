@@ -1,6 +1,6 @@
 // kinv_epilogue_per.inc -- gradient epilogue of one 128 x 128 tile (ib, jb) of K^-1 held in `acc` for a PERIODIC kernel
 //     K = os exp(-2 sum_k sin^2(pi tau_k / p_k) / ell_k) + noise I                                     (covariance.hpp);
-// textually included where kinv_epilogue_add.inc is (k_kinv_grad_add, kinv_tile_epilogue_add) when their PERDC parameter is not 0.
+// textually included where kinv_epilogue_add.inc is (k_kinv_grad_add, kinv_tile_epilogue_add) when their family F is COV_PER.
 // Names it expects in scope: those of kinv_epilogue_add.inc with ell = the lengthscales (q, d), `means` = the periods (q, d), oscale
 // (q) or null, plus the compile-time dimension capacity DC (1, 4 or 8; d <= DC).  ncomp is 1 and not looked at.
 // Per element the d phases f_k = tau_k / p_k are reduced in revolutions (per_phase) and go through the hardware sine:

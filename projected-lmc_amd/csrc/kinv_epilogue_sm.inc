@@ -1,6 +1,6 @@
 // kinv_epilogue_sm.inc -- gradient epilogue of one 128 x 128 tile (ib, jb) of K^-1 held in `acc` for a SPECTRAL-MIXTURE kernel
 //     K = sum_m w_m exp(-2 pi^2 sum_k s_mk^2 tau_k^2) prod_k cos(2 pi mu_mk tau_k) + noise I          (covariance.hpp);
-// textually included where kinv_epilogue_add.inc is (k_kinv_grad_add, kinv_tile_epilogue_add) when their SMDC parameter is not 0.
+// textually included where kinv_epilogue_add.inc is (k_kinv_grad_add, kinv_tile_epilogue_add) when their family F is COV_SM.
 // Names it expects in scope: those of kinv_epilogue_add.inc with ncomp = the number of mixture components, ell = the scales and oscale =
 // the weights (or null), plus `means` and the compile-time dimension capacity DC (1, 4 or 8; d <= DC).
 // Per element and component: the d phases are reduced in revolutions (sm_phase) and go through the hardware sine / cosine; the

@@ -1442,7 +1442,7 @@ int plmc_factorize_ex_f32(int kind, const float *X, int n, int d, const float *e
                           int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q,
                           const float *eig_lo, void *stream) {
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise};
+  const plmc::AssembleJob job{plmc::CovTable::plain(kind, d, ell, oscale), n, X, noise};
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
 }
 int plmc_factorize_ex_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale, const double *noise, double *A,
@@ -1450,17 +1450,16 @@ int plmc_factorize_ex_f64(int kind, const double *X, int n, int d, const double 
                           const double *eig_lo, void *stream) {
   (void)eig_lo;
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise};
+  const plmc::AssembleJob job{plmc::CovTable::plain(kind, d, ell, oscale), n, X, noise};
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
-// The same for an additive kernel (plmc_assemble_add_*): the job carries the component count, the sweep does not look at it
+// The same for an additive kernel (plmc_assemble_add_*): the job carries the table, the sweep does not look at it
 int plmc_factorize_add_ex_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, const float *noise,
                               float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
                               int with_inverse, int q, const float *eig_lo, void *stream) {
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)");
-  PLMC_REQUIRE(ncomp >= 1 && ncomp <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()");
-  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise, ncomp};
+  const plmc::AssembleJob job{plmc::CovTable::add(kind, d, ncomp, ell, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
 }
 int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, const double *noise,
@@ -1468,9 +1467,8 @@ int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp
                               int with_inverse, int q, const double *eig_lo, void *stream) {
   (void)eig_lo;
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)");
-  PLMC_REQUIRE(ncomp >= 1 && ncomp <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()");
-  const plmc::AssembleJob job{kind, n, d, X, ell, oscale, noise, ncomp};
+  const plmc::AssembleJob job{plmc::CovTable::add(kind, d, ncomp, ell, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
 // The same for a spectral-mixture kernel (plmc_assemble_sm_*): the job carries the table
@@ -1478,8 +1476,8 @@ int plmc_factorize_sm_ex_f32(const float *X, int n, int d, int nmix, const float
                              const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                              int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE_SM(nmix, d, means);
-  const plmc::AssembleJob job{0, n, d, X, scales, weights, noise, nmix, means};
+  const plmc::AssembleJob job{plmc::CovTable::sm(d, nmix, scales, means, weights), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
 }
 int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
@@ -1487,8 +1485,8 @@ int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const doub
                              int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
   (void)eig_lo;
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE_SM(nmix, d, means);
-  const plmc::AssembleJob job{0, n, d, X, scales, weights, noise, nmix, means};
+  const plmc::AssembleJob job{plmc::CovTable::sm(d, nmix, scales, means, weights), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
 // The same for a periodic kernel (plmc_assemble_per_*): the job carries the lengthscales and the periods
@@ -1496,8 +1494,8 @@ int plmc_factorize_per_ex_f32(const float *X, int n, int d, const float *ell, co
                               float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
                               int with_inverse, int q, const float *eig_lo, void *stream) {
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE_PER(d, period);
-  const plmc::AssembleJob job{0, n, d, X, ell, oscale, noise, 1, period, true};
+  const plmc::AssembleJob job{plmc::CovTable::per(d, ell, period, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
 }
 int plmc_factorize_per_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
@@ -1505,8 +1503,8 @@ int plmc_factorize_per_ex_f64(const double *X, int n, int d, const double *ell, 
                               int with_inverse, int q, const double *eig_lo, void *stream) {
   (void)eig_lo;
   PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  PLMC_REQUIRE_PER(d, period);
-  const plmc::AssembleJob job{0, n, d, X, ell, oscale, noise, 1, period, true};
+  const plmc::AssembleJob job{plmc::CovTable::per(d, ell, period, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,

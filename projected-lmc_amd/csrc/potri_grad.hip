@@ -140,6 +140,23 @@ __device__ __forceinline__ void kinv_tile_epilogue(const Acc<T> &acc, T *smem, c
 #undef PLMC_KINV_KEEP
 }
 
+// The part the 256-thread kernels share in front of their epilogue, as text (a function, even always inlined, changed the code of every
+// one of them): declares m, the tile (ib, jb) of latent `lat` that this workgroup owns, `smem`, and that tile of K^-1 = W^T W in `acc`.
+// Longest tiles first: jb ascending outermost, latent fastest.  A (jb, ib, lat) grid ran the long tiles of the last latent
+// at the end of the launch: 112 vs 120 TF at n = 8192, q = 8, 97 vs 118 TF at q = 1, 77 vs 104 TF at n = 4096 (the same
+// launch with every tile reading one panel pair ran no faster, so operand locality is not what limits it; an XCD-dealt
+// super-tile order was level with the grid).
+#define PLMC_KINV_TILE_PRODUCT                                                                                                                 \
+  const int m = (int)(n_pad / NB);                                                                                                             \
+  const int lat = (int)blockIdx.x % nlat;                                                                                                      \
+  int ib, jb;                                                                                                                                  \
+  tri_decode((int)blockIdx.x / nlat, ib, jb);                                                                                                  \
+  __shared__ __align__(16) T smem[tile_smem_elems<T>()];                                                                                       \
+  const T *Wl = W + (int64_t)lat * strideW + (int64_t)jb * NB * ldw;                                                                           \
+  Acc<T> acc;                                                                                                                                  \
+  acc.zero();                                                                                                                                  \
+  tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem)
+
 // SPLINE (general epilogue only): the product-form spline kernel gets its own instantiation, so that its extra live
 // values do not raise the register pressure (and the scratch) of the stationary kernels' code.
 template <typename T, int DCAP, bool SPLINE = false>
@@ -149,19 +166,7 @@ __global__ __launch_bounds__(NTHREADS, (KG_MIN_WAVES<T, DCAP>)) void k_kinv_grad
                                                          const T *__restrict__ ell, const T *__restrict__ oscale,
                                                          T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag,
                                                          double *__restrict__ partials, int nlat) {
-  const int m = (int)(n_pad / NB);
-  // longest tiles first: jb ascending outermost, latent fastest.  A (jb, ib, lat) grid ran the long tiles of the last latent
-  // at the end of the launch: 112 vs 120 TF at n = 8192, q = 8, 97 vs 118 TF at q = 1, 77 vs 104 TF at n = 4096 (the same
-  // launch with every tile reading one panel pair ran no faster, so operand locality is not what limits it; an XCD-dealt
-  // super-tile order was level with the grid).
-  const int lat = (int)blockIdx.x % nlat;
-  int ib, jb;
-  tri_decode((int)blockIdx.x / nlat, ib, jb);
-  __shared__ __align__(16) T smem[tile_smem_elems<T>()];
-  const T *Wl = W + (int64_t)lat * strideW + (int64_t)jb * NB * ldw;
-  Acc<T> acc;
-  acc.zero();
-  tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem);
+  PLMC_KINV_TILE_PRODUCT;
   // the epilogue body is textually included, not called: as an (always inlined) function it cost k_kinv_grad<float, 8>, which
   // sits at exactly 128 registers, 24 bytes of scratch per lane
   const int tid = threadIdx.x;
@@ -170,6 +175,49 @@ __global__ __launch_bounds__(NTHREADS, (KG_MIN_WAVES<T, DCAP>)) void k_kinv_grad
 #include "kinv_epilogue.inc"
 #undef PLMC_KINV_KEEP
 }
+
+// The part the split-engine kernels share in front of their epilogue, as text (see PLMC_KINV_TILE_PRODUCT): declares `lds`, m, the macro
+// tile's two products combined in `acc0`, and the tile (ib, jb) of latent `lat` that this `half` (threadIdx.x >> 8) of the workgroup owns;
+// returns from a workgroup without a macro tile.
+// Latent-major: the ~256 resident workgroups are consecutive macro tiles of ONE matrix (a few block columns jb, all their
+// ibm): 16 + 16 operand strips instead of one B and 32 A strips per XCD and latent -- the strips are shared across the XCDs
+// through the Infinity Cache (step 18.5 -> 18.1 ms at q = 8 against latent fastest, the fp32 kernel's order)
+// Tile order: XCD-dealt super-blocks of 4 macro rows x 8 block columns (= the 32 workgroups an XCD holds; workgroup w lands on
+// XCD w % 8), longest K range first, latent by latent.  With the K range walked from its END (every range ends at row n) the
+// 32 tiles of a block read their 4 A strips and 8 B strips in lockstep through one L2, and the blocks in flight on the eight
+// XCDs belong to one or two matrices (Infinity Cache).  PMC, q = 8: 12.7 GB fetched per launch; the plain orders (latent
+// fastest / latent by latent, forward walk) 14.7 / 26.4 GB at 5.1 / 4.7 ms against 4.7 ms here.
+// Planes taken over from a sweep (ws_stride > 1): the per-latent stride of that scratch is the one the sweep recorded behind
+// its scheme tag -- plmc_vd_blocks_for blocks, or plmc_vd_blocks_keep when the sweep kept its planes (with_inverse | 4).  They must be
+// of THIS scheme -- a sweep without eig_lo followed by a K^-1 call with it (or a changed PLMC_SPLIT in between) would read
+// three-plane rows as two-plane rows; the scale poisons the result instead.
+#define PLMC_KINV_BF3_TILE_PRODUCT                                                                                                             \
+  constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float); \
+  __shared__ __align__(16) unsigned char lds[LDS_BYTES];                                                                                       \
+  const int m = (int)(n_pad / NB);                                                                                                             \
+  const int SJ = (m + 7) / 8, NSB = SJ * (SJ + 1) / 2;                                                                                         \
+  const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;                                                                                        \
+  const int gb = xcd + 8 * (slot >> 5), in = slot & 31;                                                                                        \
+  if (gb >= nlat * NSB) return;                                                                                                                \
+  const int lat = gb / NSB;                                                                                                                    \
+  int sa, sj;                                                                                                                                  \
+  tri_decode(gb - lat * NSB, sa, sj);                                                                                                          \
+  const int ibm = 2 * (4 * sa + (in >> 3)), jb = 8 * sj + (in & 7);                                                                            \
+  if (jb >= m || ibm > jb) return;                                                                                                             \
+  Acc<float> acc0, acc1;                                                                                                                       \
+  acc0.zero();                                                                                                                                 \
+  acc1.zero();                                                                                                                                 \
+  if (ws_stride > 1) {                                                                                                                         \
+    ws_stride = (int64_t)wscale[VD_W_TAG + 1] * NB * NB;                                                                                       \
+    wp_lat_stride = 2 * ws_stride;                                                                                                             \
+  }                                                                                                                                            \
+  const unsigned short *Pl = Wp + (int64_t)lat * wp_lat_stride + b3_index<S>((int64_t)jb * NB, 0, 0, n_pad);                                   \
+  b3_mainloop<S, 2, 0, B3NoPre, true>(acc0, acc1, Pl + (int64_t)ibm * NB * 8, n_pad, Pl + (int64_t)jb * NB * 8, n_pad, (int)(n_pad - (int64_t)jb * NB), lds); \
+  float ws = wscale[(int64_t)lat * ws_stride];                                                                                                 \
+  if (ws_stride > 1 && wscale[(int64_t)lat * ws_stride + VD_W_TAG] != (float)S::NPL) ws = __builtin_nanf("");                                  \
+  b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));                                                                                                 \
+  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);                                                                      \
+  const int ib = ibm + half
 
 // The same on the 16-bit matrix cores (fp32 only; bf3_engine.hpp): a workgroup of 512 threads takes the macro tile
 // (ib, ib + 1) x jb of K^-1 = W^T W from the k8-ordered planes of W (`Wp`, n_pad columns per plane row, `wp_lat_stride` elements
@@ -182,171 +230,94 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
                                                             int64_t ldk, int64_t strideK, float *kinv_diag, double *__restrict__ partials, int nlat,
                                                             const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
                                                             int64_t wp_lat_stride, int64_t ws_stride) {
-  constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float);
-  __shared__ __align__(16) unsigned char lds[LDS_BYTES];
-  const int m = (int)(n_pad / NB);
-  // latent-major: the ~256 resident workgroups are consecutive macro tiles of ONE matrix (a few block columns jb, all their
-  // ibm): 16 + 16 operand strips instead of one B and 32 A strips per XCD and latent -- the strips are shared across the XCDs
-  // through the Infinity Cache (step 18.5 -> 18.1 ms at q = 8 against latent fastest, the fp32 kernel's order)
-  // Tile order: XCD-dealt super-blocks of 4 macro rows x 8 block columns (= the 32 workgroups an XCD holds; workgroup w lands on
-  // XCD w % 8), longest K range first, latent by latent.  With the K range walked from its END (every range ends at row n) the
-  // 32 tiles of a block read their 4 A strips and 8 B strips in lockstep through one L2, and the blocks in flight on the eight
-  // XCDs belong to one or two matrices (Infinity Cache).  PMC, q = 8: 12.7 GB fetched per launch; the plain orders (latent
-  // fastest / latent by latent, forward walk) 14.7 / 26.4 GB at 5.1 / 4.7 ms against 4.7 ms here.
-  const int SJ = (m + 7) / 8, NSB = SJ * (SJ + 1) / 2;
-  const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
-  const int gb = xcd + 8 * (slot >> 5), in = slot & 31;
-  if (gb >= nlat * NSB) return;
-  const int lat = gb / NSB;
-  int sa, sj;
-  tri_decode(gb - lat * NSB, sa, sj);
-  const int ibm = 2 * (4 * sa + (in >> 3)), jb = 8 * sj + (in & 7);
-  if (jb >= m || ibm > jb) return;
-  Acc<float> acc0, acc1;
-  acc0.zero();
-  acc1.zero();
-  // planes taken over from a sweep (ws_stride > 1): the per-latent stride of that scratch is the one the sweep recorded behind
-  // its scheme tag -- plmc_vd_blocks_for blocks, or plmc_vd_blocks_keep when the sweep kept its planes (with_inverse | 4)
-  if (ws_stride > 1) {
-    ws_stride = (int64_t)wscale[VD_W_TAG + 1] * NB * NB;
-    wp_lat_stride = 2 * ws_stride;
-  }
-  const unsigned short *Pl = Wp + (int64_t)lat * wp_lat_stride + b3_index<S>((int64_t)jb * NB, 0, 0, n_pad);
-  b3_mainloop<S, 2, 0, B3NoPre, true>(acc0, acc1, Pl + (int64_t)ibm * NB * 8, n_pad, Pl + (int64_t)jb * NB * 8, n_pad, (int)(n_pad - (int64_t)jb * NB), lds);
-  float ws = wscale[(int64_t)lat * ws_stride];
-  // planes taken over from a sweep (ws_stride > 1): they must be of THIS scheme -- a sweep without eig_lo followed by a K^-1 call
-  // with it (or a changed PLMC_SPLIT in between) would read three-plane rows as two-plane rows; poison the result instead
-  if (ws_stride > 1 && wscale[(int64_t)lat * ws_stride + VD_W_TAG] != (float)S::NPL) ws = __builtin_nanf("");
-  b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));
-  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
-  const int ib = ibm + half;
+  PLMC_KINV_BF3_TILE_PRODUCT;
   kinv_tile_epilogue<float, DCAP, SPLINE>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind,
                                           ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials);
 }
 
 
-// ---- additive kernels (sum of `ncomp` <= MAX_COMP scaled stationary ARD kernels): the two kernels above with the epilogue of
-// kinv_epilogue_add.inc.  One instantiation per element type / split scheme: the input dimension and the component count are run-time
-// loop bounds there.  The single kernel (ncomp = 1) never comes here (kinv_grad_impl).
-// SMDC != 0: the same kernels for a spectral-mixture kernel of up to SMDC input dimensions (kinv_epilogue_sm.inc): ncomp = its components,
-// ell = its scales, oscale = its weights, `means` its means; `kind` is not looked at.
-// PERDC != 0: the same kernels for a periodic kernel of up to PERDC input dimensions (kinv_epilogue_per.inc): ell = its lengthscales,
-// `means` its periods, oscale (q) or null; `kind` and ncomp (1) are not looked at.
-template <typename T, int SMDC, int PERDC = 0>
+// ---- the table families: the two kernels above with the epilogue of their family F.
+// COV_ADD (sum of `ncomp` <= MAX_COMP scaled stationary ARD kernels, kinv_epilogue_add.inc): one instantiation per element type / split
+// scheme, DC = 0 -- the input dimension and the component count are run-time loop bounds there.  The single kernel (ncomp = 1) never
+// comes here (kinv_grad_impl).
+// COV_SM: a spectral-mixture kernel of up to DC input dimensions (kinv_epilogue_sm.inc): ncomp = its components, ell = its scales,
+// oscale = its weights, `means` its means; `kind` is not looked at.
+// COV_PER: a periodic kernel of up to DC input dimensions (kinv_epilogue_per.inc): ell = its lengthscales, `means` its periods, oscale (q)
+// or null; `kind` and ncomp (1) are not looked at.
+template <typename T, CovFamily F, int DC>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                        const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                        int64_t strideK, T *kinv_diag, double *__restrict__ partials, const T *__restrict__ means) {
   if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
-  if constexpr (PERDC != 0) {
-    constexpr int DC = PERDC;
-#include "kinv_epilogue_per.inc"
-  } else if constexpr (SMDC == 0) {
-#include "kinv_epilogue_add.inc"
-  } else {
-    constexpr int DC = SMDC;
-#include "kinv_epilogue_sm.inc"
-  }
+#include "kinv_epilogue_table.inc"
 }
 
-template <typename T, int SMDC = 0, int PERDC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (SMDC > 0 || PERDC > 1) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+template <typename T, CovFamily F, int DC = 0>
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
                                                                 const T *__restrict__ means) {
-  const int m = (int)(n_pad / NB);
-  const int lat = (int)blockIdx.x % nlat;              // tile order of k_kinv_grad
-  int ib, jb;
-  tri_decode((int)blockIdx.x / nlat, ib, jb);
-  __shared__ __align__(16) T smem[tile_smem_elems<T>()];
-  const T *Wl = W + (int64_t)lat * strideW + (int64_t)jb * NB * ldw;
-  Acc<T> acc;
-  acc.zero();
-  tile_mainloop<T, false, true>(acc, Wl + (int64_t)ib * NB, ldw, Wl + (int64_t)jb * NB, ldw, (int)(n_pad - (int64_t)jb * NB), smem);
+  PLMC_KINV_TILE_PRODUCT;
   const int tid = threadIdx.x;
   constexpr bool live = true;
-  if constexpr (PERDC != 0) {
-    constexpr int DC = PERDC;
-#include "kinv_epilogue_per.inc"
-  } else if constexpr (SMDC == 0) {
-#include "kinv_epilogue_add.inc"
-  } else {
-    constexpr int DC = SMDC;
-#include "kinv_epilogue_sm.inc"
-  }
+#include "kinv_epilogue_table.inc"
 }
 
-template <class S, int SMDC = 0, int PERDC = 0>
+template <class S, CovFamily F, int DC = 0>
 __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int ncomp, int64_t n_pad, const float *__restrict__ alpha,
                                                                 const float *__restrict__ X, int n, int d, const float *__restrict__ ell,
                                                                 const float *__restrict__ oscale, float *Kinv, int64_t ldk, int64_t strideK,
                                                                 float *kinv_diag, double *__restrict__ partials, int nlat,
                                                                 const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
                                                                 int64_t wp_lat_stride, int64_t ws_stride, const float *__restrict__ means) {
-  constexpr int LDS_BYTES = b3_lds_bytes<S>() > 2 * tile_smem_elems<float>() * (int)sizeof(float) ? b3_lds_bytes<S>() : 2 * tile_smem_elems<float>() * (int)sizeof(float);
-  __shared__ __align__(16) unsigned char lds[LDS_BYTES];
-  const int m = (int)(n_pad / NB);
-  // tile order, operand planes and scales: exactly k_kinv_grad_bf3 (see there)
-  const int SJ = (m + 7) / 8, NSB = SJ * (SJ + 1) / 2;
-  const int w = blockIdx.x, xcd = w & 7, slot = w >> 3;
-  const int gb = xcd + 8 * (slot >> 5), in = slot & 31;
-  if (gb >= nlat * NSB) return;
-  const int lat = gb / NSB;
-  int sa, sj;
-  tri_decode(gb - lat * NSB, sa, sj);
-  const int ibm = 2 * (4 * sa + (in >> 3)), jb = 8 * sj + (in & 7);
-  if (jb >= m || ibm > jb) return;
-  Acc<float> acc0, acc1;
-  acc0.zero();
-  acc1.zero();
-  if (ws_stride > 1) {
-    ws_stride = (int64_t)wscale[VD_W_TAG + 1] * NB * NB;
-    wp_lat_stride = 2 * ws_stride;
-  }
-  const unsigned short *Pl = Wp + (int64_t)lat * wp_lat_stride + b3_index<S>((int64_t)jb * NB, 0, 0, n_pad);
-  b3_mainloop<S, 2, 0, B3NoPre, true>(acc0, acc1, Pl + (int64_t)ibm * NB * 8, n_pad, Pl + (int64_t)jb * NB * 8, n_pad, (int)(n_pad - (int64_t)jb * NB), lds);
-  float ws = wscale[(int64_t)lat * ws_stride];
-  if (ws_stride > 1 && wscale[(int64_t)lat * ws_stride + VD_W_TAG] != (float)S::NPL) ws = __builtin_nanf("");
-  b3_combine<S>(acc0, acc1, 1.0f / (ws * ws));
-  const int half = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
-  const int ib = ibm + half;
-  kinv_tile_epilogue_add<float, SMDC, PERDC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
-                                             ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
+  PLMC_KINV_BF3_TILE_PRODUCT;
+  kinv_tile_epilogue_add<float, F, DC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
+                                       ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
 }
 
-// grad[lat][k] = 1/2 * sum over upper tiles of partials, with the 1/ell_k factor for lengthscales.
-// grid (q), 1024 threads = 30 groups of GP = 34 slots; every group walks its tiles with 4 independent
+// The tile walk of the reductions below, as text (see PLMC_KINV_TILE_PRODUCT): declares `lat` = blockIdx.x and leaves in red[grp * GP + slot]
+// the sum of that slot of the partial-sum row at `row0` (in doubles) over group grp's share of the latent's upper tiles, the tiles `tstride`
+// doubles apart.  1024 threads = 30 groups of GP = 34 slots; every group walks its tiles with 4 independent
 // accumulators (the loads are latency-bound); fixed summation order throughout.
 constexpr int RED_NT = 1024;
+#define PLMC_REDUCE_TILES(tstride, row0)                                                      \
+  __shared__ double red[RED_NT];                                                              \
+  const int lat = blockIdx.x;                                                                 \
+  const int ntile = m * m;                                                                    \
+  const int slot = threadIdx.x % GP;                                                          \
+  const int grp = threadIdx.x / GP;                                                           \
+  constexpr int NG = RED_NT / GP;                                                             \
+  double s[4] = {0.0, 0.0, 0.0, 0.0};                                                         \
+  if (grp < NG) {                                                                             \
+    const double *base = partials + (int64_t)lat * ntile * (tstride) + (row0) + slot;         \
+    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {                                            \
+      _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                         \
+        const int t = t0 + u * NG;                                                            \
+        if (t < ntile) {                                                                      \
+          const int ib = t / m, jb = t - ib * m;                                              \
+          if (jb >= ib) s[u] += base[(int64_t)t * (tstride)];                                 \
+        }                                                                                     \
+      }                                                                                       \
+    }                                                                                         \
+  }                                                                                           \
+  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);                                           \
+  __syncthreads()
+// ... and the total of slot threadIdx.x < GP over the groups, in their order
+__device__ __forceinline__ double reduce_slot_total(const double *red) {
+  double tot = 0.0;
+  for (int gq = 0; gq < RED_NT / GP; ++gq) tot += red[gq * GP + threadIdx.x];
+  return tot;
+}
+
+// grad[lat][k] = 1/2 * sum over upper tiles of partials, with the 1/ell_k factor for lengthscales.  grid (q).
 template <typename T>
 __global__ __launch_bounds__(RED_NT) void k_reduce_grad(const double *__restrict__ partials, int m, int d,
                                                         const T *__restrict__ ell, double *__restrict__ grad) {
-  __shared__ double red[RED_NT];
-  const int lat = blockIdx.x;
-  const int ntile = m * m;
-  const int slot = threadIdx.x % GP;
-  const int grp = threadIdx.x / GP;
-  constexpr int NG = RED_NT / GP;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (grp < NG) {
-    const double *base = partials + (int64_t)lat * ntile * GP + slot;
-    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u * NG;
-        if (t < ntile) {
-          const int ib = t / m, jb = t - ib * m;
-          if (jb >= ib) s[u] += base[(int64_t)t * GP];
-        }
-      }
-    }
-  }
-  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
+  PLMC_REDUCE_TILES(GP, 0);
   if (threadIdx.x < GP) {
-    double tot = 0.0;
-    for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
+    const double tot = reduce_slot_total(red);
     const int k = threadIdx.x;
     if (k < d) grad[(int64_t)lat * (d + 2) + k] = 0.5 * tot / (double)ell[(int64_t)lat * d + k];
     else if (k == MAX_DIM) grad[(int64_t)lat * (d + 2) + d] = 0.5 * tot;
@@ -354,39 +325,18 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad(const double *__restrict
   }
 }
 
-// The reduction for the additive kernels: the tile's partials are `ncomp` rows of GP slots.  grid (q, ncomp), the thread layout and the
-// summation order of k_reduce_grad.  grad[lat]: [ d/d ell (ncomp x d) | d/d noise | d/d oscale (ncomp) ] -- for one component the
+// The reduction for the additive kernels: the tile's partials are `ncomp` rows of GP slots.  grid (q, ncomp).
+// grad[lat]: [ d/d ell (ncomp x d) | d/d noise | d/d oscale (ncomp) ] -- for one component the
 // layout of k_reduce_grad.  A dimension outside its component (ell = +inf) gets 0.5 * 0 / inf = 0.
 // SM: the rows of kinv_epilogue_sm.inc, grad[lat]: [ d/d scales (ncomp x d) | d/d means (ncomp x d) | d/d noise | d/d weights (ncomp) ]
 template <typename T, bool SM = false>
 __global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__restrict__ partials, int m, int d, int ncomp,
                                                             const T *__restrict__ ell, double *__restrict__ grad) {
-  __shared__ double red[RED_NT];
-  const int lat = blockIdx.x, g = blockIdx.y;
-  const int ntile = m * m;
-  const int slot = threadIdx.x % GP;
-  const int grp = threadIdx.x / GP;
-  constexpr int NG = RED_NT / GP;
+  const int g = blockIdx.y;
   const int64_t tstride = (int64_t)ncomp * GP;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (grp < NG) {
-    const double *base = partials + (int64_t)lat * ntile * tstride + (int64_t)g * GP + slot;
-    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u * NG;
-        if (t < ntile) {
-          const int ib = t / m, jb = t - ib * m;
-          if (jb >= ib) s[u] += base[(int64_t)t * tstride];
-        }
-      }
-    }
-  }
-  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
+  PLMC_REDUCE_TILES(tstride, (int64_t)g * GP);
   if (threadIdx.x < GP) {
-    double tot = 0.0;
-    for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
+    const double tot = reduce_slot_total(red);
     const int k = threadIdx.x;
     if constexpr (SM) {
       double *gl = grad + (int64_t)lat * (ncomp * (2 * d + 1) + 1);
@@ -403,36 +353,14 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_add(const double *__rest
   }
 }
 
-// The reduction for the periodic kernel: one row of GP slots per tile (kinv_epilogue_per.inc), the thread layout and the summation
-// order of k_reduce_grad.  grad[lat]: [ d/d ell (d) | d/d period (d) | d/d noise | d/d oscale ], with the factors the epilogue left out.
+// The reduction for the periodic kernel: one row of GP slots per tile (kinv_epilogue_per.inc).  grid (q).
+// grad[lat]: [ d/d ell (d) | d/d period (d) | d/d noise | d/d oscale ], with the factors the epilogue left out.
 template <typename T>
 __global__ __launch_bounds__(RED_NT) void k_reduce_grad_per(const double *__restrict__ partials, int m, int d, const T *__restrict__ ell,
                                                             const T *__restrict__ period, double *__restrict__ grad) {
-  __shared__ double red[RED_NT];
-  const int lat = blockIdx.x;
-  const int ntile = m * m;
-  const int slot = threadIdx.x % GP;
-  const int grp = threadIdx.x / GP;
-  constexpr int NG = RED_NT / GP;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  if (grp < NG) {
-    const double *base = partials + (int64_t)lat * ntile * GP + slot;
-    for (int t0 = grp; t0 < ntile; t0 += 4 * NG) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int t = t0 + u * NG;
-        if (t < ntile) {
-          const int ib = t / m, jb = t - ib * m;
-          if (jb >= ib) s[u] += base[(int64_t)t * GP];
-        }
-      }
-    }
-  }
-  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
+  PLMC_REDUCE_TILES(GP, 0);
   if (threadIdx.x < GP) {
-    double tot = 0.0;
-    for (int gq = 0; gq < NG; ++gq) tot += red[gq * GP + threadIdx.x];
+    const double tot = reduce_slot_total(red);
     const int k = threadIdx.x;
     double *gl = grad + (int64_t)lat * (2 * d + 2);
     if (k < d) {
@@ -475,16 +403,15 @@ __global__ void k_w_scale(const float *__restrict__ eig_lo, float *__restrict__ 
 }
 
 // S: split scheme of the W^T W products (void: MFMA of the element type); eig_lo: see potrf_impl.
+// `partials` is table.partials_rows() rows of GP slots per tile and `grad` as wide as the family's reduction kernel writes it.
 template <typename T, class S>
-int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n,
-                   int d, const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK,
-                   T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream, const float *Vd = nullptr, int64_t lda_vd = 0,
-                   int ncomp = 1, const T *means = nullptr, bool per = false) {
-  // ncomp > 1: additive kernel, ell (q, ncomp, d), oscale (q, ncomp), `partials` and `grad` ncomp times as wide (plmc_kinv_grad_add_vd_*)
-  // means: spectral mixture of ncomp components, ell = its scales, oscale = its weights (plmc_kinv_grad_sm_vd_*)
-  // per: periodic kernel, ell = its lengthscales, means = its periods (q, d), oscale (q) or null, ncomp = 1 (plmc_kinv_grad_per_vd_*)
-  PLMC_REQUIRE(!means || d <= SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()");
-  PLMC_REQUIRE(!per || (means && ncomp == 1 && d <= PER_MAX_DIM), "need 0 < d <= plmc_per_max_dim()");
+int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n, double *grad,
+                   T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream,
+                   const float *Vd = nullptr, int64_t lda_vd = 0) {
+  PLMC_REQUIRE_TABLE(table);
+  const CovFamily family = table.route();
+  const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
+  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second;
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -505,9 +432,10 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
-      PLMC_REQUIRE(!per, "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
-      PLMC_REQUIRE(!means, "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
-      char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * ncomp * GP * (int64_t)sizeof(double);
+      PLMC_REQUIRE(family != COV_PER && family != COV_SM,
+                   family == COV_PER ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                                     : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
+      char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * rows * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
       float *wsco = reinterpret_cast<float *>(pb + (int64_t)q * b3_elems<SplitB3>(n_pad, n_pad) * 2);
       hipLaunchKernelGGL((k_w_scale<S>), dim3(1), dim3(q < 64 ? 64 : ((q + 63) / 64) * 64), 0, st, eig_lo, wsco, q, (int)(n < n_pad));
@@ -523,50 +451,52 @@ int kinv_grad_impl(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t str
 #define PLMC_LAUNCH_KB(DC, SP) \
   hipLaunchKernelGGL((k_kinv_grad_bf3<S, DC, SP>), gridb, dim3(B3_NT), 0, st, kind, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, \
                      part, q, wp, wsc, wp_lat, ws_lat)
+#define PLMC_LAUNCH_TB(F, DC) \
+  hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, F, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
+                     kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)second)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-#define PLMC_LAUNCH_SB(DC) \
-  hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
-                     kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)means)
-    if (per)                                             // (d = 1 only: kinv_grad_f32_any)
-      hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, 0, 1>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK,
-                         kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)means);
-    else if (means) PLMC_LAUNCH_SB(1);                   // (d = 1 only: kinv_grad_f32_any)
-    else if (ncomp > 1) PLMC_LAUNCH_SB(0);
-#undef PLMC_LAUNCH_SB
-    else if (d <= 4) PLMC_LAUNCH_KB(4, false);
-    else if (d <= 8) PLMC_LAUNCH_KB(8, false);
-    else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KB(16, true); else PLMC_LAUNCH_KB(16, false); }
-    else { if (kind == K_SPLINE) PLMC_LAUNCH_KB(32, true); else PLMC_LAUNCH_KB(32, false); }
+    switch (family) {
+      case COV_PER: PLMC_LAUNCH_TB(COV_PER, 1); break;     // (d = 1 only: kinv_grad_f32_any)
+      case COV_SM: PLMC_LAUNCH_TB(COV_SM, 1); break;       // (d = 1 only: kinv_grad_f32_any)
+      case COV_ADD: PLMC_LAUNCH_TB(COV_ADD, 0); break;
+      case COV_PLAIN:
+        if (d <= 4) PLMC_LAUNCH_KB(4, false);
+        else if (d <= 8) PLMC_LAUNCH_KB(8, false);
+        else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KB(16, true); else PLMC_LAUNCH_KB(16, false); }
+        else { if (kind == K_SPLINE) PLMC_LAUNCH_KB(32, true); else PLMC_LAUNCH_KB(32, false); }
+    }
+#undef PLMC_LAUNCH_TB
 #undef PLMC_LAUNCH_KB
   } else {
     const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);          // longest tiles first (see the kernel)
 #define PLMC_LAUNCH_KG(DC, SP)                                                                                       \
   hipLaunchKernelGGL((k_kinv_grad<T, DC, SP>), grid, block, 0, st, kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, \
                      oscale, Kinv, ldk, strideK, kinv_diag, part, q)
+#define PLMC_LAUNCH_TG(F, DC) \
+  hipLaunchKernelGGL((k_kinv_grad_add<T, F, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
+                     strideK, kinv_diag, part, q, second)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-#define PLMC_LAUNCH_SG(DC) \
-  hipLaunchKernelGGL((k_kinv_grad_add<T, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
-                     strideK, kinv_diag, part, q, means)
-#define PLMC_LAUNCH_PG(DC) \
-  hipLaunchKernelGGL((k_kinv_grad_add<T, 0, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
-                     strideK, kinv_diag, part, q, means)
-    if (per) { if (d == 1) PLMC_LAUNCH_PG(1); else if (d <= 4) PLMC_LAUNCH_PG(4); else PLMC_LAUNCH_PG(8); }
-#undef PLMC_LAUNCH_PG
-    else if (means) { if (d == 1) PLMC_LAUNCH_SG(1); else if (d <= 4) PLMC_LAUNCH_SG(4); else PLMC_LAUNCH_SG(8); }
-    else if (ncomp > 1) PLMC_LAUNCH_SG(0);
-#undef PLMC_LAUNCH_SG
-    else if (d <= 4) PLMC_LAUNCH_KG(4, false);
-    else if (d <= 8) PLMC_LAUNCH_KG(8, false);
-    else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KG(16, true); else PLMC_LAUNCH_KG(16, false); }
-    else { if (kind == K_SPLINE) PLMC_LAUNCH_KG(32, true); else PLMC_LAUNCH_KG(32, false); }
+    switch (family) {
+      case COV_PER: if (d == 1) PLMC_LAUNCH_TG(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_PER, 4); else PLMC_LAUNCH_TG(COV_PER, 8); break;
+      case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
+      case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
+      case COV_PLAIN:
+        if (d <= 4) PLMC_LAUNCH_KG(4, false);
+        else if (d <= 8) PLMC_LAUNCH_KG(8, false);
+        else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_KG(16, true); else PLMC_LAUNCH_KG(16, false); }
+        else { if (kind == K_SPLINE) PLMC_LAUNCH_KG(32, true); else PLMC_LAUNCH_KG(32, false); }
+    }
+#undef PLMC_LAUNCH_TG
 #undef PLMC_LAUNCH_KG
   }
   {
-    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * ncomp * GP * sizeof(double) / 2);
-    if (per) hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, means, grad);
-    else if (means) hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
-    else if (ncomp > 1) hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad);
-    else hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
+    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
+    switch (family) {
+      case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+      case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+      case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
+    }
   }
   return launch_status(__func__);
 }
@@ -586,42 +516,51 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
   const int64_t m = n_pad / plmc::NB;
   return m * m * (int64_t)q * plmc::GP * (int64_t)sizeof(double);
 }
-static int kinv_grad_f32_any(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                             const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
-                             float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo,
-                             void *stream, const float *Vd = nullptr, int ncomp = 1, const float *means = nullptr, bool per = false) {
+// the fp32 call by the arithmetic of its products (PLMC_SPLIT); Vd: the scratch of the sweep that produced W, or null
+static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
+                             const float *X, int n, double *grad, float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
+                             const float *eig_lo, void *stream, const float *Vd = nullptr) {
   const int split = plmc::knobs().split;
   // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
   // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
-  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel (`per`, means = its
-  // periods) keeps d sines, cosine complements and 2 d sums live and follows the same rule.
-  if (split == 0 || (means && d > 1))
-    return plmc::kinv_grad_impl<float, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                             nullptr, stream, nullptr, 0, ncomp, means, per);
+  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel keeps d sines, cosine
+  // complements and 2 d sums live and follows the same rule.
+  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER) && table.d > 1))
+    return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
-    return plmc::kinv_grad_impl<float, plmc::SplitH2>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                      partials, q, eig_lo, stream, Vd, ldw, ncomp, means, per);
-  return plmc::kinv_grad_impl<float, plmc::SplitB3>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag,
-                                                    partials, q, nullptr, stream, Vd, ldw, ncomp, means, per);
+    return plmc::kinv_grad_impl<float, plmc::SplitH2>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo,
+                                                      stream, Vd, ldw);
+  return plmc::kinv_grad_impl<float, plmc::SplitB3>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr,
+                                                    stream, Vd, ldw);
 }
+static int kinv_grad_f64(const plmc::CovTable &table, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
+                         const double *X, int n, double *grad, double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
+                         void *stream) {
+  return plmc::kinv_grad_impl<double, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
+}
+// the entry points: the only place the covariance tables of this file are built from flat arguments
+using plmc::CovTable;
 int plmc_kinv_grad_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                        const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                        float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
                        void *stream) {
-  return kinv_grad_f32_any(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
+  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                           nullptr, stream);
 }
 int plmc_kinv_grad_ex_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                           const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                           float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
                           const float *eig_lo, void *stream) {
-  return kinv_grad_f32_any(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream);
+  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                           eig_lo, stream);
 }
 int plmc_kinv_grad_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                           const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
                           float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
                           const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd);
+  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                           eig_lo, stream, Vd);
 }
 int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                           const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
@@ -629,20 +568,15 @@ int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
                           const double *eig_lo, const double *Vd, void *stream) {
   (void)eig_lo;
   (void)Vd;
-  return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
-                                            strideK, kinv_diag, partials, q, nullptr, stream);
+  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
 }
 // additive kernels: plmc_kinv_grad_vd_* with a component table (include/plmc.h)
-#define PLMC_REQUIRE_ADD(kind, G)                                                                                     \
-  PLMC_REQUIRE(kind >= 0 && kind <= plmc::K_MATERN52, "additive kernels take the stationary kinds only (no spline kernel)"); \
-  PLMC_REQUIRE(G >= 1 && G <= plmc::MAX_COMP, "need 1 <= components <= plmc_max_components()")
 int plmc_kinv_grad_add_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                               const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, double *grad,
                               float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
                               const float *eig_lo, const float *Vd, void *stream) {
-  PLMC_REQUIRE_ADD(kind, ncomp);
-  return kinv_grad_f32_any(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd,
-                           ncomp);
+  return kinv_grad_f32_any(CovTable::add(kind, d, ncomp, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
+                           q, eig_lo, stream, Vd);
 }
 int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                               const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, double *grad,
@@ -650,11 +584,9 @@ int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t 
                               const double *eig_lo, const double *Vd, void *stream) {
   (void)eig_lo;
   (void)Vd;
-  PLMC_REQUIRE_ADD(kind, ncomp);
-  return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
-                                            strideK, kinv_diag, partials, q, nullptr, stream, nullptr, 0, ncomp);
+  return kinv_grad_f64(CovTable::add(kind, d, ncomp, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                       stream);
 }
-#undef PLMC_REQUIRE_ADD
 // spectral-mixture kernel: plmc_kinv_grad_vd_* with the table (scales, means, weights) (include/plmc.h)
 int64_t plmc_sm_grad_partials_bytes(int64_t n_pad, int q, int nmix, int elem_bytes) {
   (void)elem_bytes;                                   // one row of fp64 partial sums per tile and component, whatever the element type
@@ -663,18 +595,16 @@ int64_t plmc_sm_grad_partials_bytes(int64_t n_pad, int q, int nmix, int elem_byt
 int plmc_kinv_grad_sm_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
                              int nmix, const float *scales, const float *means, const float *weights, double *grad, float *Kinv, int64_t ldk,
                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  PLMC_REQUIRE_SM(nmix, d, means);
-  return kinv_grad_f32_any(0, W, n_pad, ldw, strideW, alpha, X, n, d, scales, weights, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream,
-                           Vd, nmix, means);
+  return kinv_grad_f32_any(CovTable::sm(d, nmix, scales, means, weights), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
+                           partials, q, eig_lo, stream, Vd);
 }
 int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
                              int nmix, const double *scales, const double *means, const double *weights, double *grad, double *Kinv, int64_t ldk,
                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
   (void)eig_lo;
   (void)Vd;
-  PLMC_REQUIRE_SM(nmix, d, means);
-  return plmc::kinv_grad_impl<double, void>(0, W, n_pad, ldw, strideW, alpha, X, n, d, scales, weights, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                            nullptr, stream, nullptr, 0, nmix, means);
+  return kinv_grad_f64(CovTable::sm(d, nmix, scales, means, weights), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
+                       q, stream);
 }
 // periodic kernel: plmc_kinv_grad_vd_* with the table (lengthscales, periods, output scale) (include/plmc.h)
 int64_t plmc_per_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
@@ -684,32 +614,28 @@ int64_t plmc_per_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
 int plmc_kinv_grad_per_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
                               const float *ell, const float *period, const float *oscale, double *grad, float *Kinv, int64_t ldk,
                               int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  PLMC_REQUIRE_PER(d, period);
-  return kinv_grad_f32_any(0, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream,
-                           Vd, 1, period, true);
+  return kinv_grad_f32_any(CovTable::per(d, ell, period, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                           eig_lo, stream, Vd);
 }
 int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
                               const double *ell, const double *period, const double *oscale, double *grad, double *Kinv, int64_t ldk,
                               int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
   (void)eig_lo;
   (void)Vd;
-  PLMC_REQUIRE_PER(d, period);
-  return plmc::kinv_grad_impl<double, void>(0, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                                            nullptr, stream, nullptr, 0, 1, period, true);
+  return kinv_grad_f64(CovTable::per(d, ell, period, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                       stream);
 }
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
                        void *stream) {
-  return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
-                                            strideK, kinv_diag, partials, q, nullptr, stream);
+  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
 }
 int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                           const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                           double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
                           const double *eig_lo, void *stream) {
   (void)eig_lo;
-  return plmc::kinv_grad_impl<double, void>(kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, grad, Kinv, ldk,
-                                            strideK, kinv_diag, partials, q, nullptr, stream);
+  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
 }
 }

@@ -214,12 +214,7 @@ def refuse_periodic(kernel, model):
 
 def refuse_sm(kernel, model):
     """The spectral-mixture kernel runs on the batched exact engine only: name the model that cannot take it."""
-    k = kernel
-    while k is not None and not isinstance(k, SpectralMixtureKernel):
-        k = getattr(k, "base_kernel", None)
-    if k is not None or (isinstance(kernel, type) and issubclass(kernel, SpectralMixtureKernel)):
-        raise NotImplementedError("%s does not take a SpectralMixtureKernel: it is served by the batched exact engine only "
-                                  "(ExactGPModel without inducing points, ProjectedGPModel)" % model)
+    _refuse(SpectralMixtureKernel, "SpectralMixtureKernel", kernel, model)
 
 
 def prior_diagonal(kind, x, oscale, q):

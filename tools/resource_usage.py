@@ -35,7 +35,7 @@ def analyse(src):
             cur[m.group(1).strip()] = int(m.group(2))
     names = demangle([r["name"] for r in rows])
     for r, nm in zip(rows, names):
-        r["pretty"] = re.sub(r"^void plmc::", "", nm).split("(")[0]
+        r["pretty"] = re.sub(r"^void plmc::", "", nm[:nm.index(">(") + 1] if ">(" in nm else nm.split("(")[0])   # (an enum argument prints as a cast)
     return rows
 
 
