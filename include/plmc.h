@@ -323,6 +323,13 @@ int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
  *   with d / d ell[g][k] = 0 exactly where ell[g][k] = +inf.  `partials`: the scratch of plmc_kinv_grad_vd_* for q * ncomp latents
  *   (plmc_grad_partials_bytes(n_pad, q * ncomp), resp. plmc_grad_scratch_bytes_for(n_pad, q * ncomp, elem_bytes) where the planes of W
  *   are not taken from Vd): one row of partial sums per tile AND component.
+ * plmc_kernel_vjp_add_* is plmc_kernel_vjp_* (below) for a component table: the pull-back of the adjoint G of a dense block
+ *   K_i[a][b] = sum_g oscale[i][g] k(|(x1_a - x2_b) / ell[i][g][:]|) -- K_ZZ and K_ZX of the inducing-point (SGPR) and variational models.
+ *   gX1 [q][n1][d] sums over the components; gEll [q][n1][ncomp][d] and gOs [q][n1][ncomp] are row partials per component (the caller
+ *   sums over rows).  gEll is exactly 0 where ell = +inf, gX1 exactly 0 on a dimension no component uses; a component whose own scaled
+ *   distance is 0 follows the convention of the plain kernel (Matern-1/2: nothing to gX1 / gEll, its value to gOs), also where the two
+ *   points differ outside its group.  G is read once for d <= 16; for d > 16 the components are split over passes (fp32: two per pass,
+ *   fp64: one).  The spline kind and ncomp > plmc_max_components() are argument errors.
  */
 int plmc_max_components(void);                /* most components of an additive kernel (4) */
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
@@ -349,6 +356,12 @@ int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t 
                               const double *alpha, const double *X, int n, int d, int ncomp, const double *ell,
                               const double *oscale, double *grad, double *Kinv, int64_t ldk, int64_t strideK,
                               double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+int plmc_kernel_vjp_add_f32(int kind, const float *X1, int n1, const float *X2, int n2, int d, int ncomp,
+                            const float *ell, const float *oscale, const float *G, int64_t ldg,
+                            int64_t strideG, double *gX1, double *gEll, double *gOs, int q, void *stream);
+int plmc_kernel_vjp_add_f64(int kind, const double *X1, int n1, const double *X2, int n2, int d, int ncomp,
+                            const double *ell, const double *oscale, const double *G, int64_t ldg,
+                            int64_t strideG, double *gX1, double *gEll, double *gOs, int q, void *stream);
 
 /*
  * Spectral-mixture kernel [gpytorch-knowledge: SpectralMixtureKernel; the reference's tidal study, realdata_experiments.py:130-140, runs

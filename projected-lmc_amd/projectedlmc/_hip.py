@@ -55,6 +55,7 @@ _TYPED = {
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "plmc_kernel_vjp": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_kernel_vjp_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P, _P, _P, _I, _P],
     "plmc_qr_small": [_P, _I, _I, _L, _P, _L, _P, _L, _P],
     "plmc_comm_allreduce_sum": [_P, _L, _P],
     "plmc_posterior_moments": [_P, _L, _L, _L, _I, _P, _P, _I, _P],

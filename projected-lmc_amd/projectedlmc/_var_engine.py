@@ -15,7 +15,7 @@ tile engine (`plmc_gemm_tn` through `_dense.gemm_tn`; every product is written i
 import torch
 
 from . import _hip
-from ._engine import Workspace, _contig
+from ._engine import Workspace, _check_kernel_shape, _contig, _kernel_call
 from ._pivot import PivotCheck
 
 _ws = {}
@@ -34,22 +34,24 @@ def _workspace(m, q, n, dtype, device, with_inverse):
 def _factorize_kzz(kind, Z, ell, oscale, jitter, ws, rhs=None, X=None, eager=False):
     """Assemble [K_ZZ + jitter I | rhs | K_ZX] into ws and run the sweep; returns its pivot check (read at once if `eager`).
     rhs: (q, nrhs, m) right-hand-side columns or None; X: (n, d) for cross columns K(Z, X) behind them, or None.  The number of
-    augmented columns and the inverse factor are the workspace's (ws.naug, ws.with_inverse)."""
+    augmented columns and the inverse factor are the workspace's (ws.naug, ws.with_inverse).
+    ell (q, d), oscale (q) | None, or the component table of an additive kernel, ell (q, G, d), oscale (q, G) | None (_engine.py)."""
     L = _hip.lib()
+    _check_kernel_shape(L, ell)
     dt, dev = ws.dtype, ws.device
     st = _hip.stream_ptr(dev)
     k = _hip.KIND[kind]
     m, d = Z.shape
     q = ws.q
     jit = torch.full((q,), float(jitter), dtype=dt, device=dev)
-    L.call("plmc_assemble", dt, k, _hip.ptr(Z), m, d, _hip.ptr(ell), _hip.ptr(oscale), _hip.ptr(jit),
-           _hip.ptr(ws.A), ws.lda, ws.strideA, q, st)
+    _kernel_call(L, "plmc_assemble", dt, (k, _hip.ptr(Z), m, d), ell, (_hip.ptr(oscale), _hip.ptr(jit),
+                 _hip.ptr(ws.A), ws.lda, ws.strideA, q, st))
     if ws.naug_pad > 0:
         L.call("plmc_write_rhs", dt, _hip.ptr(rhs), 0 if rhs is None else rhs.shape[1], m, _hip.ptr(ws.A), ws.lda, ws.strideA, 0,
                ws.naug_pad, q, st)
     if X is not None:
-        L.call("plmc_assemble_cross", dt, k, _hip.ptr(Z), m, _hip.ptr(X), X.shape[0], d, _hip.ptr(ell), _hip.ptr(oscale),
-               _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad, ws.n_pad, q, st)
+        _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(Z), m, _hip.ptr(X), X.shape[0], d), ell, (_hip.ptr(oscale),
+                     _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad, ws.n_pad, q, st))
     # eig_lo = the jitter: lambda_min(K_ZZ + jitter I) >= jitter (bound for the fp16 split of the bulk fp32 products)
     L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
            _hip.ptr(ws.logdet), _hip.ptr(ws.info), int(ws.with_inverse), q, _hip.ptr(jit), st)
@@ -64,25 +66,36 @@ def _raise_if_not_pd(check, pivots=True):
 
 
 def kernel_vjp(kind, X1, X2, ell, oscale, G):
-    """(gX1 (n1,d) summed over latents, gEll (q,d), gOs (q)) in fp64 for K_i = os_i k(X1, X2; ell_i)."""
+    """(gX1 (n1,d) summed over latents, gEll (q,d), gOs (q)) in fp64 for K_i = os_i k(X1, X2; ell_i); for the component table of an
+    additive kernel, ell (q,G,d) and oscale (q,G) | None, gEll (q,G,d) and gOs (q,G) (plmc_kernel_vjp_add)."""
     L = _hip.lib()
     dt, dev = G.dtype, G.device
     q, n1, n2 = G.shape
     d = X1.shape[1]
     G = G.contiguous()
+    per_latent = tuple(ell.shape[1:])                       # (d) | (G, d)
     gX = torch.empty(q, n1, d, dtype=torch.float64, device=dev)
-    gE = torch.empty(q, n1, d, dtype=torch.float64, device=dev)
-    gO = torch.empty(q, n1, dtype=torch.float64, device=dev)
-    L.call("plmc_kernel_vjp", dt, _hip.KIND[kind], _hip.ptr(X1), n1, _hip.ptr(X2), n2, d, _hip.ptr(ell),
-           _hip.ptr(oscale), _hip.ptr(G), n2, n1 * n2, _hip.ptr(gX), _hip.ptr(gE), _hip.ptr(gO), q,
-           _hip.stream_ptr(dev))
+    gE = torch.empty((q, n1) + per_latent, dtype=torch.float64, device=dev)
+    gO = torch.empty((q, n1) + per_latent[:-1], dtype=torch.float64, device=dev)
+    _kernel_call(L, "plmc_kernel_vjp", dt, (_hip.KIND[kind], _hip.ptr(X1), n1, _hip.ptr(X2), n2, d), ell,
+                 (_hip.ptr(oscale), _hip.ptr(G), n2, n1 * n2, _hip.ptr(gX), _hip.ptr(gE), _hip.ptr(gO), q,
+                  _hip.stream_ptr(dev)))
     return gX.sum(0), gE.sum(1), gO.sum(1)
+
+
+def prior_variance(oscale, q, dtype, device):
+    """k(x, x) of a stationary kernel per latent, (q): the output scale (1 without one), summed over the components of an additive
+    kernel's table (kernels.prior_diagonal)."""
+    if oscale is None:
+        return torch.ones(q, dtype=dtype, device=device)
+    return oscale.sum(-1) if oscale.dim() == 2 else oscale
 
 
 class WhitenedInterp(torch.autograd.Function):
     """A_i = L_i^-1 K_i(Z, X),  L_i L_i^T = K_i(Z, Z) + jitter I   for q latent kernels.
 
-    forward(Z (m,d), X (n,d), ell (q,d), oscale (q)|None, kind, jitter) -> A (q, m, n)"""
+    forward(Z (m,d), X (n,d), ell (q,d), oscale (q)|None, kind, jitter) -> A (q, m, n)
+    ell (q,G,d), oscale (q,G)|None: the component table of an additive kernel; the gradients have the shapes of the inputs."""
 
     @staticmethod
     def forward(ctx, Z, X, ell, oscale, kind, jitter):
@@ -256,7 +269,7 @@ def unwhitened_predictive(kind, Z, X, ell, oscale, mvar, Ls, jitter):
     from ._dense import gemm_tn, TRI_A_LOWER
     B = gemm_tn(torch.tril(ws.W[:, :n, :n]), C, TRI_A_LOWER)                         # Khat^-1 K_ZX = W^T C
     mean = (B.transpose(-1, -2) @ mvar.to(dt).unsqueeze(-1)).squeeze(-1)
-    os_ = torch.ones(q, dtype=dt, device=dev) if osc is None else osc
+    os_ = prior_variance(osc, q, dt, dev)
     LB = gemm_tn(torch.tril(Ls.to(dt)), B, TRI_A_LOWER)                               # Ls^T B
     var = os_[:, None] - (C * C).sum(-2) + (LB * LB).sum(-2)
     return mean, var

@@ -43,6 +43,10 @@ class AdditiveKernel(Kernel):
             raise NotImplementedError("all sub-kernels of a decomposition must be of the same type")
         return kinds[0], torch.stack(ells, 1), torch.stack(oss, 1)
 
+    def _pieces(self, d, like=None):
+        """The component table, for the wrappers that ask a kernel for its pieces (sgpr.InducingPointKernel, the variational strategies)."""
+        return self.table(d)
+
     def forward(self, x1, x2=None, **params):
         kind, ell, osc = self.table(x1.shape[-1])
         return LazyKernel(kind, x1, x1 if x2 is None else x2, ell, osc, torch.Size([ell.shape[0]]))

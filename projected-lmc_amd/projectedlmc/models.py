@@ -352,12 +352,17 @@ class ExactGPModel(ExactGP):
         return torch.linalg.cond(lazy.to_dense())
 
     # -- inspection helpers (projected_lmc.py:324-365)
-    def _base(self):
+    def _kernel(self):
+        """The model's kernel without the inducing-point wrapper (sgpr.InducingPointKernel) around it."""
         cm = self.covar_module
+        return cm.base_kernel if hasattr(cm, "inducing_points") else cm
+
+    def _base(self):
+        cm = self._kernel()
         return cm.base_kernel if hasattr(cm, "base_kernel") else cm
 
     def lscales(self, unpacked=True):
-        cm = self.covar_module
+        cm = self._kernel()
         if hasattr(cm, "kernels"):                                   # additive decomposition: one entry per sub-kernel
             return [(k.base_kernel if hasattr(k, "base_kernel") else k).lengthscale.data.squeeze() for k in cm.kernels]
         scales = self._base().lengthscale.data.squeeze()
@@ -365,7 +370,7 @@ class ExactGPModel(ExactGP):
 
     def outputscale(self, unpacked=False):
         n_funcs = self.n_latents if hasattr(self, "n_latents") else self.n_tasks
-        cm = self.covar_module
+        cm = self._kernel()
         if hasattr(cm, "kernels"):
             res = torch.zeros((n_funcs, len(cm.kernels)))
             for i_ker, k in enumerate(cm.kernels):

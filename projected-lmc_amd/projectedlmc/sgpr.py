@@ -94,7 +94,7 @@ class LazySgprKernel:
         s1 = s.reshape(q)
         quad = ((y * y).sum(-1) - cc / s1) / s1
         logdet = n * torch.log(s1) + logdetB
-        os_ = torch.ones(q, dtype=A.dtype, device=A.device) if self.oscale is None else self.oscale
+        os_ = _var_engine.prior_variance(self.oscale, q, A.dtype, A.device)         # k(x, x): an additive kernel's scales summed
         self.owner._added_loss = -0.5 * (n * os_ - (A * A).sum((-2, -1))) / s1
         return -0.5 * (quad + logdet + n * math.log(2.0 * math.pi))
 

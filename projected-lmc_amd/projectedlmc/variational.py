@@ -89,7 +89,7 @@ class VariationalStrategy(torch.nn.Module):
         mean_f = (A.transpose(-1, -2) @ mvar.unsqueeze(-1)).squeeze(-1)
         Bm = _var_engine.lower_t_matmul(Ls, A)                                    # Ls^T A, triangular contraction ranges
         q = ell.shape[0]
-        os_ = torch.ones(q, dtype=dt, device=ell.device) if osc is None else osc
+        os_ = _var_engine.prior_variance(osc, q, dt, ell.device)
         var_f = os_[:, None] + jit - (A * A).sum(-2) + (Bm * Bm).sum(-2)
         m = Z.shape[-2]
         logdetS = 2.0 * torch.log(torch.diagonal(Ls, dim1=-2, dim2=-1).abs()).sum(-1)
@@ -252,11 +252,19 @@ class VariationalMultitaskGPModel(torch.nn.Module):
 
     def lscales(self, unpacked=True):
         cm = self.covar_module
+        if hasattr(cm, "kernels"):                                   # additive decomposition: one entry per sub-kernel (ExactGPModel.lscales)
+            return [(k.base_kernel if hasattr(k, "base_kernel") else k).lengthscale.data.squeeze() for k in cm.kernels]
         base = cm.base_kernel if hasattr(cm, "base_kernel") else cm
         scales = base.lengthscale.data
         return scales if unpacked else [scales]
 
     def outputscale(self, unpacked=False):
+        cm = self.covar_module
+        if hasattr(cm, "kernels"):
+            res = torch.zeros((self.n_latents, len(cm.kernels)))
+            for i_ker, k in enumerate(cm.kernels):
+                res[:, i_ker] = k.outputscale.data.squeeze()
+            return res
         res = torch.zeros((self.n_latents, 1))
         res[:, 0] = self.covar_module.outputscale.data.squeeze()
         return res.squeeze() if unpacked else res
