@@ -467,6 +467,61 @@ int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64
                               int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
 
 /*
+ * Leave-one-out objective (LeaveOneOutPseudoLikelihood, projected_lmc.py:86-105): with P = Khat^-1, alpha = P y, p_i = P_ii,
+ *     L = sum_i [ 1/2 log p_i - 1/2 alpha_i^2 / p_i ] - n/2 log 2 pi,
+ *     c_i = 1/2 / p_i + 1/2 alpha_i^2 / p_i^2,   g_i = -alpha_i / p_i,   u = P g = dL / dy,
+ *     dL / dKhat = G = -[ P diag(c) P + 1/2 (alpha u^T + u alpha^T) ].
+ * For any s > 0 and v+- = s alpha +- u / s:  2 G = beta beta^T - Xop^T Xop  with  beta = v- / sqrt 2  and
+ *     Xop = [ diag(sqrt(2 c)) P ; v+^T / sqrt 2 ],
+ * the full symmetric P with scaled rows and one more row.  That is the form (a a^T - X^T X) whose contraction with dKhat / dtheta the
+ * epilogues of plmc_kinv_grad*_vd_* reduce, so the gradient of L is those epilogues behind another tile product.
+ *
+ * plmc_loo_grad*_: the arguments of the family's plmc_kinv_grad*_vd_* with (W, n_pad, ldw, strideW, alpha) replaced by
+ *   (Xop, n_pad, krows, ldx, strideX, beta) and without Kinv, ldk, strideK, kinv_diag, eig_lo and Vd.
+ *     grad[latent] = the family's gradient table (same layout, same reductions) of
+ *                    1/2 sum_{i, j < n} (beta_i beta_j - [Xop^T Xop]_ij) dKhat_ij / dtheta.
+ *   Xop: krows x n_pad per latent, K-major (row = contraction index), leading dimension ldx, batch stride strideX; every row in
+ *   [0, krows) is contracted, so rows that carry nothing must be zero.  krows a multiple of 16, ldx a multiple of plmc_block() and >=
+ *   n_pad, the pointer 16-byte aligned.  beta: q x n_pad.  `partials`: plmc_grad_partials_bytes(n_pad, q * ncomp),
+ *   plmc_sm_grad_partials_bytes, plmc_per_grad_partials_bytes as for the `_vd` calls.  With Xop = W (the inverse factor with zeros above
+ *   its diagonal, krows = n_pad) and beta = alpha the call returns what plmc_kinv_grad*_vd_* returns.  Both element types form the
+ *   product with the matrix instructions of that type (fp32: v_mfma_f32_16x16x4_f32 whatever PLMC_SPLIT says).  q n_pad^2 krows
+ *   flop (upper tiles only).
+ * plmc_loo_operand_*: Xop[k][i] = rowscale[k] P_ki for k, i < n from the upper triangle that plmc_kinv_grad*_vd_* writes into `Kinv`
+ *   (n_pad x ldk per latent; what lies below the diagonal is not read), mirrored across the diagonal; exact zeros everywhere else in
+ *   [0, krows) x [0, n_pad).  rowscale: q x n_pad.  krows >= n, a multiple of 16.  The caller writes the extra row afterwards.
+ * Bad arguments fail through plmc_last_error() before anything is launched.
+ */
+int plmc_loo_grad_f32(int kind, const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta,
+                      const float *X, int n, int d, const float *ell, const float *oscale, double *grad, void *partials, int q,
+                      void *stream);
+int plmc_loo_grad_f64(int kind, const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta,
+                      const double *X, int n, int d, const double *ell, const double *oscale, double *grad, void *partials, int q,
+                      void *stream);
+int plmc_loo_grad_add_f32(int kind, const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta,
+                          const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, double *grad, void *partials,
+                          int q, void *stream);
+int plmc_loo_grad_add_f64(int kind, const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta,
+                          const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, double *grad, void *partials,
+                          int q, void *stream);
+int plmc_loo_grad_sm_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                         int n, int d, int nmix, const float *scales, const float *means, const float *weights, double *grad,
+                         void *partials, int q, void *stream);
+int plmc_loo_grad_sm_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                         int n, int d, int nmix, const double *scales, const double *means, const double *weights, double *grad,
+                         void *partials, int q, void *stream);
+int plmc_loo_grad_per_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                          int n, int d, const float *ell, const float *period, const float *oscale, double *grad, void *partials, int q,
+                          void *stream);
+int plmc_loo_grad_per_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                          int n, int d, const double *ell, const double *period, const double *oscale, double *grad, void *partials, int q,
+                          void *stream);
+int plmc_loo_operand_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *rowscale, float *Xop, int64_t krows,
+                         int64_t ldx, int64_t strideX, int n, int q, void *stream);
+int plmc_loo_operand_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *rowscale, double *Xop, int64_t krows,
+                         int64_t ldx, int64_t strideX, int n, int q, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

@@ -501,6 +501,176 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
   return launch_status(__func__);
 }
 
+
+// ---- leave-one-out pseudo-likelihood: the gradient epilogues above behind another tile product.
+// d L_loo / d Khat = G with 2 G = beta beta^T - Xop^T Xop ("Leave-one-out objective"): Xop is the full symmetric Khat^-1 with
+// scaled rows and one more row, krows x n_pad per latent, K-major like W.  So the tile (ib, jb) is the product of the two column strips
+// over ALL krows rows (W^T W stops at the diagonal block: W is triangular, Xop is not), `beta` is staged where alpha was, and the epilogue
+// text reduces (beta_i beta_j - acc_ij) dKhat_ij / dtheta exactly as it does for the marginal likelihood; nothing is stored.
+// Every tile has the same depth, so the order is the XCD-dealt one of gemm_core.hpp: the 64 tiles of a super-block stream their 8 + 8
+// strips through one L2.  fp32 runs on v_mfma_f32_16x16x4_f32 (no split engine for this product).
+#define PLMC_LOO_TILE_PRODUCT                                                                                                                  \
+  const int m = (int)(n_pad / NB);                                                                                                             \
+  int lat, ib, jb;                                                                                                                             \
+  if (!xcd_tri_decode((int)blockIdx.x, m, nlat, lat, ib, jb)) return;                                                                          \
+  __shared__ __align__(16) T smem[tile_smem_elems<T>()];                                                                                       \
+  const T *Xl = Xop + (int64_t)lat * strideX;                                                                                                  \
+  Acc<T> acc;                                                                                                                                  \
+  acc.zero();                                                                                                                                  \
+  tile_mainloop<T, false, false>(acc, Xl + (int64_t)ib * NB, ldx, Xl + (int64_t)jb * NB, ldx, (int)krows, smem);                               \
+  const T *__restrict__ alpha = beta;                                                                                                          \
+  T *const Kinv = nullptr, *const kinv_diag = nullptr;                                                                                         \
+  constexpr int64_t ldk = 0, strideK = 0;                                                                                                      \
+  const int tid = threadIdx.x;                                                                                                                 \
+  constexpr bool live = true
+
+// occupancy floor: that of k_kinv_grad, except fp32 with 5..8 dimensions -- k_kinv_grad<float, 8> sits at exactly 128 registers, and behind
+// this tile product the same epilogue text needs a few more: at 4 waves per SIMD it would spill 24 bytes per lane, at 3 it does not
+template <typename T, int DCAP> constexpr int LOO_MIN_WAVES = (sizeof(T) == 4 && DCAP == 8) ? 3 : KG_MIN_WAVES<T, DCAP>;
+
+template <typename T, int DCAP, bool SPLINE = false>
+__global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad(int kind, const T *__restrict__ Xop, int64_t n_pad, int64_t krows,
+                                                                                int64_t ldx, int64_t strideX, const T *__restrict__ beta,
+                                                                                const T *__restrict__ X, int n, int d, const T *__restrict__ ell,
+                                                                                const T *__restrict__ oscale, double *__restrict__ partials,
+                                                                                int nlat) {
+  PLMC_LOO_TILE_PRODUCT;
+#define PLMC_KINV_KEEP (sizeof(T) == 4)
+#include "kinv_epilogue.inc"
+#undef PLMC_KINV_KEEP
+}
+
+template <typename T, CovFamily F, int DC = 0>
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
+    int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
+    const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
+    const T *__restrict__ means) {
+  PLMC_LOO_TILE_PRODUCT;
+#include "kinv_epilogue_table.inc"
+}
+
+// Xop[k][i] = rowscale[k] P_ki for k, i < n from the upper triangle of P = Khat^-1 that the K^-1 + gradient kernels store (their `Kinv`
+// output), mirrored across the diagonal; exact zeros in the rest of [0, krows) x [0, n_pad).  One 64 x 64 tile of Xop per workgroup: the
+// source tile (min, max) of the pair goes through LDS with 16-byte loads and is read back straight or transposed.  grid (n_pad / 64,
+// ceil(krows / 64), q).  HBM-bound: one read and one write per element.
+constexpr int OPT = 64;
+template <typename T>
+__global__ __launch_bounds__(NTHREADS) void k_loo_operand(const T *__restrict__ Kinv, int64_t ldk, int64_t strideK, const T *__restrict__ rowscale,
+                                                          int64_t n_pad, T *__restrict__ Xop, int64_t krows, int64_t ldx, int64_t strideX, int n) {
+  using vec_t = typename Traits<T>::vec_t;
+  constexpr int EPV = Traits<T>::EPV;
+  constexpr int CPR = OPT / EPV;                       // 16-byte chunks per tile row
+  constexpr int NCH = OPT * CPR / NTHREADS;            // chunks per thread
+  __shared__ T s[OPT][OPT + 1];
+  const int cb = blockIdx.x, kb = blockIdx.y, lat = blockIdx.z;
+  const int k0 = kb * OPT, i0 = cb * OPT;
+  const int tid = threadIdx.x;
+  const bool any = k0 < n && i0 < n;                   // (then both tiles lie inside n_pad x n_pad)
+  if (any) {
+    const int rb = kb < cb ? kb : cb, sb = kb < cb ? cb : kb;
+    const T *src = Kinv + (int64_t)lat * strideK + (int64_t)rb * OPT * ldk + (int64_t)sb * OPT;
+#pragma unroll
+    for (int h = 0; h < NCH; ++h) {
+      const int c = tid + h * NTHREADS, r = c / CPR, c0 = (c % CPR) * EPV;
+      const vec_t v = *reinterpret_cast<const vec_t *>(src + (int64_t)r * ldk + c0);
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) s[r][c0 + e] = v[e];
+    }
+    __syncthreads();
+  }
+  T *dst = Xop + (int64_t)lat * strideX + (int64_t)k0 * ldx + i0;
+#pragma unroll
+  for (int h = 0; h < NCH; ++h) {
+    const int c = tid + h * NTHREADS, r = c / CPR, c0 = (c % CPR) * EPV;
+    const int k = k0 + r;
+    if (k >= krows) continue;
+    vec_t o;
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) o[e] = T(0);
+    if (any && k < n) {
+      const T rs = rowscale[(int64_t)lat * n_pad + k];
+#pragma unroll
+      for (int e = 0; e < EPV; ++e) {
+        const int li = c0 + e;
+        const bool straight = kb < cb || (kb == cb && li >= r);
+        const T p = straight ? s[r][li] : s[li][r];
+        o[e] = i0 + li < n ? rs * p : T(0);
+      }
+    }
+    *reinterpret_cast<vec_t *>(dst + (int64_t)r * ldx + c0) = o;
+  }
+}
+
+// The sibling of kinv_grad_impl<T, void> for the leave-one-out gradient: the same table, the same partial sums, the same reductions.
+template <typename T>
+int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,
+                  double *grad, void *partials, int q, void *stream) {
+  PLMC_REQUIRE_TABLE(table);
+  const CovFamily family = table.route();
+  const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
+  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second;
+  PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
+  PLMC_REQUIRE(Xop && beta && X && ell && grad && partials, "null pointer");
+  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && n > 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE(krows > 0 && krows % BK == 0 && krows < ((int64_t)1 << 31), "krows must be a positive multiple of 16");
+  PLMC_REQUIRE(ldx >= n_pad && ldx % NB == 0, "ldx must be a multiple of the block size, at least n_pad");
+  PLMC_REQUIRE(q == 1 || strideX >= krows * ldx, "strideX too small");
+  PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
+  PLMC_REQUIRE(aligned16(Xop) && strideX % (16 / (int64_t)sizeof(T)) == 0, "unaligned Xop");
+  hipStream_t st = (hipStream_t)stream;
+  const int m = (int)(n_pad / NB);
+  double *part = reinterpret_cast<double *>(partials);
+  const double np = (double)n_pad;
+  const dim3 grid(xcd_tri_grid(m, q)), block(NTHREADS);
+#define PLMC_LAUNCH_LG(DC, SP) \
+  hipLaunchKernelGGL((k_loo_grad<T, DC, SP>), grid, block, 0, st, kind, Xop, n_pad, krows, ldx, strideX, beta, X, n, d, ell, oscale, part, q)
+#define PLMC_LAUNCH_LT(F, DC) \
+  hipLaunchKernelGGL((k_loo_grad_add<T, F, DC>), grid, block, 0, st, kind, ncomp, Xop, n_pad, krows, ldx, strideX, beta, X, n, d, ell, oscale, part, q, \
+                     second)
+  {
+    ProfScope ps(PK_KINV_GRAD, st, q * np * np * (double)krows, q * np * (double)krows * sizeof(T));
+    switch (family) {
+      case COV_PER: if (d == 1) PLMC_LAUNCH_LT(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_PER, 4); else PLMC_LAUNCH_LT(COV_PER, 8); break;
+      case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
+      case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
+      case COV_PLAIN:
+        if (d <= 4) PLMC_LAUNCH_LG(4, false);
+        else if (d <= 8) PLMC_LAUNCH_LG(8, false);
+        else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_LG(16, true); else PLMC_LAUNCH_LG(16, false); }
+        else { if (kind == K_SPLINE) PLMC_LAUNCH_LG(32, true); else PLMC_LAUNCH_LG(32, false); }
+    }
+  }
+#undef PLMC_LAUNCH_LT
+#undef PLMC_LAUNCH_LG
+  {
+    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
+    switch (family) {
+      case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+      case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+      case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
+    }
+  }
+  return launch_status(__func__);
+}
+
+template <typename T>
+int loo_operand_impl(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *rowscale, T *Xop, int64_t krows, int64_t ldx,
+                     int64_t strideX, int n, int q, void *stream) {
+  constexpr int64_t EPV = 16 / (int64_t)sizeof(T);
+  PLMC_REQUIRE(Kinv && rowscale && Xop, "null pointer");
+  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && n > 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
+  PLMC_REQUIRE(q > 0 && q <= 65535, "need 0 < q <= 65535");
+  PLMC_REQUIRE(krows >= n && krows % BK == 0 && krows <= 65535 * (int64_t)OPT, "krows must be a multiple of 16, at least n");
+  PLMC_REQUIRE(ldk >= n_pad && ldk % EPV == 0 && strideK % EPV == 0 && aligned16(Kinv), "Kinv: ldk >= n_pad, 16-byte aligned rows");
+  PLMC_REQUIRE(ldx >= n_pad && ldx % NB == 0 && strideX % EPV == 0 && aligned16(Xop), "Xop: ldx a multiple of the block size, at least n_pad");
+  PLMC_REQUIRE(q == 1 || (strideK >= n_pad * ldk && strideX >= krows * ldx), "batch stride too small");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(n_pad / OPT), (unsigned)((krows + OPT - 1) / OPT), q);
+  hipLaunchKernelGGL(k_loo_operand<T>, grid, dim3(NTHREADS), 0, st, Kinv, ldk, strideK, rowscale, n_pad, Xop, krows, ldx, strideX, n);
+  return launch_status(__func__);
+}
+
 }  // namespace plmc
 
 extern "C" {
@@ -638,4 +808,31 @@ int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
   (void)eig_lo;
   return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
 }
+// leave-one-out pseudo-likelihood (include/plmc.h, "Leave-one-out objective"): the family's gradient table of 1/2 (beta beta^T - Xop^T Xop)
+#define PLMC_LOO_ENTRY(SUF, T)                                                                                                                  \
+  int plmc_loo_grad_##SUF(int kind, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n, \
+                          int d, const T *ell, const T *oscale, double *grad, void *partials, int q, void *stream) {                           \
+    return plmc::loo_grad_impl<T>(CovTable::plain(kind, d, ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
+  }                                                                                                                                             \
+  int plmc_loo_grad_add_##SUF(int kind, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X,    \
+                              int n, int d, int ncomp, const T *ell, const T *oscale, double *grad, void *partials, int q, void *stream) {     \
+    return plmc::loo_grad_impl<T>(CovTable::add(kind, d, ncomp, ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q,   \
+                                  stream);                                                                                                      \
+  }                                                                                                                                             \
+  int plmc_loo_grad_sm_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n, int d, \
+                             int nmix, const T *scales, const T *means, const T *weights, double *grad, void *partials, int q, void *stream) { \
+    return plmc::loo_grad_impl<T>(CovTable::sm(d, nmix, scales, means, weights), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, \
+                                  stream);                                                                                                      \
+  }                                                                                                                                             \
+  int plmc_loo_grad_per_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
+                              int d, const T *ell, const T *period, const T *oscale, double *grad, void *partials, int q, void *stream) {      \
+    return plmc::loo_grad_impl<T>(CovTable::per(d, ell, period, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
+  }                                                                                                                                             \
+  int plmc_loo_operand_##SUF(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *rowscale, T *Xop, int64_t krows, int64_t ldx, \
+                             int64_t strideX, int n, int q, void *stream) {                                                                    \
+    return plmc::loo_operand_impl<T>(Kinv, n_pad, ldk, strideK, rowscale, Xop, krows, ldx, strideX, n, q, stream);                              \
+  }
+PLMC_LOO_ENTRY(f32, float)
+PLMC_LOO_ENTRY(f64, double)
+#undef PLMC_LOO_ENTRY
 }

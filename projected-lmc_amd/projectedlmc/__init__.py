@@ -12,7 +12,7 @@ from .kernels import RBFKernel, MaternKernel, SplineKernel, SpectralMixtureKerne
 from .means import ZeroMean, ConstantMean, MultitaskMean, LinearMean, PolynomialMean  # noqa: F401
 from .likelihoods import GaussianLikelihood, MultitaskGaussianLikelihood  # noqa: F401
 from .distributions import MultivariateNormal, MultitaskMultivariateNormal  # noqa: F401
-from .mlls import ExactMarginalLogLikelihood  # noqa: F401
+from .mlls import ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood  # noqa: F401
 from .models import (ExactGPModel, handle_covar_, init_lmc_coefficients, ScalarParam,  # noqa: F401
                      PositiveDiagonalParam, UpperTriangularParam, LowerTriangularParam)
 from .projected import LMCMixingMatrix, ProjectedGPModel, ProjectedLMCmll  # noqa: F401

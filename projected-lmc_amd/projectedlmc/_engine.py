@@ -139,12 +139,14 @@ def _contig(t, dtype=None):
 # [d lengthscales | d periods | d noise | d oscale] splits like the others.
 PER = "periodic"
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
-        "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd"}
+        "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
+        "plmc_loo_grad": "plmc_loo_grad_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
-       "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd"}
+       "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
+       "plmc_loo_grad": "plmc_loo_grad_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
-        "plmc_kernel_vjp": "plmc_kernel_vjp_add"}
+        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add"}
 
 
 def is_sm(ell):
@@ -452,6 +454,103 @@ def exact_loo(kind, X, ell, oscale, noise, y):
                  _hip.ptr(ws.partials), q, _hip.ptr(nzc), _hip.ptr(ws.Vd), st))
     sigma2 = 1.0 / kd[:, :n]
     return sigma2, ws.alpha[:, :n] * sigma2
+
+
+def loo_gradient_operands(kdiag, alpha, u=None, n=None):
+    """What the gradient of the leave-one-out objective L = sum_i [1/2 log p_i - 1/2 alpha_i^2 / p_i] is built from (DESIGN.md,
+    "Leave-one-out objective"), from p = diag(Khat^-1) and alpha = Khat^-1 y, both (q, n_pad); plain torch on any device.
+        c = 1/2 / p + 1/2 alpha^2 / p^2 ,   g = -alpha / p          (u = Khat^-1 g is dL / dy)
+    and, given u (q, n_pad), with s = sqrt(|u| / |alpha|) per latent and v+- = s alpha +- u / s:
+        beta = v- / sqrt 2 ,   rowscale = sqrt(2 c) ,   extra_row = v+ / sqrt 2 ,
+    so that 2 dL / dKhat = beta beta^T - Xop^T Xop for Xop = [diag(rowscale) Khat^-1 ; extra_row^T].  Entries at or beyond n are 0.
+    Returns (c, g) or (c, g, beta, rowscale, extra_row)."""
+    n = kdiag.shape[-1] if n is None else n
+    live = torch.arange(kdiag.shape[-1], device=kdiag.device) < n
+    p = torch.where(live, kdiag, torch.ones_like(kdiag))
+    a = torch.where(live, alpha, torch.zeros_like(alpha))
+    c = torch.where(live, 0.5 / p + 0.5 * a * a / (p * p), torch.zeros_like(p))
+    g = -a / p
+    if u is None:
+        return c, g
+    u = torch.where(live, u, torch.zeros_like(u))
+    nu, na = u.norm(dim=-1, keepdim=True), a.norm(dim=-1, keepdim=True)
+    s = torch.where((nu > 0) & (na > 0), (nu / na.clamp_min(torch.finfo(a.dtype).tiny)).sqrt(), torch.ones_like(nu))
+    r = math.sqrt(0.5)
+    return c, g, (s * a - u / s) * r, (2.0 * c).sqrt(), (s * a + u / s) * r
+
+
+def _loo_buffers(ws):
+    """K^-1 (n_pad rows of n_pad + NB) and the gradient product's operand (n_pad + NB rows of n_pad; n_pad + 16 are used) of the
+    leave-one-out objective, q (n_pad + NB) n_pad elements each, kept with the workspace."""
+    buf = getattr(ws, "loo", None)
+    if buf is None:
+        buf = ws.loo = (torch.empty(ws.q, ws.n_pad, ws.n_pad + ws.NB, dtype=ws.dtype, device=ws.device),
+                        torch.empty(ws.q, ws.n_pad + ws.NB, ws.n_pad, dtype=ws.dtype, device=ws.device))
+    return buf
+
+
+class ExactLooLogProb(torch.autograd.Function):
+    """Leave-one-out log predictive density sum_i log N(y_i; mu_-i, sigma2_-i) of q independent GPs, with the analytic gradient
+    computed in the same pass ("Leave-one-out objective"): from the factorisation the MLL uses,
+        L = sum_i [1/2 log p_i - 1/2 alpha_i^2 / p_i] - n/2 log 2 pi ,   p = diag(Khat^-1), alpha = Khat^-1 y.
+    forward(X (n,d), ell, oscale, noise (q), y (q,n), kind) -> (q,), ell / oscale as for ExactLatentLogProb.  Everything runs on the
+    current stream."""
+
+    @staticmethod
+    def forward(ctx, X, ell, oscale, noise, y, kind):
+        _hip.require_device(X, ell, noise, y)
+        L = _hip.lib()
+        dt, dev = y.dtype, y.device
+        if dt not in (torch.float32, torch.float64):
+            raise TypeError("projectedlmc hot path supports float32 and float64 tensors")
+        q, n = y.shape
+        d = X.shape[1]
+        _check_kernel_shape(L, ell, kind)
+        need_grad = any(ctx.needs_input_grad[1:5])
+        Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
+        ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), kind == PER)
+        st = _hip.stream_ptr(dev)
+        factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
+        L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
+        L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z), _hip.ptr(ws.alpha), q, st)
+        Kinv, Xop = _loo_buffers(ws)
+        ldk, ldx, krows = Kinv.shape[2], Xop.shape[2], ws.n_pad + 16
+        grad = torch.empty(q, grad_table_width(ellc, kind), dtype=torch.float64, device=dev)
+        kd = torch.empty(q, ws.n_pad, dtype=dt, device=dev)
+        # K^-1 and its diagonal; the MLL gradient table this call also writes is overwritten below
+        _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.alpha),
+                     _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad), _hip.ptr(Kinv), ldk, ws.n_pad * ldk, _hip.ptr(kd),
+                     _hip.ptr(ws.partials), q, _hip.ptr(nzc), _hip.ptr(ws.Vd), st))
+        p, a = kd[:, :n].double(), ws.alpha[:, :n].double()
+        value = (0.5 * p.log() - 0.5 * a * a / p).sum(-1) - 0.5 * n * LOG2PI
+        if need_grad:
+            c, g = loo_gradient_operands(kd, ws.alpha, n=n)
+            rowscale = (2.0 * c).sqrt()
+            L.call("plmc_loo_operand", dt, _hip.ptr(Kinv), ws.n_pad, ldk, ws.n_pad * ldk, _hip.ptr(rowscale), _hip.ptr(Xop), krows, ldx,
+                   Xop.shape[1] * ldx, n, q, st)
+            # u = Khat^-1 g = Xop^T (g / rowscale) over the live block
+            u = torch.zeros(q, ws.n_pad, dtype=dt, device=dev)
+            u[:, :n] = torch.bmm(Xop[:, :n, :n].transpose(1, 2), (g[:, :n] / rowscale[:, :n]).unsqueeze(-1)).squeeze(-1)
+            beta, extra = loo_gradient_operands(kd, ws.alpha, u, n)[2::2]
+            Xop[:, ws.n_pad, :] = extra
+            beta = beta.contiguous()
+            _kernel_call(L, "plmc_loo_grad", dt, (kind_code(kind), _hip.ptr(Xop), ws.n_pad, krows, ldx, Xop.shape[1] * ldx, _hip.ptr(beta),
+                         _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad), _hip.ptr(ws.partials), q, st))
+            ctx.save_for_backward(grad, u[:, :n].clone())
+        ctx.ell_shape = ell.shape
+        ctx.os_shape = None if oscale is None else oscale.shape
+        return value.to(dt)
+
+    @staticmethod
+    def backward(ctx, gout):
+        grad, u = ctx.saved_tensors
+        g_ell, g_noise, g_os = _split_grad_table(gout.to(torch.float64)[:, None] * grad, ctx.ell_shape, ctx.os_shape)
+        return None, g_ell, g_os, g_noise, gout[:, None].to(u.dtype) * u, None
+
+
+def exact_loo_log_prob(kind, X, ell, oscale, noise, y):
+    """(q,) leave-one-out log predictive densities of y (q, n) under q independent exact GPs; see ExactLooLogProb."""
+    return ExactLooLogProb.apply(X, ell, oscale, noise, y, kind)
 
 
 class PosteriorCache:

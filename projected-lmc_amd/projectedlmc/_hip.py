@@ -51,6 +51,11 @@ _TYPED = {
     "plmc_kinv_grad_add_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_per_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
+    "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_per": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],

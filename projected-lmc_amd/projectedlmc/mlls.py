@@ -45,3 +45,46 @@ class ExactMarginalLogLikelihood(MarginalLogLikelihood):
         res = self._add_other_terms(res, params)
         num_data = function_dist.event_shape.numel()
         return res / num_data
+
+
+class LeaveOneOutPseudoLikelihood(ExactMarginalLogLikelihood):
+    """The leave-one-out cross-validation objective of the reference (projected_lmc.py:86-105; gpytorch ships it under the same name):
+    loo(model(X), Y) = [ sum_i log N(y_i; mu_-i, sigma2_-i) + other terms ] / num_data, the predictive density of every training point
+    given all the others (Rasmussen & Williams 5.4.2), from diag(Khat^-1) and Khat^-1 y of the factorisation the MLL uses, with the
+    analytic gradient (_engine.ExactLooLogProb).  Constructor order as in the reference; train_x / train_y are kept and not used.
+    Serves ExactGPModel without inducing points (a batch of independent tasks is summed, as log_prob does)."""
+
+    def __init__(self, likelihood, model, train_x=None, train_y=None):
+        super().__init__(likelihood, model)
+        self.train_x = train_x
+        self.train_y = train_y
+
+    def forward(self, function_dist, target, *params):
+        if not isinstance(function_dist, MultivariateNormal):
+            raise RuntimeError("LeaveOneOutPseudoLikelihood can only operate on Gaussian random variables")
+        from .kernels import LazyKernel, LazyLmcKernel
+        from .projected import ProjectedGPModel
+        # refusals by the type of the covariance (and of the model that owns it), before anything looks at a device
+        c = function_dist.lazy_covariance_matrix
+        if isinstance(self.model, ProjectedGPModel):
+            raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for ProjectedGPModel (its latent processes see "
+                                      "projected data: train it with ProjectedLMCmll)")
+        if hasattr(c, "log_prob_batch"):
+            raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for the inducing-point (SGPR) covariance of "
+                                      "ExactGPModel(n_inducing_points=...)")
+        if isinstance(c, LazyLmcKernel):
+            raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for MultitaskGPModel (dense LMC / ICM covariance)")
+        if not isinstance(c, LazyKernel):
+            raise NotImplementedError("LeaveOneOutPseudoLikelihood on %s" % type(c).__name__)
+        output = self.likelihood(function_dist, *params)
+        ind = getattr(output, "_independent", None)          # independent tasks built from a batch (from_batch_mvn): (n, p) -> (p, n)
+        dist, y = (output, target) if ind is None else (ind, target.transpose(-1, -2))
+        k = dist.lazy_covariance_matrix
+        from . import _engine
+        q = k.ell.shape[0]
+        diff = (y - dist.mean).reshape(q, -1)
+        res = _engine.exact_loo_log_prob(k.kind, k.x1, k.ell, k.oscale, k.noise.reshape(-1), diff)
+        res = res.reshape(dist.batch_shape) if ind is None else res.sum(-1)
+        res = self._add_other_terms(res, params)
+        num_data = function_dist.event_shape.numel()
+        return res / num_data
