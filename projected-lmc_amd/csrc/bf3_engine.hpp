@@ -24,8 +24,10 @@
 // so that (a) a stage of 32 contraction rows of a tile is a few runs of 2-4 KB, copied to LDS by LDS-DMA
 // (buffer_load_dwordx4 ... lds: no staging registers, no ds_write, one 1 KB piece per wave instruction) and (b) an MFMA
 // fragment is ONE conflict-free ds_read_b128 per lane (lanes 16 g .. 16 g + 15 read 256 contiguous bytes of k-group g):
-// no transposing reads, no swizzle.  Two LDS stages (SplitB3: 72 KB each, SplitH2: 48 KB); one barrier per stage: the DMA
-// of stage s + 1 is issued right after the barrier that ends the reads of stage s - 1 and lands while stage s is multiplied.
+// no transposing reads, no swizzle.  One barrier per stage.  SplitH2 (48 KB per stage): a ring of THREE LDS stages, the DMA
+// of stage s + 2 issued piece by piece between the first MFMAs behind the barrier of stage s and retired by a counted wait;
+// SplitB3 (72 KB per stage): two stages, the DMA of stage s + 1 issued right behind the barrier that ends the reads of stage
+// s - 1.  Either way a piece has at least one full stage of its wave's MFMAs to land (b3_mainloop; tests/test_isa_mainloop_layout.py).
 // Alone on the GPU (tools/bf3v2_probe.hip, depth-1024 update tiles): fp32 engine 127 TF, SplitB3 223 TF, SplitH2 353 TF
 // fp32-equivalent.
 #pragma once
@@ -69,7 +71,9 @@ struct SplitH2 {
   }
 };
 template <class S> constexpr int b3_stage_bytes() { return S::NPL * (B3_A_PLANE + B3_B_PLANE); }    // 73 728 / 49 152
-template <class S> constexpr int b3_lds_bytes() { return 2 * b3_stage_bytes<S>() > 2 * B3_WB_BYTES ? 2 * b3_stage_bytes<S>() : 2 * B3_WB_BYTES; }
+// LDS stages of the main loop: a ring of three where three fit the 160 KB of a CU (SplitH2: 144 KB), else two (SplitB3: 144 KB)
+template <class S> constexpr int b3_nstages() { return 3 * b3_stage_bytes<S>() <= 160 * 1024 ? 3 : 2; }
+template <class S> constexpr int b3_lds_bytes() { return b3_nstages<S>() * b3_stage_bytes<S>() > 2 * B3_WB_BYTES ? b3_nstages<S>() * b3_stage_bytes<S>() : 2 * B3_WB_BYTES; }
 
 // element (k, plane, column) of a k8-ordered plane buffer with `ld` columns, in 16-bit elements
 template <class S> __host__ __device__ inline int64_t b3_index(int64_t k, int plane, int64_t col, int64_t ld) {
@@ -129,21 +133,33 @@ __device__ __forceinline__ void b3_split_block(const float *__restrict__ Sp, int
 
 // acc0 / acc1 += the two levels of  sum_{k < K} A[k][a-columns]^T B[k][b-columns]  for this wave's 64 x 64 block.
 //   Ap: plane buffer at (k = first row of the K range, plane 0, first of the 256 A columns), lda_ columns per plane row;
-//   Bp: likewise, first of the 128 B columns, ldb_ columns;  K % 64 == 0;  lds: b3_lds_bytes<S>(), 16-byte aligned, the
-//   kernel's ONLY __shared__ object (a second one makes hipcc drain the DMA before every fragment read).
+//   Bp: likewise, first of the 128 B columns, ldb_ columns;  K % 64 == 0 and K >= 128 (the ring starts with three stages in
+//   flight; every caller's depth is a multiple of 128);  lds: b3_lds_bytes<S>(), 16-byte aligned, the kernel's ONLY __shared__
+//   object (a second one makes hipcc drain the DMA before every fragment read).
 // All 512 threads must call it; ends with a barrier (LDS free for the epilogue).
-// `pre` (optional): called once, right behind the LAST DMA issue of the loop, two stages before its end -- the place for the
-// epilogue's first C loads (b3_preload): NPRE = the vector-memory loads it issues (0 or 8).  They are the youngest memory
-// operations of the wave, so the remaining barriers wait for "all but the NPRE youngest" and the loads stay in flight
+// `pre` (optional): pre(h), h = 0 .. NPRE - 1, each ONE vector-memory load, called behind the LAST DMA issue of the loop, two
+// stages before its end -- the place for the epilogue's first C loads (b3_preload; NPRE = 0 or 8).  They are the youngest memory
+// operations of the wave, so the remaining waits are for "all but the NPRE youngest" and the loads stay in flight
 // through the last two stages (an older load would hold back every DMA piece behind it: vmcnt counts in issue order).
-struct B3NoPre { __device__ __forceinline__ void operator()() const {} };
+// Diagnostic build of tools/engine_rate_probe.hip (-DPLMC_STAGE_STAMPS; never in the library): every wave stamps s_memtime at
+// seven points of its LAST steady-state stage -- 0 barrier exit, 1 behind the first pair of MFMAs, 2 behind the last DMA issue,
+// 3 behind the last MFMA, 4 arrival at the wait in front of the next barrier, 5 that wait done, 6 next barrier exit (the
+// two-stage loop stamps 0, 3 and 6 only) -- and the waves of the first 16 workgroups leave them in
+// plmc_b3_stamps[(workgroup * 8 + wave) * 8 + point], a buffer nothing else reads.
+#ifdef PLMC_STAGE_STAMPS
+__device__ unsigned long long *plmc_b3_stamps;
+#define B3_STAMP(i) b3_st[i] = __builtin_readcyclecounter()
+#else
+#define B3_STAMP(i) do { } while (0)
+#endif
+struct B3NoPre { __device__ __forceinline__ void operator()(int) const {} };
 // REV: walk the K range from its last stage to its first -- tiles whose ranges END at the same row (the K^-1 tiles: every
 // range ends at n) then read the same operand rows at the same time, whatever their length.
-template <class S, int NSTG = 2, int NPRE = 0, class PRE = B3NoPre, bool REV = false>
+template <class S, int NPRE = 0, class PRE = B3NoPre, bool REV = false>
 __device__ __forceinline__ void b3_mainloop(Acc<float> &acc0, Acc<float> &acc1, const unsigned short *__restrict__ Ap, int64_t lda_,
                                             const unsigned short *__restrict__ Bp, int64_t ldb_, int K, unsigned char *lds, PRE pre = PRE()) {
-  static_assert(NPRE == 0 || (NPRE == 8 && NSTG == 2), "pre-loads: eight, two-stage loop only");
-  constexpr int NPL = S::NPL, STAGE = b3_stage_bytes<S>();
+  static_assert(NPRE == 0 || NPRE == 8, "pre-loads: none or eight");
+  constexpr int NPL = S::NPL, STAGE = b3_stage_bytes<S>(), NSTG = b3_nstages<S>();
   typedef typename S::frag_t frag_t;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave 0..7, provably uniform (DMA destinations are scalar)
@@ -163,19 +179,22 @@ __device__ __forceinline__ void b3_mainloop(Acc<float> &acc0, Acc<float> &acc1, 
   const char *baseA = reinterpret_cast<const char *>(Ap) + (REV ? (int64_t)(K / B3_K - 1) * fwdA : 0);
   const char *baseB = reinterpret_cast<const char *>(Bp) + (REV ? (int64_t)(K / B3_K - 1) * fwdB : 0);
   typedef __attribute__((address_space(3))) void lds_void;
-  auto issue = [&](int buf) {
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(baseA), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(baseB), 0, 0x7fffffff, 0x00020000);
+  auto piece = [&](int buf, int j) {                               // piece j of the stage at baseA / baseB: 2 NPL of A, then NPL of B
     unsigned char *sb = lds + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < 2 * NPL; ++j)
+    if (j < 2 * NPL) {
+      const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(baseA), 0, 0x7fffffff, 0x00020000);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_void *)(sb + lA0 + (j >> 1) * B3_A_PLANE + (j & 1) * (2 * B3_AW * 16)), 16, voff,
                                                gA0 + (unsigned)(j & 1) * 2u * RSA + (unsigned)(j >> 1) * PLA, 0, 0);
+    } else {
+      const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(baseB), 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_void *)(sb + lB0 + (j - 2 * NPL) * B3_B_PLANE), 16, voff, gB0 + (unsigned)(j - 2 * NPL) * PLB, 0, 0);
+    }
+  };
+  auto advance = [&]() { baseA += stepA; baseB += stepB; };
+  auto issue = [&](int buf) {
 #pragma unroll
-    for (int j = 0; j < NPL; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_void *)(sb + lB0 + j * B3_B_PLANE), 16, voff, gB0 + (unsigned)j * PLB, 0, 0);
-    baseA += stepA;
-    baseB += stepB;
+    for (int j = 0; j < 3 * NPL; ++j) piece(buf, j);
+    advance();
   };
   // ---- fragment addresses: lane (kg = lane >> 4, fr = lane & 15) reads 16 bytes of k-group kg, row / column .. + fr
   const int kg = lane >> 4, fr = lane & 15;
@@ -223,21 +242,42 @@ __device__ __forceinline__ void b3_mainloop(Acc<float> &acc0, Acc<float> &acc1, 
       mm(acc0, a0, b0);               // h0 . h0
     }
   };
-  const int nst = K / B3_K;                                        // even
+  const int nst = K / B3_K;                                        // even, >= 4
+#ifdef PLMC_STAGE_STAMPS
+  unsigned long long b3_st[7] = {0, 0, 0, 0, 0, 0, 0};
+  auto stamps_out = [&]() {
+    if (plmc_b3_stamps && lane == 0 && blockIdx.x < 16 && blockIdx.y == 0 && blockIdx.z == 0)
+      for (int i = 0; i < 7; ++i) plmc_b3_stamps[((int)blockIdx.x * 8 + w) * 8 + i] = b3_st[i];
+  };
+#else
+  auto stamps_out = [&]() {};
+#endif
   if constexpr (NSTG == 2) {
+    // two stages (SplitB3: a third does not fit).  The pieces of stage s + 1 are issued in front of every MFMA of stage s and the
+    // wait that retires them stands behind the last one: each piece has the wave's 96 MFMAs to land.  The fences keep the compiler
+    // from sinking pieces into the stage (it put nine of eighteen 17 MFMAs in front of their wait) and MFMAs across the barrier.
+    auto fence = [&]() { __builtin_amdgcn_sched_barrier(0); };
     issue(0);
 #pragma unroll 1
     for (int s = 0; s + 2 < nst; s += 2) {
       __syncthreads();               // (vmcnt(0) + barrier) stage s has landed for every wave; stage s - 1 is read out
+      B3_STAMP(0);
       issue(1);                      // nst is even: stage s + 1 always exists
+      fence();
       compute(0);
+      fence();
+      B3_STAMP(3);
       __syncthreads();
+      B3_STAMP(6);
       issue(0);
+      fence();
       compute(1);
+      fence();
     }
     __syncthreads();                 // the last two stages
     issue(1);
-    pre();
+#pragma unroll
+    for (int h = 0; h < NPRE; ++h) pre(h);
     compute(0);
     if constexpr (NPRE == 0) {
       __syncthreads();
@@ -248,31 +288,124 @@ __device__ __forceinline__ void b3_mainloop(Acc<float> &acc0, Acc<float> &acc1, 
       compute(1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                                // LDS free for the epilogue (no vmcnt wait)
+      stamps_out();
       return;
     }
+    __syncthreads();
   } else {
-    // three stages: the DMA of stage s + 2 is issued behind the barrier that ends the reads of stage s - 1, so a stage has
-    // two stage times to land (fabric / HBM latency under load is longer than one); before stage s is read only ITS pieces
-    // must have landed: the 3 NPL younger ones of stage s + 1 may stay in flight (vmcnt counts in issue order)
-    static_assert(NSTG == 3 && 3 * STAGE <= 160 * 1024, "three stages must fit the LDS");
+    static_assert(NSTG == 3 && NPL == 2 && 3 * STAGE <= 160 * 1024, "the ring: three two-plane stages in the LDS");
+    // ---- the ring (SplitH2).  Stage s lives in buffer s % 3 and is requested TWO stages ahead; the wave's schedule inside a stage is
+    // written down here and, in the head, pinned (a sched_barrier(0) fence behind every group), not left to the compiler:
+    //   head     16 MFMAs h0.h0 of stage s - 1, whose operands a0 / b0 stayed in registers across the barrier ("owed" product), in
+    //            eight groups of two; with each of the first six groups ONE DMA piece of stage s + 2 (or, two stages before the end,
+    //            with each of the eight one C pre-load), with each of the first four one a1 read of stage s, and behind every
+    //            column group (four MFMAs) that is done with an old b0 fragment the b0 read of stage s that replaces it;
+    //   middle   16 MFMAs h1.h0 of stage s, two reads (a0, b1 of stage s) behind every four;
+    //   end      16 MFMAs h0.h1 of stage s.  h0.h0 of stage s is owed to the next head (the last one: behind the final barrier).
+    // So the matrix pipe has register-only work from the barrier on, no DMA piece is issued as a bare block, and per accumulator
+    // the MFMA sequence is the one of the two-stage loop (k order; level 1: h1.h0 then h0.h1; level 0: h0.h0).
+    //
+    // Hazard table (all eight waves run the same schedule; B(s) = the barrier at the head of stage s; piece counts per wave):
+    //   buffer s % 3, stage s            | by whom / where
+    //   issue                            | head of stage s - 2, behind B(s - 2)  (stages 0, 1, 2: before the loop)
+    //   wait that retires the pieces     | s_waitcnt in front of B(s): vmcnt(6) = all but the six pieces of stage s + 1
+    //                                    |   (stage 0: vmcnt(12), stages 1 and 2 fly; last stage: vmcnt(NPRE), the pre-loads fly)
+    //   barrier that publishes it        | B(s): every wave has passed its own wait
+    //   first read                       | a1, head of stage s, behind B(s)
+    //   last read                        | a0 / b1, middle of stage s; returned before the h0.h1 MFMAs that use them issue, i.e.
+    //                                    |   before the wave arrives at B(s + 1) (the wait there also says lgkmcnt(0))
+    //   next overwrite                   | pieces of stage s + 3, issued behind B(s + 1)
+    //   MFMAs of the issuing wave between a piece's issue and its retiring wait: >= 4 + 32 + 48 = 84 (one stage is 48)
+    // C pre-loads (NPRE = 8): issued in the head of stage nst - 2, behind the LAST DMA pieces (those of stage nst - 1, head of stage
+    // nst - 3): they are the youngest vector-memory operations of the wave at the one wait they cross, vmcnt(8) in front of
+    // B(nst - 1), and fly through the last two stages; nothing is issued behind them.
+    frag_t a0[4], a1[4], b0[4], b1[4];
+    // OWED: the h0.h0 product of the previous stage is still to do; VM: 0 nothing, 1 the DMA pieces of the stage two ahead into
+    // buffer `nbuf`, 2 the pre-loads.  The head is pinned group by group (pair of MFMAs, one vector-memory operation, at most two
+    // reads): the fences order the DMA; the reads of the middle and the end, and their lgkmcnt ladder, are the compiler's.
+    auto stage = [&](auto owed_, auto vm_, const unsigned char *st, int nbuf) {
+      constexpr bool OWED = decltype(owed_)::value;
+      constexpr int VM = decltype(vm_)::value;
+      const unsigned char *sa = st + aA, *sb = st + aB;
+      auto rdA = [&](int plane, int t) { return *reinterpret_cast<const frag_t *>(sa + plane * B3_A_PLANE + t * 256); };
+      auto rdB = [&](int plane, int t) { return *reinterpret_cast<const frag_t *>(sb + plane * B3_B_PLANE + t * 256); };
+      if constexpr (OWED) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int nt = i >> 1;
+          if (i < 4) a1[i] = rdA(1, i);
+#pragma unroll
+          for (int mt = 2 * (i & 1); mt < 2 * (i & 1) + 2; ++mt) acc0.v[mt][nt] = S::mfma(a0[mt], b0[nt], acc0.v[mt][nt]);   // h0 . h0 of the previous stage
+          if (VM == 1 && i < 3 * NPL) piece(nbuf, i);
+          if (VM == 2 && i < NPRE) pre(i);
+          if (i & 1) b0[nt] = rdB(0, nt);
+          if (VM == 1 && i == 0) B3_STAMP(1);
+          if (VM == 1 && i == 3 * NPL - 1) B3_STAMP(2);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (VM == 1) advance();
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { a1[t] = rdA(1, t); b0[t] = rdB(0, t); }
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc1.v[mt][nt] = S::mfma(a1[mt], b0[nt], acc1.v[mt][nt]);       // h1 . h0
+        a0[nt] = rdA(0, nt);
+        b1[nt] = rdB(1, nt);
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc1.v[mt][nt] = S::mfma(a0[mt], b1[nt], acc1.v[mt][nt]);       // h0 . h1
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto head = [&]() {                                            // B(s): the wait in front of it is the caller's
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    typedef std::integral_constant<bool, true> yes;
+    typedef std::integral_constant<bool, false> no;
+    typedef std::integral_constant<int, 0> vm_none;
+    typedef std::integral_constant<int, 1> vm_dma;
+    typedef std::integral_constant<int, NPRE ? 2 : 0> vm_pre;
     issue(0);
     issue(1);
-    int buf = 0;
+    issue(2);
+    asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+    head();
+    stage(no(), vm_none(), lds, 0);
+    int buf = 1;
 #pragma unroll 1
-    for (int s = 0; s < nst; ++s) {
-      if (s + 1 < nst) {
-        if constexpr (NPL == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      if (s + 2 < nst) issue(buf == 0 ? 2 : buf - 1);               // (s + 2) % 3 = the buffer of stage s - 1
-      compute(buf);
+    for (int s = 1; s + 2 < nst; ++s) {
+      B3_STAMP(4);
+      asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+      head();
+      B3_STAMP(0);
+      stage(yes(), vm_dma(), lds + buf * STAGE, buf == 0 ? 2 : buf - 1);          // stage s + 2 into the buffer of stage s - 1
+      B3_STAMP(3);
       buf = buf == 2 ? 0 : buf + 1;
     }
+    B3_STAMP(4);
+    asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");    // stage nst - 2
+    B3_STAMP(5);
+    head();
+    B3_STAMP(6);
+    stage(yes(), vm_pre(), lds + buf * STAGE, 0);
+    buf = buf == 2 ? 0 : buf + 1;
+    if constexpr (NPRE == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // stage nst - 1
+    else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+    head();
+    stage(yes(), vm_none(), lds + buf * STAGE, 0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                  // LDS free for the epilogue (no vmcnt wait: the pre-loads)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) acc0.v[mt][nt] = S::mfma(a0[mt], b0[nt], acc0.v[mt][nt]);         // the owed h0 . h0 of the last stage
   }
-  __syncthreads();
+  stamps_out();
 }
 
 // acc0 <- (acc0 + LEVEL1 acc1) * unscale   (unscale = 1 / (scale of the A family x scale of the B family); SplitB3: 1)
@@ -309,12 +442,12 @@ constexpr int B3_WB_NCH = 8;
 #ifndef B3_C_AUX_ST
 #define B3_C_AUX_ST 2
 #endif
-__device__ __forceinline__ void b3_preload(f32x4 (&vc)[B3_WB_NCH], const float *Cg, int64_t ldc, int tid, bool live) {
+// chunk h (0 .. B3_WB_NCH - 1) of the first pass
+__device__ __forceinline__ void b3_preload(f32x4 (&vc)[B3_WB_NCH], const float *Cg, int64_t ldc, int tid, bool live, int h) {
   const __amdgpu_buffer_rsrc_t rC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Cg), 0, __builtin_amdgcn_readfirstlane(live ? 0x7fffffff : 0), 0x00020000);
   const unsigned voff = (unsigned)(((int64_t)(tid / 32) * ldc + (tid % 32) * 4) * 4);
   const unsigned rstep = (unsigned)((int64_t)8 * ldc * 4);
-#pragma unroll
-  for (int h = 0; h < B3_WB_NCH; ++h) vc[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rC, voff, (unsigned)h * rstep, B3_C_AUX));
+  vc[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rC, voff, (unsigned)h * rstep, B3_C_AUX));
 }
 template <class S, int MODE, bool PLANES, bool PRE = false>
 __device__ __forceinline__ void b3_writeback(const Acc<float> &acc, float *Cg, int64_t ldc, float *smem, int tid, bool live,

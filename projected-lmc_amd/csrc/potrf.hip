@@ -463,13 +463,13 @@ __global__ __launch_bounds__(B3_NT, 2) void k_update_bf3(float *A, int64_t lda, 
   const int tid = (int)threadIdx.x & 255;
   // the C rows of the first write-back pass are requested two stages before the main loop ends (nothing for a first touch)
   f32x4 vc0[B3_WB_NCH];
-  auto pre = [&]() { b3_preload(vc0, C, ldc, tid, live && !first); };
+  auto pre = [&](int h) { b3_preload(vc0, C, ldc, tid, live && !first, h); };
   // B operand: the column's planes of the group's rows -- U / augmented columns in the rolling buffer, inverse-factor columns in
   // the full-height planes of W (global row index, n_pad columns per plane row)
   const unsigned short *Bp = Pr + colp * 8;
   int64_t ldb = lda;
   if (bx >= cm.nU + cm.Taug) { Bp = Wk + (int64_t)lat * wk_lat_stride + b3_index<S>(kr0, 0, col0, cm.n_pad); ldb = cm.n_pad; }
-  b3_mainloop<S, 2, B3_WB_NCH>(acc0, acc1, Pr + (int64_t)ibm * NB * 8, lda, Bp, ldb, depth, lds, pre);
+  b3_mainloop<S, B3_WB_NCH>(acc0, acc1, Pr + (int64_t)ibm * NB * 8, lda, Bp, ldb, depth, lds, pre);
   b3_combine<S>(acc0, acc1, 1.0f / (scl[SC_SU] * sB));
   if (Praw && ibm < raw_end) {              // uniform per workgroup; a half at or beyond raw_end writes no planes
     unsigned short *Pp = Praw + (int64_t)lat * praw_lat_stride + b3_index<S>((int64_t)(ibm + half - ib0) * NB, 0, colp, lda);

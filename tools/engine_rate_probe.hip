@@ -1,6 +1,7 @@
 // engine_rate_probe.hip -- where does a macro tile of the split engine (bf3_engine.hpp) spend its time?
 //
 //   hipcc -O3 --offload-arch=gfx950 -o tools/bin/engine_rate_probe tools/engine_rate_probe.hip && tools/bin/engine_rate_probe
+//   ... -DPLMC_STAGE_STAMPS -o tools/bin/engine_rate_stamps: the per-wave cycle budget of a stage instead (run_stamps below)
 //
 // The SHIPPED main loop (b3_mainloop<SplitH2>) on grids that are whole multiples of the 256 CUs (no quantisation), at depths
 // K = 256 .. 8192 and with three epilogues (none: one store per lane; WB_STORE; WB_SUB = the read-modify-write of the tail
@@ -61,13 +62,13 @@ __global__ __launch_bounds__(B3_NT, 2) void k_rate(const unsigned short *__restr
 
 
 // ---- the tail update's real shape: per latent a 1024-row panel of `ld` columns (planes), 24 macro rows x (48 triangular
-// + 17 full) tile columns, C read-modify-write.  ORDER 0: the shipped grid (column fastest, then macro row, then latent);
+// + 17 full) tile columns, C read-modify-write; the stage count is the engine's (b3_nstages: a ring of three for SplitH2).  ORDER 0: the shipped grid (column fastest, then macro row, then latent);
 // ORDER 1 / 2: one-dimensional grid per latent, workgroup t -> XCD t % 8 gets whole blocks of BR x BC macro tiles (its 32
 // resident workgroups share BR A strips and BC B strips), blocks dealt round-robin to the XCDs along the rows.
-template <class S, int NSTG, int ORDER, int BR, int BC, int EPI = 2>
+template <class S, int ORDER, int BR, int BC, int EPI = 2>
 __global__ __launch_bounds__(B3_NT, 2) void k_tail(const unsigned short *__restrict__ P, int64_t pstride, float *C, int64_t cstride, int64_t ld, int K,
                                                     int mrows, int nU, int nF, int tri = 1) {
-  __shared__ __align__(16) unsigned char lds[NSTG * b3_stage_bytes<S>()];
+  __shared__ __align__(16) unsigned char lds[b3_lds_bytes<S>()];
   const int tcols = nU + nF;
   int mb, jb;
   if (ORDER == 0) { jb = blockIdx.x; mb = blockIdx.y; }
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(B3_NT, 2) void k_tail(const unsigned short *__restr
   Acc<float> acc0, acc1;
   acc0.zero();
   acc1.zero();
-  b3_mainloop<S, NSTG>(acc0, acc1, Pl + (int64_t)mb * 256 * 8, ld, Pl + (int64_t)jb * NB * 8, ld, K, lds);
+  b3_mainloop<S>(acc0, acc1, Pl + (int64_t)mb * 256 * 8, ld, Pl + (int64_t)jb * NB * 8, ld, K, lds);
   b3_combine<S>(acc0, acc1, 1.0f / 1048576.0f);
   const int tid = threadIdx.x & 255, half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);
   float *Cg = C + (int64_t)lat * cstride + ((int64_t)mb * 256 + half * 128) * ld + (int64_t)jb * NB;
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(B3_NT, 2) void k_tail(const unsigned short *__restr
   }
 }
 
-template <class S, int NSTG, int ORDER, int BR, int BC, int EPI = 2>
+template <class S, int ORDER, int BR, int BC, int EPI = 2>
 int run_tail_one(const char *name, const unsigned short *P, int64_t pstride, float *C, int64_t cstride, int64_t ld, int K, int mrows, int nU, int nF, int q) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -118,7 +119,7 @@ int run_tail_one(const char *name, const unsigned short *P, int64_t pstride, flo
     const int nb = ((tcols + BC - 1) / BC) * ((mrows + BR - 1) / BR);
     grid = dim3(8 * ((nb + 7) / 8) * BR * BC, 1, q);
   }
-  auto launch = [&]() { hipLaunchKernelGGL((k_tail<S, NSTG, ORDER, BR, BC, EPI>), grid, dim3(B3_NT), 0, 0, P, pstride, C, cstride, ld, K, mrows, nU, nF); };
+  auto launch = [&]() { hipLaunchKernelGGL((k_tail<S, ORDER, BR, BC, EPI>), grid, dim3(B3_NT), 0, 0, P, pstride, C, cstride, ld, K, mrows, nU, nF); };
   for (int w = 0; w < 2; ++w) launch();
   float ms = 0.f;
   const int reps = 5;
@@ -159,7 +160,7 @@ int run_shapes() {
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     const dim3 grid(sh.nu + sh.nf, sh.mr, sh.q);
-    auto launch = [&]() { hipLaunchKernelGGL((k_tail<S, 2, 0, 1, 1, 0>), grid, dim3(B3_NT), 0, 0, P, pstride, C, cstride, ld, K, sh.mr, sh.nu, sh.nf, sh.tri); };
+    auto launch = [&]() { hipLaunchKernelGGL((k_tail<S, 0, 1, 1, 0>), grid, dim3(B3_NT), 0, 0, P, pstride, C, cstride, ld, K, sh.mr, sh.nu, sh.nf, sh.tri); };
     for (int w = 0; w < 3; ++w) launch();
     float ms = 0.f;
     CK(hipEventRecord(e0));
@@ -194,17 +195,13 @@ int run_tail() {
   printf("tail shape: %d latents x (%d macro rows x (%d triangular + %d full) tile columns), depth %d, planes %.0f MB + C %.0f MB per latent\n", Q, MR, NU, NF,
          K, pstride * 2 / 1e6, cstride * 4 / 1e6);
   for (int rep = 0; rep < 2; ++rep) {
-    if (run_tail_one<S, 2, 0, 1, 1, 0>("shipped order, 2 stages, NO epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 2, 0, 1, 1, 1>("shipped order, 2 stages, store-only epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 3, 1, 4, 8, 0>("XCD blocks 4 x 8, 3 stages, NO epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 2, 0, 1, 1>("shipped order, 2 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 3, 0, 1, 1>("shipped order, 3 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 2, 1, 4, 8>("XCD blocks 4 x 8, 2 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 3, 1, 4, 8>("XCD blocks 4 x 8, 3 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 2, 1, 2, 16>("XCD blocks 2 x 16, 2 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 3, 1, 2, 16>("XCD blocks 2 x 16, 3 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 2, 1, 8, 4>("XCD blocks 8 x 4, 2 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
-    if (run_tail_one<S, 3, 1, 8, 4>("XCD blocks 8 x 4, 3 stages", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 0, 1, 1, 0>("shipped order, NO epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 0, 1, 1, 1>("shipped order, store-only epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 1, 4, 8, 0>("XCD blocks 4 x 8, NO epilogue", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 0, 1, 1>("shipped order", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 1, 4, 8>("XCD blocks 4 x 8", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 1, 2, 16>("XCD blocks 2 x 16", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
+    if (run_tail_one<S, 1, 8, 4>("XCD blocks 8 x 4", P, pstride, C, cstride, ld, K, MR, NU, NF, Q)) return 1;
   }
   CK(hipFree(P));
   CK(hipFree(C));
@@ -263,7 +260,71 @@ template <class S> int run(const char *name, int products) {
   return 0;
 }
 
+#ifdef PLMC_STAGE_STAMPS
+// Stage budget from the stamps of bf3_engine.hpp (build with -DPLMC_STAGE_STAMPS): cycles of s_memtime between the points of the
+// last steady-state stage, waves 0 and 4 (one SIMD) of the first workgroups, (a) the K sweep's L2-resident shape, (b) the
+// tail's shape at q = 8 without epilogue.
+int print_stamps(const char *what, unsigned long long *dbuf) {
+  unsigned long long h[16 * 8 * 8];
+  CK(hipMemcpy(h, dbuf, sizeof(h), hipMemcpyDeviceToHost));
+  printf("%s\n  wg wave | exit->1st MFMA pair | ->last DMA issue | ->last MFMA | ->wait reached | ->wait done | ->next exit || stage\n", what);
+  for (int g = 0; g < 16; g += 5)
+    for (int w = 0; w < 8; w += 4) {
+      const unsigned long long *t = h + (g * 8 + w) * 8;
+      if (t[1]) printf("  %2d  %d   | %6lld | %6lld | %6lld | %6lld | %6lld | %6lld || %6lld\n", g, w, (long long)(t[1] - t[0]), (long long)(t[2] - t[1]),
+                       (long long)(t[3] - t[2]), (long long)(t[4] - t[3]), (long long)(t[5] - t[4]), (long long)(t[6] - t[5]), (long long)(t[6] - t[0]));
+      else printf("  %2d  %d   | exit->last MFMA %6lld | ->next exit %6lld || stage %6lld\n", g, w, (long long)(t[3] - t[0]), (long long)(t[6] - t[3]),
+                  (long long)(t[6] - t[0]));
+    }
+  return 0;
+}
+template <class S> int run_stamps(const char *name) {
+  unsigned long long *dbuf = nullptr;
+  CK(hipMalloc(&dbuf, 16 * 8 * 8 * 8));
+  CK(hipMemset(dbuf, 0, 16 * 8 * 8 * 8));
+  CK(hipMemcpyToSymbol(HIP_SYMBOL(plmc_b3_stamps), &dbuf, sizeof(dbuf)));
+  {
+    const int MR = 16, TC = 32, K = 1024;
+    const int64_t ld = (int64_t)(2 * MR + TC) * NB + 128;
+    unsigned short *P = nullptr;
+    float *C = nullptr;
+    CK(hipMalloc(&P, (size_t)b3_elems<S>(K, ld) * 2));
+    CK(hipMalloc(&C, (size_t)MR * 256 * ld * 4));
+    hipLaunchKernelGGL((k_fill<S>), dim3((unsigned)((ld + NTHREADS - 1) / NTHREADS), K / 8), dim3(NTHREADS), 0, 0, P, ld, K, 12345u);
+    for (int r = 0; r < 4; ++r) hipLaunchKernelGGL((k_rate<S, 0>), dim3(512), dim3(B3_NT), 0, 0, P, C, ld, K, MR, TC);
+    CK(hipDeviceSynchronize());
+    printf("%s\n", name);
+    if (print_stamps("L2-resident operands (16 x 32 tiles, depth 1024, grid 512)", dbuf)) return 1;
+    CK(hipFree(P));
+    CK(hipFree(C));
+  }
+  {
+    const int K = 1024, MR = 24, NU = 48, NF = 17, Q = 8;
+    const int64_t ld = (int64_t)(NU + NF) * NB + 128;
+    const int64_t pstride = b3_elems<S>(K, ld), cstride = (int64_t)MR * 256 * ld;
+    unsigned short *P = nullptr;
+    float *C = nullptr;
+    CK(hipMalloc(&P, (size_t)pstride * Q * 2));
+    CK(hipMalloc(&C, (size_t)cstride * Q * 4));
+    for (int l = 0; l < Q; ++l)
+      hipLaunchKernelGGL((k_fill<S>), dim3((unsigned)((ld + NTHREADS - 1) / NTHREADS), K / 8), dim3(NTHREADS), 0, 0, P + (int64_t)l * pstride, ld, K, 777u + l);
+    // the stamped workgroups (blockIdx.y == z == 0) are the first in the grid: launch twice so that they start beside a full chip
+    for (int r = 0; r < 3; ++r) hipLaunchKernelGGL((k_tail<S, 0, 1, 1, 0>), dim3(NU + NF, MR, Q), dim3(B3_NT), 0, 0, P, pstride, C, cstride, ld, K, MR, NU, NF, 1);
+    CK(hipDeviceSynchronize());
+    if (print_stamps("the tail's shape, q = 8, no epilogue", dbuf)) return 1;
+    CK(hipFree(P));
+    CK(hipFree(C));
+  }
+  CK(hipFree(dbuf));
+  return 0;
+}
+#endif
+
 int main(int argc, char **argv) {
+#ifdef PLMC_STAGE_STAMPS
+  if (run_stamps<SplitH2>("SplitH2 stage stamps")) return 1;
+  return run_stamps<SplitB3>("SplitB3 stage stamps");
+#endif
   if (argc > 1 && argv[1][0] == 's') return run_shapes();
   if (run_tail()) return 1;
   if (argc < 2) return 0;                                    // any argument: also the K sweep of the bare loop
