@@ -467,6 +467,64 @@ int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64
                               int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
 
 /*
+ * Rational-quadratic kernel [gpytorch-knowledge: RQKernel, unverified offline] on the batched exact engine:
+ *     Khat_i = os[i] (1 + r^2 / (2 alpha[i]))^(-alpha[i]) + noise[i] I,   r^2 = sum_k ((x_k - x'_k) / ell[i][k])^2,
+ *     1 <= d <= plmc_rq_max_dim().  Exceeding the limit, d <= 0 or a null `alpha` is an argument error (plmc_last_error()); nothing is
+ *     launched.
+ * Table, per latent i:  lengthscales ell (q x d, contiguous), alpha (q) > 0, output scale os (q) or NULL (all ones).  noise: q.
+ * Every entry point takes the arguments of its periodic form with (ell, period) replaced by (ell, alpha) and does what that form does:
+ *   plmc_assemble_rq_*        plmc_assemble_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_rq_*  plmc_assemble_cross_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_rq_ex_*    plmc_factorize_ex_*    (assembly overlapped with the sweep; bit-identical to plmc_assemble_rq_* followed
+ *                                                     by plmc_potrf_ex_*)
+ *   plmc_kinv_grad_rq_vd_*    plmc_kinv_grad_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ *   plmc_loo_grad_rq_*        plmc_loo_grad_*        (the gradient table of the leave-one-out objective, below)
+ * The value is exp(-alpha log1p(u)), u = r^2 fl(1 / (2 alpha)), with r^2 from the raw differences x - x' scaled by 1 / ell: the fp32
+ * assembly is within (d + 8) 2^-24 os of the fp64 formula at the fp32 inputs per element WHATEVER alpha is (pow(1 + u, -alpha) loses
+ * alpha 2^-24).  The diagonal is os + noise with one rounding, a coincident pair off the diagonal gives exactly os.
+ * Gradient table of plmc_kinv_grad_rq_vd_* and plmc_loo_grad_rq_* (double), d + 3 entries per latent:
+ *     grad[latent] = [ d logp / d ell: d | d / d alpha | d / d noise | d / d os ]
+ *   d k / d alpha = -k h(u), h(u) = log1p(u) - u / (1 + u), evaluated without cancellation (a series below u = 1/8).  The diagonal
+ *   (u = 0) contributes to noise and os only.
+ *   plmc_kinv_grad_rq_vd_f32 with d = 1 follows PLMC_SPLIT like every other kernel.  With d > 1 it follows the knob where that selects
+ *   the two fp16 planes (the default with eig_lo given); where the three bf16 planes would run (PLMC_SPLIT=3, or no eig_lo) it forms
+ *   K^-1 with the fp32 matrix instructions instead (the knob and eig_lo are not looked at; no planes of W are needed).
+ * Scratch.  `Vd`: as for plmc_kinv_grad_vd_*.  `partials`: plmc_grad_partials_bytes(n_pad, q) bytes, one row of partial sums per tile.
+ *   The fp32 split engine takes the planes of W from the Vd of the sweep that produced W and refuses a call without them; fp64 and
+ *   PLMC_SPLIT=0 need no planes.
+ */
+int plmc_rq_max_dim(void);                    /* largest input dimension of a rational-quadratic kernel (16) */
+int plmc_assemble_rq_f32(const float *X, int n, int d, const float *ell, const float *alpha, const float *oscale, const float *noise,
+                         float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_rq_f64(const double *X, int n, int d, const double *ell, const double *alpha, const double *oscale, const double *noise,
+                         double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_rq_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *alpha,
+                               const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream);
+int plmc_assemble_cross_rq_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *alpha,
+                               const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                               void *stream);
+int plmc_factorize_rq_ex_f32(const float *X, int n, int d, const float *ell, const float *alpha, const float *oscale, const float *noise,
+                             float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                             int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_rq_ex_f64(const double *X, int n, int d, const double *ell, const double *alpha, const double *oscale, const double *noise,
+                             double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
+                             int with_inverse, int q, const double *eig_lo, void *stream);
+/* (`shape` is the kernel's alpha; `alpha` is Khat^-1 y, as in every plmc_kinv_grad* call) */
+int plmc_kinv_grad_rq_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                             const float *ell, const float *shape, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_rq_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                             const double *ell, const double *shape, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+int plmc_loo_grad_rq_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                         int n, int d, const float *ell, const float *alpha, const float *oscale, double *grad, void *partials, int q,
+                         void *stream);
+int plmc_loo_grad_rq_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                         int n, int d, const double *ell, const double *alpha, const double *oscale, double *grad, void *partials, int q,
+                         void *stream);
+
+/*
  * Leave-one-out objective (LeaveOneOutPseudoLikelihood, projected_lmc.py:86-105): with P = Khat^-1, alpha = P y, p_i = P_ii,
  *     L = sum_i [ 1/2 log p_i - 1/2 alpha_i^2 / p_i ] - n/2 log 2 pi,
  *     c_i = 1/2 / p_i + 1/2 alpha_i^2 / p_i^2,   g_i = -alpha_i / p_i,   u = P g = dL / dy,

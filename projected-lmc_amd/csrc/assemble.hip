@@ -413,7 +413,48 @@ template <typename T, int DCAP> struct PerTable {
   }
 };
 
-// d <= 8 (DCAP in {4, 8}; spectral mixture and periodic also 1); P: AddTable / SmTable / PerTable
+// The rational-quadratic table (covariance.hpp): per latent lengthscales (d), alpha, output scale | null.  In LDS: w = 1 / ell [DCAP]
+// (0 beyond d: that dimension adds exactly 0 to r^2), alpha, 1 / (2 alpha), os.
+template <typename T, int DCAP> struct RqPairValue {
+  const T *w;
+  T alpha, i2a, os;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    typedef Pair<T> T2;
+    T2 r2 = {T(0), T(0)};
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      const T2 sd = (xr[k] - xc[k]) * w[k];
+      r2 += sd * sd;
+    }
+    return os * T2{rq_profile(r2.x, alpha, i2a), rq_profile(r2.y, alpha, i2a)};
+  }
+};
+template <typename T, int DCAP> struct RqTable {
+  static constexpr int LDS = DCAP + 3;
+  const T *ell, *alpha, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < DCAP) par[tid] = tid < d ? T(1) / ell[(int64_t)lat * d + tid] : T(0);
+    if (tid == 0) {
+      const T a = alpha[lat];
+      par[DCAP] = a;
+      par[DCAP + 1] = T(0.5) / a;
+      par[DCAP + 2] = oscale ? oscale[lat] : T(1);
+    }
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, RqPairValue<T, DCAP>{par, par[DCAP], par[DCAP + 1], par[DCAP + 2]}, nz, Al, lda, ib, jb, n, edge);
+  }
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T a[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) a[k] = xa[k];
+    return par[DCAP + 2] * rq_value<T, DCAP>(a, xs, par, par[DCAP], par[DCAP + 1]);
+  }
+};
+
+// d <= 8 (DCAP in {4, 8}; spectral mixture, periodic and rational quadratic also 1; rational quadratic also 16); P: AddTable / SmTable / PerTable / RqTable
 template <typename T, int DCAP, class P>
 __global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
                                                                     const T *__restrict__ noise, T *__restrict__ A,
@@ -532,7 +573,7 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross_table(const P prm, 
   }
 }
 
-// One launch of a table kernel: P<T, DC> is AddTable / SmTable / PerTable, `args` what follows the table in the kernel's signature
+// One launch of a table kernel: P<T, DC> is AddTable / SmTable / PerTable / RqTable, `args` what follows the table in the kernel's signature
 template <typename T, int DC, template <typename, int> class P, class... Args>
 void launch_small_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... args) {
   hipLaunchKernelGGL((k_assemble_small_table<T, DC, P<T, DC>>), grid, dim3(NTHREADS), 0, st, prm, args...);
@@ -545,6 +586,7 @@ void launch_cross_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... 
 template <typename T, int DC> AddTable<T, DC> add_table(const CovTable &t) { return {t.kind, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
 template <typename T, int DC> SmTable<T, DC> sm_table(const CovTable &t) { return {t.ncomp, (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
 template <typename T, int DC> PerTable<T, DC> per_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
+template <typename T, int DC> RqTable<T, DC> rq_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
 
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
@@ -554,7 +596,7 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
   PLMC_REQUIRE_TABLE(t);
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
-  const bool small_only = t.family == COV_SM || t.family == COV_PER;       // d <= 8 by the family's limit
+  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ;       // d <= 8 (rational quadratic: 16) by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
   PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
@@ -597,6 +639,12 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
       if (d == 1) table(per_table<T, 1>(t));
       else if (d <= 4) table(per_table<T, 4>(t));
       else table(per_table<T, 8>(t));
+      break;
+    case COV_RQ:
+      if (d == 1) table(rq_table<T, 1>(t));
+      else if (d <= 4) table(rq_table<T, 4>(t));
+      else if (d <= 8) table(rq_table<T, 8>(t));
+      else table(rq_table<T, 16>(t));
       break;
   }
   return launch_status(__func__);
@@ -659,6 +707,12 @@ int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int n
       if (d == 1) table(per_table<T, 1>(t));
       else if (d <= 4) table(per_table<T, 4>(t));
       else table(per_table<T, 8>(t));
+      break;
+    case COV_RQ:
+      if (d == 1) table(rq_table<T, 1>(t));
+      else if (d <= 4) table(rq_table<T, 4>(t));
+      else if (d <= 8) table(rq_table<T, 8>(t));
+      else table(rq_table<T, 16>(t));
       break;
   }
   return launch_status(__func__);
@@ -743,6 +797,19 @@ int plmc_assemble_cross_per_f64(const double *X, int n, const double *Xs, int ns
                                 void *stream) {
   return plmc::assemble_cross_impl<double>(CovTable::per(d, ell, period, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
 }
+int plmc_rq_max_dim(void) { return plmc::RQ_MAX_DIM; }
+#define PLMC_RQ_ENTRY(SUF, T)                                                                                                                  \
+  int plmc_assemble_rq_##SUF(const T *X, int n, int d, const T *ell, const T *alpha, const T *oscale, const T *noise, T *A, int64_t lda,       \
+                             int64_t strideA, int q, void *stream) {                                                                           \
+    return plmc::assemble_impl<T>(CovTable::rq(d, ell, alpha, oscale), X, n, noise, A, lda, strideA, q, stream);                               \
+  }                                                                                                                                            \
+  int plmc_assemble_cross_rq_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *alpha, const T *oscale, T *Out,       \
+                                   int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                          \
+    return plmc::assemble_cross_impl<T>(CovTable::rq(d, ell, alpha, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);        \
+  }
+PLMC_RQ_ENTRY(f32, float)
+PLMC_RQ_ENTRY(f64, double)
+#undef PLMC_RQ_ENTRY
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
   return plmc::assemble_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);

@@ -210,6 +210,50 @@ __device__ __forceinline__ T per_value(const T (&a)[DCAP], const T (&b)[DCAP], c
   }
   return dexp(T(-2) * e);
 }
+
+// ---- rational quadratic [gpytorch-knowledge: RQKernel, unverified offline]:
+//     k(x, x') = (1 + r^2 / (2 alpha))^(-alpha),   r^2 = sum_k ((x_k - x'_k) / ell_k)^2,   alpha > 0 one scalar per latent.
+// The value is exp(-alpha log1p(u)), u = r^2 fl(1 / (2 alpha)): pow(1 + u, -alpha) and log(1 + u) lose the low bits of u in the sum
+// 1 + u, which alpha then multiplies (alpha 2^-24 absolute in fp32; a trained alpha is 10^3 .. 10^6 when the data are RBF-like).  With the
+// library's log1p (accurate at small u) the exponent a = alpha log1p(u) <= r^2 / 2 carries a few ulp RELATIVE whatever alpha is
+// ("Rational-quadratic kernel: fp32 numerics").  u = 0 gives exactly 1.
+__device__ __forceinline__ float  rq_log1p(float u) { return log1pf(u); }
+__device__ __forceinline__ double rq_log1p(double u) { return log1p(u); }
+__device__ __forceinline__ float  rq_rcp(float x) { return __builtin_amdgcn_rcpf(x); }        // 1 ulp; weights a reduction only
+__device__ __forceinline__ double rq_rcp(double x) { return 1.0 / x; }
+template <typename T> __device__ __forceinline__ T rq_profile(T r2, T alpha, T i2a) { return dexp(-alpha * rq_log1p(r2 * i2a)); }
+// h(u) = log1p(u) - u / (1 + u) >= 0, the factor of d k / d alpha = -k h(u); h ~ u^2 / 2, and the two terms agree to u / 2 of their
+// size.  Below u = 1/8 the series sum_{k >= 2} (-1)^k (k - 1) / k u^k, through u^9 (fp32) / u^19 (fp64): the first term left out is
+// below 1.9 u^(K - 1) of h, i.e. 1.9 2^-24 / 1.9 2^-54.  From 1/8 on the direct form from `l1p` = log1p(u) and `rc` = 1 / (1 + u): its two
+// terms carry ~5 roundings of size u, h >= 0.43 u^2 there, so <= ~12 / u <= 96 roundings = 48 ulp relative.
+template <typename T> __device__ __forceinline__ T rq_h(T u, T l1p, T rc) {
+  constexpr int KMAX = sizeof(T) == 4 ? 9 : 19;
+  T p = T((KMAX & 1 ? -1.0 : 1.0) * (KMAX - 1) / KMAX);
+#pragma unroll
+  for (int k = KMAX - 1; k >= 2; --k) p = __builtin_fma(p, u, T((k & 1 ? -1.0 : 1.0) * (k - 1) / k));
+  return u < T(0.125) ? p * (u * u) : __builtin_fma(-u, rc, l1p);
+}
+// gradient epilogue: value, base = val / (1 + u) (d k / d ell_k = base df_k^2 / ell_k, the library's convention) and val h(u), unit
+// output scale.  The accurate exponential here too: d / d alpha at large alpha is a sum of terms ~ u^2 that the error of __expf
+// (|a| 2^-24) would be weighed against.
+template <typename T> __device__ __forceinline__ void rq_value_base_h(T r2, T alpha, T i2a, T &val, T &base, T &vh) {
+  const T u = r2 * i2a, l1p = rq_log1p(u), rc = rq_rcp(T(1) + u);
+  val = dexp(-alpha * l1p);
+  base = val * rc;
+  vh = val * rq_h(u, l1p, rc);
+}
+// one covariance value (unit output scale): rows of DCAP raw coordinates a, b; w = 1 / ell [DCAP] (0 beyond d).  The difference is
+// taken from the RAW inputs and then scaled (k_kernel_vjp_add): no |x| / ell term in the error, exactly 0 at coincident points.
+template <typename T, int DCAP>
+__device__ __forceinline__ T rq_value(const T (&a)[DCAP], const T (&b)[DCAP], const T *w, T alpha, T i2a) {
+  T r2 = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    const T sd = (a[k] - b[k]) * w[k];
+    r2 += sd * sd;
+  }
+  return rq_profile(r2, alpha, i2a);
+}
 #undef dexp
 #undef dsqrt
 

@@ -244,6 +244,8 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // oscale = its weights, `means` its means; `kind` is not looked at.
 // COV_PER: a periodic kernel of up to DC input dimensions (kinv_epilogue_per.inc): ell = its lengthscales, `means` its periods, oscale (q)
 // or null; `kind` and ncomp (1) are not looked at.
+// COV_RQ: a rational-quadratic kernel of up to DC (1, 4, 8, 16) input dimensions (kinv_epilogue_rq.inc): ell = its lengthscales, `means` its alpha (q),
+// oscale (q) or null; `kind` and ncomp (1) are not looked at.
 template <typename T, CovFamily F, int DC>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
@@ -254,7 +256,7 @@ __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *sme
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
@@ -375,6 +377,23 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_per(const double *__rest
   }
 }
 
+// The reduction for the rational-quadratic kernel: one row of GP slots per tile (kinv_epilogue_rq.inc).  grid (q).
+// grad[lat]: [ d/d ell (d) | d/d alpha | d/d noise | d/d oscale ], with the factor 1 / ell_k and the sign of d/d alpha the epilogue left out.
+template <typename T>
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_rq(const double *__restrict__ partials, int m, int d, const T *__restrict__ ell,
+                                                           double *__restrict__ grad) {
+  PLMC_REDUCE_TILES(GP, 0);
+  if (threadIdx.x < GP) {
+    const double tot = reduce_slot_total(red);
+    const int k = threadIdx.x;
+    double *gl = grad + (int64_t)lat * (d + 3);
+    if (k < d) gl[k] = 0.5 * tot / (double)ell[(int64_t)lat * d + k];
+    else if (k == RQ_MAX_DIM) gl[d] = -0.5 * tot;
+    else if (k == MAX_DIM) gl[d + 1] = 0.5 * tot;
+    else if (k == MAX_DIM + 1) gl[d + 2] = 0.5 * tot;
+  }
+}
+
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -432,9 +451,10 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
-      PLMC_REQUIRE(family != COV_PER && family != COV_SM,
-                   family == COV_PER ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                                     : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
+      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ,
+                   family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                   : family == COV_RQ ? "the rational-quadratic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                                      : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * rows * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
       float *wsco = reinterpret_cast<float *>(pb + (int64_t)q * b3_elems<SplitB3>(n_pad, n_pad) * 2);
@@ -457,6 +477,13 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     switch (family) {
       case COV_PER: PLMC_LAUNCH_TB(COV_PER, 1); break;     // (d = 1 only: kinv_grad_f32_any)
+      case COV_RQ:                                         // (three planes: d = 1 only, kinv_grad_f32_any -- DC = 4 / 8 would spill there)
+        if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_RQ, 1);
+        else if (d == 1) PLMC_LAUNCH_TB(COV_RQ, 1);
+        else if (d <= 4) PLMC_LAUNCH_TB(COV_RQ, 4);
+        else if (d <= 8) PLMC_LAUNCH_TB(COV_RQ, 8);
+        else PLMC_LAUNCH_TB(COV_RQ, 16);
+        break;
       case COV_SM: PLMC_LAUNCH_TB(COV_SM, 1); break;       // (d = 1 only: kinv_grad_f32_any)
       case COV_ADD: PLMC_LAUNCH_TB(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -478,6 +505,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_TG(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_PER, 4); else PLMC_LAUNCH_TG(COV_PER, 8); break;
+      case COV_RQ: if (d == 1) PLMC_LAUNCH_TG(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_RQ, 8); else PLMC_LAUNCH_TG(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -493,6 +521,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
@@ -541,7 +570,7 @@ __global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
     int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
     const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
     const T *__restrict__ means) {
@@ -631,6 +660,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * (double)krows, q * np * (double)krows * sizeof(T));
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_LT(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_PER, 4); else PLMC_LAUNCH_LT(COV_PER, 8); break;
+      case COV_RQ: if (d == 1) PLMC_LAUNCH_LT(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_RQ, 8); else PLMC_LAUNCH_LT(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -646,6 +676,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
@@ -694,8 +725,11 @@ static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_
   // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
   // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
   // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel keeps d sines, cosine
-  // complements and 2 d sums live and follows the same rule.
-  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER) && table.d > 1))
+  // complements and 2 d sums live and follows the same rule.  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
+  // every d; beside the three bf16 planes (PLMC_SPLIT=3, or no eig_lo) it fits at d = 1 only, so d > 1 takes the fp32 products there.
+  const bool three_planes = !(split == 2 && eig_lo);
+  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER) && table.d > 1) ||
+      (table.family == plmc::COV_RQ && table.d > 1 && three_planes))
     return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
@@ -795,6 +829,22 @@ int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64
   return kinv_grad_f64(CovTable::per(d, ell, period, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
                        stream);
 }
+// rational-quadratic kernel: plmc_kinv_grad_vd_* with the table (lengthscales, alpha, output scale) (include/plmc.h); `partials` is sized
+// by plmc_grad_partials_bytes.  (`shape` is the kernel's alpha; `alpha` is K^-1 y as everywhere in this file)
+int plmc_kinv_grad_rq_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                             const float *ell, const float *shape, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
+  return kinv_grad_f32_any(CovTable::rq(d, ell, shape, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                           eig_lo, stream, Vd);
+}
+int plmc_kinv_grad_rq_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                             const double *ell, const double *shape, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  return kinv_grad_f64(CovTable::rq(d, ell, shape, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                       stream);
+}
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
@@ -827,6 +877,10 @@ int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
   int plmc_loo_grad_per_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
                               int d, const T *ell, const T *period, const T *oscale, double *grad, void *partials, int q, void *stream) {      \
     return plmc::loo_grad_impl<T>(CovTable::per(d, ell, period, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
+  }                                                                                                                                             \
+  int plmc_loo_grad_rq_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,        \
+                             int d, const T *ell, const T *alpha, const T *oscale, double *grad, void *partials, int q, void *stream) {         \
+    return plmc::loo_grad_impl<T>(CovTable::rq(d, ell, alpha, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);  \
   }                                                                                                                                             \
   int plmc_loo_operand_##SUF(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *rowscale, T *Xop, int64_t krows, int64_t ldx, \
                              int64_t strideX, int n, int q, void *stream) {                                                                    \

@@ -137,7 +137,15 @@ def _contig(t, dtype=None):
 # (q) | None; it goes to the `_per` entry points, which take no kind and (ell, period) in the place of ell (include/plmc.h, "Periodic
 # kernel").  Its table has the rank of an additive one, so the functions that size things take the kind beside it.  The gradient table
 # [d lengthscales | d periods | d noise | d oscale] splits like the others.
+# Kind "rq" (kernels.RQKernel): `ell` is its table (q, d + 1) = [lengthscales | alpha], `oscale` (q) | None; it goes to the `_rq` entry
+# points, which take no kind and (ell, alpha) in the place of ell (include/plmc.h, "Rational-quadratic kernel").  Its table has the rank of
+# a plain one, so what reads the input dimension off the table takes the kind beside it.  The gradient table [d lengthscales | d alpha |
+# d noise | d oscale] splits like the others: its first d + 1 entries are the gradient of the table.
 PER = "periodic"
+RQ = "rq"
+_RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
+       "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
+       "plmc_loo_grad": "plmc_loo_grad_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
         "plmc_loo_grad": "plmc_loo_grad_per"}
@@ -160,20 +168,27 @@ def n_components(ell, kind=None):
 
 
 def kind_code(kind):
-    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic kernel
-    likewise: its name stands in the code's place and sends _kernel_call to them."""
-    return None if kind == "sm" else (PER if kind == PER else _hip.KIND[kind])
+    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic and the
+    rational-quadratic kernel likewise: their name stands in the code's place and sends _kernel_call to them."""
+    return None if kind == "sm" else (kind if kind in (PER, RQ) else _hip.KIND[kind])
 
 
 def grad_table_width(ell, kind=None):
     """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)];
     spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights];
-    periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale]."""
+    periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale];
+    rational quadratic: ell[0] is (d + 1), [d/d lengthscales | d/d alpha | d/d noise | d/d oscale]."""
     return ell[0].numel() + 1 + n_components(ell, kind)
 
 
 def _check_kernel_shape(L, ell, kind=None):
-    d = ell.shape[-1]
+    d = ell.shape[-1] - (1 if kind == RQ else 0)
+    if kind == RQ:
+        if ell.dim() != 2 or d < 1:
+            raise ValueError("a rational-quadratic kernel's table is (q, d + 1) = [lengthscales | alpha]")
+        if d > L.cdll.plmc_rq_max_dim():
+            raise ValueError("rational-quadratic kernel on %d dimensions exceeds plmc_rq_max_dim()=%d" % (d, L.cdll.plmc_rq_max_dim()))
+        return
     if d > L.cdll.plmc_max_dim():
         raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
     if kind == PER:
@@ -191,8 +206,19 @@ def _check_kernel_shape(L, ell, kind=None):
 
 def _kernel_call(L, base, dt, head, ell, tail, stream=None):
     """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
-    form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER.
+    form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER, or its
+    rational-quadratic form (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ.
     `stream`: the side stream the call is queued on, if not the current one."""
+    if isinstance(head[0], str) and head[0] == RQ:
+        rows = getattr(ell, "_rq_rows", None)                # split once per table, as the periodic kernel's rows below
+        if rows is None:
+            d = ell.shape[1] - 1
+            rows = ell._rq_rows = (ell[:, :d].contiguous(), ell[:, d].contiguous())
+        if stream is not None:
+            rows[0].record_stream(stream)
+            rows[1].record_stream(stream)
+        L.call(_RQ[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), *tail)
+        return
     if isinstance(head[0], str) and head[0] == PER:
         rows = getattr(ell, "_per_rows", None)               # split once per table, as the spectral mixture's planes below
         if rows is None:

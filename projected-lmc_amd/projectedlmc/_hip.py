@@ -26,17 +26,20 @@ _TYPED = {
     "plmc_assemble": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_add": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_per": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    "plmc_assemble_rq": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_sm": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_write_rhs": [_P, _I, _I, _P, _L, _L, _I, _I, _I, _P],
     "plmc_assemble_cross": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "plmc_assemble_cross_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_potrf": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P],
     "plmc_potrf_ex": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_ex": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_add_ex": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_per_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
+    "plmc_factorize_rq_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_sm_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
     "plmc_potrs_aug_kept": [_P, _L, _L, _I, _L, _L, _P, _I, _P, _P],
@@ -50,10 +53,12 @@ _TYPED = {
     "plmc_kinv_grad_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_add_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_per_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
+    "plmc_kinv_grad_rq_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_per": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_rq": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
@@ -81,6 +86,7 @@ _PLAIN = {
     "plmc_sm_grad_partials_bytes": ([_L, _I, _I, _I], _L),
     "plmc_per_max_dim": ([], _I),
     "plmc_per_grad_partials_bytes": ([_L, _I, _I], _L),
+    "plmc_rq_max_dim": ([], _I),
     "plmc_qr_max": ([], _I),
     "plmc_last_error": ([], _c.c_char_p),
     "plmc_grad_scratch_bytes": ([_L, _I], _L),

@@ -198,6 +198,39 @@ class PeriodicKernel(Kernel):
         return self.kind, torch.stack([self._ell(d, like), period], 1), None
 
 
+class RQKernel(Kernel):
+    """Rational-quadratic kernel [gpytorch-knowledge: RQKernel, unverified offline]:
+        k(x, x') = (1 + r^2 / (2 alpha))^(-alpha),   r^2 = sum_k ((x_k - x'_k) / ell_k)^2,
+    the scale mixture of RBF kernels (alpha -> inf: the RBF kernel).  gpytorch's parameter names and shapes, so state dicts line up:
+    raw_lengthscale (*batch, 1, d) and raw_alpha (*batch, 1), zero-initialised, Positive constraints.  On the HIP path it is kernel kind
+    "rq" of the batched exact engine (include/plmc.h, "Rational-quadratic kernel"); the additive kernel, SGPR, the dense LMC / ICM and
+    the variational models refuse it."""
+    has_lengthscale = True
+    kind = "rq"
+    is_stationary = True
+
+    def __init__(self, ard_num_dims=None, batch_shape=torch.Size(), active_dims=None, alpha_constraint=None, lengthscale_prior=None,
+                 lengthscale_constraint=None, **kwargs):
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, active_dims=active_dims,
+                         lengthscale_prior=lengthscale_prior, lengthscale_constraint=lengthscale_constraint, **kwargs)
+        self.register_parameter("raw_alpha", torch.nn.Parameter(torch.zeros(*self.batch_shape, 1)))
+        self.raw_alpha_constraint = alpha_constraint or Positive()
+
+    @property
+    def alpha(self):
+        return self.raw_alpha_constraint.transform(self.raw_alpha)
+
+    @alpha.setter
+    def alpha(self, value):
+        value = torch.as_tensor(value, dtype=self.raw_alpha.dtype, device=self.raw_alpha.device)
+        with torch.no_grad():
+            self.raw_alpha.copy_(self.raw_alpha_constraint.inverse_transform(value).expand_as(self.raw_alpha))
+
+    def _pieces(self, d, like=None):
+        """The table (q, d + 1) = [lengthscales | alpha] and no output scale."""
+        return self.kind, torch.cat([self._ell(d, like), self.alpha.reshape(-1, 1)], 1), None
+
+
 def _refuse(cls, name, kernel, model):
     k = kernel
     while k is not None and not isinstance(k, cls):
@@ -210,6 +243,11 @@ def _refuse(cls, name, kernel, model):
 def refuse_periodic(kernel, model):
     """The periodic kernel runs on the batched exact engine only: name the model that cannot take it."""
     _refuse(PeriodicKernel, "PeriodicKernel", kernel, model)
+
+
+def refuse_rq(kernel, model):
+    """The rational-quadratic kernel runs on the batched exact engine only: name the model that cannot take it."""
+    _refuse(RQKernel, "RQKernel", kernel, model)
 
 
 def refuse_sm(kernel, model):
@@ -261,7 +299,8 @@ class LazyKernel:
     ell (q, d), oscale (q) | None: one ARD kernel per latent.  ell (q, G, d), oscale (q, G): the component table of an additive
     kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there.
     kind "sm": ell (q, 2, M, d) holds the scales and the means of a spectral mixture, oscale (q, M) its weights (`scales`, `means`,
-    `weights`).  kind "periodic": ell (q, 2, d) holds the lengthscales and the periods, oscale (q) | None."""
+    `weights`).  kind "periodic": ell (q, 2, d) holds the lengthscales and the periods, oscale (q) | None.  kind "rq": ell (q, d + 1) holds
+    the lengthscales and, in its last column, alpha; oscale (q) | None."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise

@@ -57,6 +57,7 @@ def handle_covar_(kernel, dim, decomp=None, n_funcs=1, prior_scales=None, prior_
     if len(decomp) > 1:
         _k.refuse_sm(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         _k.refuse_periodic(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
+        _k.refuse_rq(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         # k(x) = sum_g s_g k_g(x[idx_g]): every sub-kernel gets an output scale (:159-162)
         from .additive import AdditiveKernel
         subs = []
@@ -275,6 +276,7 @@ class ExactGPModel(ExactGP):
         if n_inducing_points is not None:
             _k.refuse_sm(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_periodic(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
+            _k.refuse_rq(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             from .sgpr import InducingPointKernel
             self.covar_module = InducingPointKernel(self.covar_module, torch.randn(n_inducing_points, self.dim),
                                                     likelihood)

@@ -25,6 +25,7 @@ class MultitaskGPModel(ExactGPModel):
                  fix_diagonal=False, **kwargs):
         _k.refuse_sm(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_periodic(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
+        _k.refuse_rq(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         super().__init__(train_x, train_y, likelihood, n_tasks=1, outputscales=False, **kwargs)
         self.mean_module = _m.MultitaskMean(self.mean_module, num_tasks=n_tasks)
         base = self.covar_module
