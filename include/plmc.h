@@ -128,6 +128,13 @@ int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, 
  * columns is required.
  * with_inverse with bit 1 set (2, 3, ...) is refused before anything is launched: Khat^-1 and the gradient come from
  * plmc_kinv_grad_* behind the sweep.
+ * The square part after the sweep: U is the ELEMENT-WISE upper triangle (i <= j) of columns [0, n_pad), padded rows i >= n
+ * included -- those hold the identity exactly (1 on the diagonal, 0 right of it), and the padded rows of every augmented column
+ * hold exactly 0.  Everything below the diagonal is unspecified: the 128 x 128 tiles strictly below the block diagonal are neither
+ * read nor written, and the part of a diagonal block below its diagonal is loaded with the block (give it finite values: plmc_assemble_* fills the
+ * whole block symmetrically) and left with whatever the input held -- W_kk, the inverse of a diagonal block, goes to Vd and to the W columns, never there.  W: tiles on
+ * and below the block diagonal are written (zeros above the diagonal inside a diagonal block), the tiles above are never touched.
+ * tests/test_gpu_factor.py pins all of this against an fp64 CPU factorisation.
  */
 #define PLMC_INFO_CHAIN_ABORT 0x7ffffff0
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,

@@ -1,6 +1,6 @@
 """What the host does about a factorisation that may not be positive definite -- once, for every model of the package.
 
-The blocked sweep leaves one `info` word per latent (include/plmc.h): 0, the index of the first failing pivot, or
+The blocked sweep leaves one `info` word per latent (include/plmc.h): 0, 1 + the index of the first failing pivot (tests/test_gpu_factor.py), or
 PLMC_INFO_CHAIN_ABORT.  This module owns the reading of those words (`PivotCheck`, at once or behind the kernels that follow
 the sweep), the context a caller uses to collect the checks of a forward pass it can redo (`deferred_pivot_checks`), and the
 jitter ladder of gpytorch's psd_safe_cholesky [gpytorch-knowledge] (`walk`; reference call sites: experiments.py:265,
@@ -28,7 +28,7 @@ class PivotCheck:
     pinned host memory right behind the sweep and looked at only after the kernels that follow it have been queued, so the
     GPU runs from the sweep straight into them while the host waits for the copy (not for those kernels).
     PivotCheck.eager(ws) reads `info` now (one synchronising copy).  Either way failed() says whether a pivot failed and
-    leaves the first failing pivot per latent in `first_bad`."""
+    leaves the `info` words -- 1 + the first failing pivot per latent, 0 for a latent that passed -- in `first_bad`."""
     first_bad = None
 
     def __init__(self, ws):
