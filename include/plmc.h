@@ -532,6 +532,72 @@ int plmc_loo_grad_rq_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_
                          void *stream);
 
 /*
+ * Locally periodic kernel [gpytorch-knowledge: ProductKernel of PeriodicKernel and RBFKernel, the elementwise product of its factors,
+ * unverified offline] on the batched exact engine, the model of a periodicity whose shape drifts:
+ *     Khat_i = os[i] exp(-2 sum_k sin^2(pi tau_k / p[i][k]) / ell[i][k] - 1/2 sum_k (tau_k / lam[i][k])^2) + noise[i] I,   tau = x - x'
+ *     (ell the periodic lengthscale, not squared; p the period; lam = `rbf_ell` the RBF lengthscale),   1 <= d <= plmc_lper_max_dim().
+ *     Exceeding the limit, d <= 0 or a null `period` or `rbf_ell` is an argument error (plmc_last_error()); nothing is launched.
+ * Table, per latent i:  ell, p and lam (q x d each, contiguous), output scale os (q) or NULL (all ones).  noise: q.
+ * Every entry point takes the arguments of its periodic form with (ell, period, oscale) replaced by (ell, period, rbf_ell, oscale) and
+ * does what that form does:
+ *   plmc_assemble_lper_*        plmc_assemble_per_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_lper_*  plmc_assemble_cross_per_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_lper_ex_*    plmc_factorize_per_ex_*    (assembly overlapped with the sweep; bit-identical to plmc_assemble_lper_*
+ *                                                           followed by plmc_potrf_ex_*)
+ *   plmc_kinv_grad_lper_vd_*    plmc_kinv_grad_per_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ *   plmc_loo_grad_lper_*        plmc_loo_grad_per_*        (the gradient table of the leave-one-out objective, below)
+ * The periodic exponent is the periodic kernel's (phase reduced in revolutions, 1 / p as two terms), the RBF exponent comes from the raw
+ * differences x - x' scaled by 1 / lam, and ONE accurate exponential takes their sum: the fp32 assembly is within
+ *     [24 d (1 + 1 / min_k ell_k) + (d + 8)] 2^-24 os
+ * of the fp64 formula at the fp32 inputs per element, at any phase below 2^20 revolutions.  The diagonal is os + noise
+ * with one rounding, a coincident pair off the diagonal gives exactly os.
+ * Limits.  lam = +inf (1 / lam = 0) gives the value of plmc_assemble_per_* and ell = +inf that of the RBF kernel with lengthscales lam;
+ *   the gradient entries of the factor that is switched off are then EXACTLY 0 (finite tile sums divided by +inf), all others finite.
+ * Gradient table of plmc_kinv_grad_lper_vd_* and plmc_loo_grad_lper_* (double), 3 d + 2 entries per latent:
+ *     grad[latent] = [ d logp / d ell: d | d / d period: d | d / d rbf_ell: d | d / d noise | d / d os ]
+ *   The diagonal (tau = 0) contributes to noise and os only; an off-diagonal sine that is exactly 0 gives exactly 0 for ell and period.
+ *   plmc_kinv_grad_lper_vd_f32 with d > 1 forms K^-1 with the fp32 matrix instructions whatever PLMC_SPLIT says, as the periodic kernel
+ *   does (the knob and eig_lo are not looked at; no planes of W are needed): the split-engine epilogue is instantiated for d = 1 only,
+ *   which follows the knob like every other kernel.
+ * Scratch.  `Vd`: as for plmc_kinv_grad_vd_*.  `partials`: plmc_lper_grad_partials_bytes(n_pad, q, elem bytes) bytes, one row of
+ *   partial sums per tile (the size plmc_per_grad_partials_bytes gives); a function of its arguments only, never of a dev knob.  The
+ *   fp32 split engine takes the planes of W from the Vd of the sweep that produced W and refuses a call without them; fp64 and
+ *   PLMC_SPLIT=0 need no planes.
+ */
+int plmc_lper_max_dim(void);                  /* largest input dimension of a locally periodic kernel (8) */
+int64_t plmc_lper_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes);
+int plmc_assemble_lper_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
+                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_lper_f64(const double *X, int n, int d, const double *ell, const double *period, const double *rbf_ell, const double *oscale,
+                           const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_lper_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period,
+                                 const float *rbf_ell, const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
+                                 int64_t n_rows, int q, void *stream);
+int plmc_assemble_cross_lper_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
+                                 const double *rbf_ell, const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
+                                 int64_t n_rows, int q, void *stream);
+int plmc_factorize_lper_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
+                               const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                               int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_lper_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *rbf_ell, const double *oscale,
+                               const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                               int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_lper_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                               const float *ell, const float *period, const float *rbf_ell, const float *oscale, double *grad, float *Kinv,
+                               int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd,
+                               void *stream);
+int plmc_kinv_grad_lper_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                               const double *ell, const double *period, const double *rbf_ell, const double *oscale, double *grad, double *Kinv,
+                               int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd,
+                               void *stream);
+int plmc_loo_grad_lper_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                           int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale, double *grad,
+                           void *partials, int q, void *stream);
+int plmc_loo_grad_lper_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                           int n, int d, const double *ell, const double *period, const double *rbf_ell, const double *oscale, double *grad,
+                           void *partials, int q, void *stream);
+
+/*
  * Leave-one-out objective (LeaveOneOutPseudoLikelihood, projected_lmc.py:86-105): with P = Khat^-1, alpha = P y, p_i = P_ii,
  *     L = sum_i [ 1/2 log p_i - 1/2 alpha_i^2 / p_i ] - n/2 log 2 pi,
  *     c_i = 1/2 / p_i + 1/2 alpha_i^2 / p_i^2,   g_i = -alpha_i / p_i,   u = P g = dL / dy,
@@ -548,7 +614,7 @@ int plmc_loo_grad_rq_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_
  *   Xop: krows x n_pad per latent, K-major (row = contraction index), leading dimension ldx, batch stride strideX; every row in
  *   [0, krows) is contracted, so rows that carry nothing must be zero.  krows a multiple of 16, ldx a multiple of plmc_block() and >=
  *   n_pad, the pointer 16-byte aligned.  beta: q x n_pad.  `partials`: plmc_grad_partials_bytes(n_pad, q * ncomp),
- *   plmc_sm_grad_partials_bytes, plmc_per_grad_partials_bytes as for the `_vd` calls.  With Xop = W (the inverse factor with zeros above
+ *   plmc_sm_grad_partials_bytes, plmc_per_grad_partials_bytes, plmc_lper_grad_partials_bytes as for the `_vd` calls.  With Xop = W (the inverse factor with zeros above
  *   its diagonal, krows = n_pad) and beta = alpha the call returns what plmc_kinv_grad*_vd_* returns.  Both element types form the
  *   product with the matrix instructions of that type (fp32: v_mfma_f32_16x16x4_f32 whatever PLMC_SPLIT says).  q n_pad^2 krows
  *   flop (upper tiles only).

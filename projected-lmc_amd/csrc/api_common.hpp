@@ -16,6 +16,7 @@ constexpr int SM_MAX_MIX = 8;        // most components of a spectral-mixture ke
 constexpr int SM_MAX_DIM = 8;        // largest input dimension of a spectral-mixture kernel (plmc_sm_max_dim())
 constexpr int PER_MAX_DIM = 8;       // largest input dimension of a periodic kernel (plmc_per_max_dim())
 constexpr int RQ_MAX_DIM = 16;       // largest input dimension of a rational-quadratic kernel (plmc_rq_max_dim())
+constexpr int LPER_MAX_DIM = 8;      // largest input dimension of a locally periodic kernel (plmc_lper_max_dim())
 
 char *err_buf();                     // thread-local, defined in api.hip
 
@@ -74,17 +75,23 @@ const Knobs &knobs();
 //   SM     spectral mixture of ncomp components: ell = its scales, second = its means (q, ncomp, d), oscale = its weights (q, ncomp) | null
 //   PER    periodic: ell = its lengthscales, second = its periods (q, d), oscale (q) | null
 //   RQ     rational quadratic: ell = its lengthscales (q, d), second = its alpha (q), oscale (q) | null
-// `kind` is not looked at for SM, PER and RQ; the pointers are of the call's element type.
-enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ };
+//   LPER   locally periodic (periodic x RBF): ell = its periodic lengthscales, second = its periods, third = its RBF lengthscales (q, d
+//          each), oscale (q) | null
+// `kind` is not looked at for SM, PER, RQ and LPER; the pointers are of the call's element type.  `third` is null for every other family.
+enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER };
 struct CovTable {
   CovFamily family;
   int kind, d, ncomp;
   const void *ell, *second, *oscale;
+  const void *third = nullptr;
   static CovTable plain(int kind, int d, const void *ell, const void *oscale) { return {COV_PLAIN, kind, d, 1, ell, nullptr, oscale}; }
   static CovTable add(int kind, int d, int ncomp, const void *ell, const void *oscale) { return {COV_ADD, kind, d, ncomp, ell, nullptr, oscale}; }
   static CovTable sm(int d, int nmix, const void *scales, const void *means, const void *weights) { return {COV_SM, 0, d, nmix, scales, means, weights}; }
   static CovTable per(int d, const void *ell, const void *period, const void *oscale) { return {COV_PER, 0, d, 1, ell, period, oscale}; }
   static CovTable rq(int d, const void *ell, const void *alpha, const void *oscale) { return {COV_RQ, 0, d, 1, ell, alpha, oscale}; }
+  static CovTable lper(int d, const void *ell, const void *period, const void *rbf_ell, const void *oscale) {
+    return {COV_LPER, 0, d, 1, ell, period, oscale, rbf_ell};
+  }
   // the family's limits: the message of the first one missed, or null
   const char *check() const {
     if (family == COV_ADD) {
@@ -97,8 +104,11 @@ struct CovTable {
       if (d <= 0 || d > PER_MAX_DIM) return "need 0 < d <= plmc_per_max_dim()";
     } else if (family == COV_RQ) {
       if (d <= 0 || d > RQ_MAX_DIM) return "need 0 < d <= plmc_rq_max_dim()";
+    } else if (family == COV_LPER) {
+      if (d <= 0 || d > LPER_MAX_DIM) return "need 0 < d <= plmc_lper_max_dim()";
+      if (!third) return "null pointer";
     }
-    return (family == COV_SM || family == COV_PER || family == COV_RQ) && !second ? "null pointer" : nullptr;
+    return (family == COV_SM || family == COV_PER || family == COV_RQ || family == COV_LPER) && !second ? "null pointer" : nullptr;
   }
   // the family whose kernels run: an additive table of one component IS the plain kernel (ell (q, 1, d) is ell (q, d)) and takes the
   // plain instantiations, bit for bit

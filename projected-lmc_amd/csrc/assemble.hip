@@ -454,7 +454,49 @@ template <typename T, int DCAP> struct RqTable {
   }
 };
 
-// d <= 8 (DCAP in {4, 8}; spectral mixture, periodic and rational quadratic also 1; rational quadratic also 16); P: AddTable / SmTable / PerTable / RqTable
+// The locally periodic table (covariance.hpp): per latent periodic lengthscales, periods, RBF lengthscales (d each), output scale | null.
+// In LDS: ip = 1 / p, its residual ipr, w = 1 / ell, v = 1 / lam [DCAP] each (0 beyond d: that dimension adds exactly 0 to both
+// exponents), os.
+template <typename T, int DCAP> struct LperPairValue {
+  const T *ip, *ipr, *w, *v;
+  T os;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    T b0[DCAP], b1[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) { b0[k] = xc[k].x; b1[k] = xc[k].y; }
+    return Pair<T>{os * lper_value<T, DCAP>(xr, b0, ip, ipr, w, v), os * lper_value<T, DCAP>(xr, b1, ip, ipr, w, v)};
+  }
+};
+template <typename T, int DCAP> struct LperTable {
+  static constexpr int LDS = 4 * DCAP + 1;
+  const T *ell, *period, *rbf_ell, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < DCAP) {
+      T ip = T(0), ipr = T(0);
+      if (tid < d) per_inv_period(period[(int64_t)lat * d + tid], ip, ipr);
+      par[tid] = ip;
+      par[DCAP + tid] = ipr;
+      par[2 * DCAP + tid] = tid < d ? T(1) / ell[(int64_t)lat * d + tid] : T(0);
+      par[3 * DCAP + tid] = tid < d ? T(1) / rbf_ell[(int64_t)lat * d + tid] : T(0);
+    }
+    if (tid == 0) par[4 * DCAP] = oscale ? oscale[lat] : T(1);
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, LperPairValue<T, DCAP>{par, par + DCAP, par + 2 * DCAP, par + 3 * DCAP, par[4 * DCAP]}, nz, Al,
+                                 lda, ib, jb, n, edge);
+  }
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T a[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) a[k] = xa[k];
+    return par[4 * DCAP] * lper_value<T, DCAP>(a, xs, par, par + DCAP, par + 2 * DCAP, par + 3 * DCAP);
+  }
+};
+
+// d <= 8 (DCAP in {4, 8}; spectral mixture, periodic, locally periodic and rational quadratic also 1; rational quadratic also 16);
+// P: AddTable / SmTable / PerTable / RqTable / LperTable
 template <typename T, int DCAP, class P>
 __global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
                                                                     const T *__restrict__ noise, T *__restrict__ A,
@@ -573,7 +615,7 @@ __global__ __launch_bounds__(NTHREADS) void k_assemble_cross_table(const P prm, 
   }
 }
 
-// One launch of a table kernel: P<T, DC> is AddTable / SmTable / PerTable / RqTable, `args` what follows the table in the kernel's signature
+// One launch of a table kernel: P<T, DC> is AddTable / SmTable / PerTable / RqTable / LperTable, `args` what follows the table in the kernel's signature
 template <typename T, int DC, template <typename, int> class P, class... Args>
 void launch_small_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... args) {
   hipLaunchKernelGGL((k_assemble_small_table<T, DC, P<T, DC>>), grid, dim3(NTHREADS), 0, st, prm, args...);
@@ -587,6 +629,9 @@ template <typename T, int DC> AddTable<T, DC> add_table(const CovTable &t) { ret
 template <typename T, int DC> SmTable<T, DC> sm_table(const CovTable &t) { return {t.ncomp, (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
 template <typename T, int DC> PerTable<T, DC> per_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
 template <typename T, int DC> RqTable<T, DC> rq_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
+template <typename T, int DC> LperTable<T, DC> lper_table(const CovTable &t) {
+  return {(const T *)t.ell, (const T *)t.second, (const T *)t.third, (const T *)t.oscale};
+}
 
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
@@ -596,7 +641,7 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
   PLMC_REQUIRE_TABLE(t);
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
-  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ;       // d <= 8 (rational quadratic: 16) by the family's limit
+  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER;   // d <= 8 (rational quadratic: 16) by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
   PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
@@ -645,6 +690,11 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
       else if (d <= 4) table(rq_table<T, 4>(t));
       else if (d <= 8) table(rq_table<T, 8>(t));
       else table(rq_table<T, 16>(t));
+      break;
+    case COV_LPER:
+      if (d == 1) table(lper_table<T, 1>(t));
+      else if (d <= 4) table(lper_table<T, 4>(t));
+      else table(lper_table<T, 8>(t));
       break;
   }
   return launch_status(__func__);
@@ -713,6 +763,11 @@ int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int n
       else if (d <= 4) table(rq_table<T, 4>(t));
       else if (d <= 8) table(rq_table<T, 8>(t));
       else table(rq_table<T, 16>(t));
+      break;
+    case COV_LPER:
+      if (d == 1) table(lper_table<T, 1>(t));
+      else if (d <= 4) table(lper_table<T, 4>(t));
+      else table(lper_table<T, 8>(t));
       break;
   }
   return launch_status(__func__);
@@ -810,6 +865,21 @@ int plmc_rq_max_dim(void) { return plmc::RQ_MAX_DIM; }
 PLMC_RQ_ENTRY(f32, float)
 PLMC_RQ_ENTRY(f64, double)
 #undef PLMC_RQ_ENTRY
+int plmc_lper_max_dim(void) { return plmc::LPER_MAX_DIM; }
+#define PLMC_LPER_ENTRY(SUF, T)                                                                                                                \
+  int plmc_assemble_lper_##SUF(const T *X, int n, int d, const T *ell, const T *period, const T *rbf_ell, const T *oscale, const T *noise,     \
+                               T *A, int64_t lda, int64_t strideA, int q, void *stream) {                                                      \
+    return plmc::assemble_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), X, n, noise, A, lda, strideA, q, stream);                   \
+  }                                                                                                                                            \
+  int plmc_assemble_cross_lper_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *period, const T *rbf_ell,           \
+                                     const T *oscale, T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,               \
+                                     void *stream) {                                                                                           \
+    return plmc::assemble_cross_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q,     \
+                                        stream);                                                                                               \
+  }
+PLMC_LPER_ENTRY(f32, float)
+PLMC_LPER_ENTRY(f64, double)
+#undef PLMC_LPER_ENTRY
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
   return plmc::assemble_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);

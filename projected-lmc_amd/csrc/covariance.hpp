@@ -254,6 +254,28 @@ __device__ __forceinline__ T rq_value(const T (&a)[DCAP], const T (&b)[DCAP], co
   }
   return rq_profile(r2, alpha, i2a);
 }
+
+// ---- locally periodic [gpytorch-knowledge: ProductKernel of PeriodicKernel and RBFKernel, unverified offline]:
+//     k(x, x') = exp(-2 sum_k sin^2(pi tau_k / p_k) / ell_k - 1/2 sum_k (tau_k / lam_k)^2),   tau = x - x'
+// (ell the periodic lengthscale, not squared; lam the RBF lengthscale).  The periodic exponent is per_value's: the phase reduced in
+// revolutions, 1 / p as two terms.  The RBF exponent is rq_value's r^2: the RAW difference scaled by v = 1 / lam, exactly 0 at coincident
+// points and beyond d.  ONE accurate exponential of the summed exponent ("Locally periodic kernel: fp32 numerics"); with
+// v = 0 the sum is per_value's exponent bit for bit, with w = 0 it is -r^2 / 2.
+template <typename T> __device__ __forceinline__ T lper_exp(T e, T r2) { return dexp(__builtin_fma(T(-0.5), r2, T(-2) * e)); }
+// one covariance value (unit output scale): rows of DCAP raw coordinates a, b; ip, ipr, w = 1 / ell, v = 1 / lam [DCAP] (all 0 beyond d:
+// that dimension adds exactly 0 to both exponents)
+template <typename T, int DCAP>
+__device__ __forceinline__ T lper_value(const T (&a)[DCAP], const T (&b)[DCAP], const T *ip, const T *ipr, const T *w, const T *v) {
+  T e = T(0), r2 = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    const T s = per_sinpi(per_phase(a[k], b[k], ip[k], ipr[k]));
+    e += (s * s) * w[k];
+    const T sd = (a[k] - b[k]) * v[k];
+    r2 += sd * sd;
+  }
+  return lper_exp(e, r2);
+}
 #undef dexp
 #undef dsqrt
 

@@ -2,6 +2,8 @@
 // k_kinv_grad_add (256 threads) and by kinv_tile_epilogue_add (the halves of k_kinv_grad_add_bf3), which name what the bodies use.
   if constexpr (F == COV_PER) {
 #include "kinv_epilogue_per.inc"
+  } else if constexpr (F == COV_LPER) {
+#include "kinv_epilogue_lper.inc"
   } else if constexpr (F == COV_RQ) {
 #include "kinv_epilogue_rq.inc"
   } else if constexpr (F == COV_SM) {

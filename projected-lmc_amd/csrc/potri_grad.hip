@@ -246,21 +246,25 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // or null; `kind` and ncomp (1) are not looked at.
 // COV_RQ: a rational-quadratic kernel of up to DC (1, 4, 8, 16) input dimensions (kinv_epilogue_rq.inc): ell = its lengthscales, `means` its alpha (q),
 // oscale (q) or null; `kind` and ncomp (1) are not looked at.
+// COV_LPER: a locally periodic kernel of up to DC (1, 4, 8) input dimensions (kinv_epilogue_lper.inc): ell = its periodic lengthscales,
+// `means` its periods, `third` its RBF lengthscales, oscale (q) or null; `kind` and ncomp (1) are not looked at.  No other family reads
+// `third`.
 template <typename T, CovFamily F, int DC>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                        const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
-                                                       int64_t strideK, T *kinv_diag, double *__restrict__ partials, const T *__restrict__ means) {
+                                                       int64_t strideK, T *kinv_diag, double *__restrict__ partials, const T *__restrict__ means,
+                                                       const T *__restrict__ third) {
   if (!live) { n = 0; Kinv = nullptr; kinv_diag = nullptr; }       // every element predicate below is then false
 #include "kinv_epilogue_table.inc"
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || ((F == COV_PER || F == COV_LPER) && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
-                                                                const T *__restrict__ means) {
+                                                                const T *__restrict__ means, const T *__restrict__ third) {
   PLMC_KINV_TILE_PRODUCT;
   const int tid = threadIdx.x;
   constexpr bool live = true;
@@ -273,10 +277,11 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_add_bf3(int kind, int nc
                                                                 const float *__restrict__ oscale, float *Kinv, int64_t ldk, int64_t strideK,
                                                                 float *kinv_diag, double *__restrict__ partials, int nlat,
                                                                 const unsigned short *__restrict__ Wp, const float *__restrict__ wscale,
-                                                                int64_t wp_lat_stride, int64_t ws_stride, const float *__restrict__ means) {
+                                                                int64_t wp_lat_stride, int64_t ws_stride, const float *__restrict__ means,
+                                                                const float *__restrict__ third) {
   PLMC_KINV_BF3_TILE_PRODUCT;
   kinv_tile_epilogue_add<float, F, DC>(acc0, reinterpret_cast<float *>(lds) + half * tile_smem_elems<float>(), (int)threadIdx.x & 255, ib <= jb, kind, ncomp,
-                                       ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means);
+                                       ib, jb, lat, m, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, kinv_diag, partials, means, third);
 }
 
 // The tile walk of the reductions below, as text (see PLMC_KINV_TILE_PRODUCT): declares `lat` = blockIdx.x and leaves in red[grp * GP + slot]
@@ -394,6 +399,30 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_rq(const double *__restr
   }
 }
 
+// The reduction for the locally periodic kernel: one row of GP slots per tile (kinv_epilogue_lper.inc).  grid (q).
+// grad[lat]: [ d/d ell (d) | d/d period (d) | d/d lam (d) | d/d noise | d/d oscale ], with the factors the epilogue left out.  A factor
+// that is switched off (ell = +inf or lam = +inf) gets finite sum / inf = exactly 0.
+template <typename T>
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_lper(const double *__restrict__ partials, int m, int d, const T *__restrict__ ell,
+                                                             const T *__restrict__ period, const T *__restrict__ rbf_ell,
+                                                             double *__restrict__ grad) {
+  PLMC_REDUCE_TILES(GP, 0);
+  if (threadIdx.x < GP) {
+    const double tot = reduce_slot_total(red);
+    const int k = threadIdx.x, kk = k % LPER_MAX_DIM;
+    double *gl = grad + (int64_t)lat * (3 * d + 2);
+    if (k < 3 * LPER_MAX_DIM && kk < d) {
+      const double l = (double)ell[(int64_t)lat * d + kk];
+      if (k < LPER_MAX_DIM) gl[kk] = 0.5 * tot / (l * l);
+      else if (k < 2 * LPER_MAX_DIM) {
+        const double p = (double)period[(int64_t)lat * d + kk];
+        gl[d + kk] = 0.5 * tot * SM_2PI / (l * p * p);
+      } else gl[2 * d + kk] = 0.5 * tot / (double)rbf_ell[(int64_t)lat * d + kk];
+    } else if (k == MAX_DIM) gl[3 * d] = 0.5 * tot;
+    else if (k == MAX_DIM + 1) gl[3 * d + 1] = 0.5 * tot;
+  }
+}
+
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -430,7 +459,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
   const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
-  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second;
+  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -451,8 +480,9 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
-      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ,
+      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER,
                    family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                   : family == COV_LPER ? "the locally periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_RQ ? "the rational-quadratic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                                       : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * rows * GP * (int64_t)sizeof(double);
@@ -473,10 +503,11 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
                      part, q, wp, wsc, wp_lat, ws_lat)
 #define PLMC_LAUNCH_TB(F, DC) \
   hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, F, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
-                     kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)second)
+                     kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)second, (const float *)third)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     switch (family) {
       case COV_PER: PLMC_LAUNCH_TB(COV_PER, 1); break;     // (d = 1 only: kinv_grad_f32_any)
+      case COV_LPER: PLMC_LAUNCH_TB(COV_LPER, 1); break;   // (d = 1 only: kinv_grad_f32_any)
       case COV_RQ:                                         // (three planes: d = 1 only, kinv_grad_f32_any -- DC = 4 / 8 would spill there)
         if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_RQ, 1);
         else if (d == 1) PLMC_LAUNCH_TB(COV_RQ, 1);
@@ -501,10 +532,11 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
                      oscale, Kinv, ldk, strideK, kinv_diag, part, q)
 #define PLMC_LAUNCH_TG(F, DC) \
   hipLaunchKernelGGL((k_kinv_grad_add<T, F, DC>), grid, block, 0, st, kind, ncomp, W, n_pad, ldw, strideW, alpha, X, n, d, ell, oscale, Kinv, ldk, \
-                     strideK, kinv_diag, part, q, second)
+                     strideK, kinv_diag, part, q, second, third)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_TG(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_PER, 4); else PLMC_LAUNCH_TG(COV_PER, 8); break;
+      case COV_LPER: if (d == 1) PLMC_LAUNCH_TG(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_LPER, 4); else PLMC_LAUNCH_TG(COV_LPER, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_TG(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_RQ, 8); else PLMC_LAUNCH_TG(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
@@ -521,6 +553,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
@@ -570,10 +603,10 @@ __global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || (F == COV_PER && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
+__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || ((F == COV_PER || F == COV_LPER) && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
     int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
     const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
-    const T *__restrict__ means) {
+    const T *__restrict__ means, const T *__restrict__ third) {
   PLMC_LOO_TILE_PRODUCT;
 #include "kinv_epilogue_table.inc"
 }
@@ -637,7 +670,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
   const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
-  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second;
+  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(Xop && beta && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && n > 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
@@ -655,11 +688,12 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
   hipLaunchKernelGGL((k_loo_grad<T, DC, SP>), grid, block, 0, st, kind, Xop, n_pad, krows, ldx, strideX, beta, X, n, d, ell, oscale, part, q)
 #define PLMC_LAUNCH_LT(F, DC) \
   hipLaunchKernelGGL((k_loo_grad_add<T, F, DC>), grid, block, 0, st, kind, ncomp, Xop, n_pad, krows, ldx, strideX, beta, X, n, d, ell, oscale, part, q, \
-                     second)
+                     second, third)
   {
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * (double)krows, q * np * (double)krows * sizeof(T));
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_LT(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_PER, 4); else PLMC_LAUNCH_LT(COV_PER, 8); break;
+      case COV_LPER: if (d == 1) PLMC_LAUNCH_LT(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_LPER, 4); else PLMC_LAUNCH_LT(COV_LPER, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_LT(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_RQ, 8); else PLMC_LAUNCH_LT(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
@@ -676,6 +710,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
     ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+      case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
@@ -725,10 +760,10 @@ static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_
   // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
   // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
   // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel keeps d sines, cosine
-  // complements and 2 d sums live and follows the same rule.  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
+  // complements and 2 d sums live and follows the same rule, and so does the locally periodic kernel (3 d sums).  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
   // every d; beside the three bf16 planes (PLMC_SPLIT=3, or no eig_lo) it fits at d = 1 only, so d > 1 takes the fp32 products there.
   const bool three_planes = !(split == 2 && eig_lo);
-  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER) && table.d > 1) ||
+  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER || table.family == plmc::COV_LPER) && table.d > 1) ||
       (table.family == plmc::COV_RQ && table.d > 1 && three_planes))
     return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
@@ -845,6 +880,28 @@ int plmc_kinv_grad_rq_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_
   return kinv_grad_f64(CovTable::rq(d, ell, shape, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
                        stream);
 }
+// locally periodic kernel: plmc_kinv_grad_vd_* with the table (periodic lengthscales, periods, RBF lengthscales, output scale)
+// (include/plmc.h); `partials` is sized by plmc_lper_grad_partials_bytes
+int64_t plmc_lper_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
+  (void)elem_bytes;                                   // one row of fp64 partial sums per tile, whatever the element type
+  return plmc_grad_partials_bytes(n_pad, q);
+}
+int plmc_kinv_grad_lper_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                               const float *ell, const float *period, const float *rbf_ell, const float *oscale, double *grad, float *Kinv,
+                               int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd,
+                               void *stream) {
+  return kinv_grad_f32_any(CovTable::lper(d, ell, period, rbf_ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
+                           partials, q, eig_lo, stream, Vd);
+}
+int plmc_kinv_grad_lper_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                               const double *ell, const double *period, const double *rbf_ell, const double *oscale, double *grad, double *Kinv,
+                               int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd,
+                               void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  return kinv_grad_f64(CovTable::lper(d, ell, period, rbf_ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
+                       partials, q, stream);
+}
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
@@ -877,6 +934,12 @@ int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
   int plmc_loo_grad_per_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
                               int d, const T *ell, const T *period, const T *oscale, double *grad, void *partials, int q, void *stream) {      \
     return plmc::loo_grad_impl<T>(CovTable::per(d, ell, period, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
+  }                                                                                                                                             \
+  int plmc_loo_grad_lper_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,      \
+                               int d, const T *ell, const T *period, const T *rbf_ell, const T *oscale, double *grad, void *partials, int q,   \
+                               void *stream) {                                                                                                  \
+    return plmc::loo_grad_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, \
+                                  q, stream);                                                                                                   \
   }                                                                                                                                             \
   int plmc_loo_grad_rq_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,        \
                              int d, const T *ell, const T *alpha, const T *oscale, double *grad, void *partials, int q, void *stream) {         \

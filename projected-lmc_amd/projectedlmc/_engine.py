@@ -57,8 +57,9 @@ class Workspace:
             # per-tile partial sums of the gradient kernel; the 16-bit planes of W it multiplies are left in Vd by the sweep
             # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none
             # (a spectral-mixture table: the library's own size call for it, include/plmc.h "Spectral-mixture kernel")
-            # (a periodic table likewise: "Periodic kernel")
+            # (a periodic table likewise: "Periodic kernel"; `per` is that kind or the locally periodic one, which has its own size call)
             nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(self.n_pad, q, ncomp, esz) if sm
+                         else L.cdll.plmc_lper_grad_partials_bytes(self.n_pad, q, esz) if per == LPER
                          else L.cdll.plmc_per_grad_partials_bytes(self.n_pad, q, esz) if per
                          else L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
             self.partials = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
@@ -85,7 +86,7 @@ def _drop_all():
 def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1, sm=False, per=False):
     ncomp = ncomp if need_grad else 1                   # (only the partial sums of the gradient kernel depend on it)
     sm = bool(sm) and bool(need_grad)
-    per = bool(per) and bool(need_grad)
+    per = per if (per and need_grad) else False       # False, PER or LPER (_per_kind)
     key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp, sm, per)
     ws = _ws_cache.get(key)
     if ws is None:
@@ -141,8 +142,17 @@ def _contig(t, dtype=None):
 # points, which take no kind and (ell, alpha) in the place of ell (include/plmc.h, "Rational-quadratic kernel").  Its table has the rank of
 # a plain one, so what reads the input dimension off the table takes the kind beside it.  The gradient table [d lengthscales | d alpha |
 # d noise | d oscale] splits like the others: its first d + 1 entries are the gradient of the table.
+# Kind "locally_periodic" (kernels.ProductKernel of a periodic and an RBF kernel): `ell` is the three rows of its table stacked,
+# (q, 3, d) = [periodic lengthscales | periods | RBF lengthscales], `oscale` (q) | None; it goes to the `_lper` entry points, which take no
+# kind and (ell, period, rbf_ell) in the place of ell (include/plmc.h, "Locally periodic kernel").  Like the periodic table it has the
+# rank of an additive one and travels with its kind.  The gradient table [d lengthscales | d periods | d RBF lengthscales | d noise |
+# d oscale] splits like the others.
 PER = "periodic"
+LPER = "locally_periodic"
 RQ = "rq"
+_LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
+         "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
+         "plmc_loo_grad": "plmc_loo_grad_lper"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
        "plmc_loo_grad": "plmc_loo_grad_rq"}
@@ -161,22 +171,28 @@ def is_sm(ell):
     return ell.dim() == 4
 
 
+def _per_kind(kind):
+    """The kind if its table is a stack of (q, d) rows with one row of partial sums per tile (periodic, locally periodic), else False."""
+    return kind if kind in (PER, LPER) else False
+
+
 def n_components(ell, kind=None):
-    if kind == PER:
+    if kind in (PER, LPER):
         return 1
     return ell.shape[2] if ell.dim() == 4 else (ell.shape[1] if ell.dim() == 3 else 1)
 
 
 def kind_code(kind):
-    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic and the
-    rational-quadratic kernel likewise: their name stands in the code's place and sends _kernel_call to them."""
-    return None if kind == "sm" else (kind if kind in (PER, RQ) else _hip.KIND[kind])
+    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic, the locally
+    periodic and the rational-quadratic kernel likewise: their name stands in the code's place and sends _kernel_call to them."""
+    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) else _hip.KIND[kind])
 
 
 def grad_table_width(ell, kind=None):
     """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)];
     spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights];
     periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale];
+    locally periodic: ell[0] is the three rows (3, d), [d/d lengthscales | d/d periods | d/d RBF lengthscales | d/d noise | d/d oscale];
     rational quadratic: ell[0] is (d + 1), [d/d lengthscales | d/d alpha | d/d noise | d/d oscale]."""
     return ell[0].numel() + 1 + n_components(ell, kind)
 
@@ -196,6 +212,11 @@ def _check_kernel_shape(L, ell, kind=None):
             raise ValueError("a periodic kernel's table is (q, 2, d) = [lengthscales | periods]")
         if d > L.cdll.plmc_per_max_dim():
             raise ValueError("periodic kernel on %d dimensions exceeds plmc_per_max_dim()=%d" % (d, L.cdll.plmc_per_max_dim()))
+    elif kind == LPER:
+        if ell.dim() != 3 or ell.shape[1] != 3:
+            raise ValueError("a locally periodic kernel's table is (q, 3, d) = [periodic lengthscales | periods | RBF lengthscales]")
+        if d > L.cdll.plmc_lper_max_dim():
+            raise ValueError("locally periodic kernel on %d dimensions exceeds plmc_lper_max_dim()=%d" % (d, L.cdll.plmc_lper_max_dim()))
     elif is_sm(ell):
         if d > L.cdll.plmc_sm_max_dim() or n_components(ell) > L.cdll.plmc_sm_max_mixtures():
             raise ValueError("spectral mixture with %d components on %d dimensions exceeds plmc_sm_max_mixtures()=%d / plmc_sm_max_dim()=%d"
@@ -207,7 +228,8 @@ def _check_kernel_shape(L, ell, kind=None):
 def _kernel_call(L, base, dt, head, ell, tail, stream=None):
     """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
     form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER, or its
-    rational-quadratic form (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ.
+    locally periodic form (*head[1:], lengthscales, periods, RBF lengthscales, *tail) when head[0] is LPER, or its rational-quadratic form
+    (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ.
     `stream`: the side stream the call is queued on, if not the current one."""
     if isinstance(head[0], str) and head[0] == RQ:
         rows = getattr(ell, "_rq_rows", None)                # split once per table, as the periodic kernel's rows below
@@ -218,6 +240,15 @@ def _kernel_call(L, base, dt, head, ell, tail, stream=None):
             rows[0].record_stream(stream)
             rows[1].record_stream(stream)
         L.call(_RQ[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), *tail)
+        return
+    if isinstance(head[0], str) and head[0] == LPER:
+        rows = getattr(ell, "_lper_rows", None)              # split once per table, as the periodic kernel's rows below
+        if rows is None:
+            rows = ell._lper_rows = (ell[:, 0].contiguous(), ell[:, 1].contiguous(), ell[:, 2].contiguous())
+        if stream is not None:
+            for r in rows:
+                r.record_stream(stream)
+        L.call(_LPER[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), _hip.ptr(rows[2]), *tail)
         return
     if isinstance(head[0], str) and head[0] == PER:
         rows = getattr(ell, "_per_rows", None)               # split once per table, as the spectral mixture's planes below
@@ -322,7 +353,7 @@ class ExactLatentLogProb(torch.autograd.Function):
         G = n_components(ell, kind)
         need_grad = any(ctx.needs_input_grad[1:5]) or table is not None
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), kind == PER)
+        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), _per_kind(kind))
         st = _hip.stream_ptr(dev)
         grad = table if table is not None else (torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
@@ -366,7 +397,7 @@ class ExactLatentLogProb(torch.autograd.Function):
             if check and info.failed():
                 def attempt(jit):
                     nonlocal ws
-                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), kind == PER)   # waits for the failed attempt's gradient kernel
+                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), _per_kind(kind))   # waits for the failed attempt's gradient kernel
                     return enqueue(nzc + jit)
 
                 logp = walk(dt, info, attempt)[1]
@@ -466,7 +497,7 @@ def exact_loo(kind, X, ell, oscale, noise, y):
     d = X.shape[1]
     Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
     _check_kernel_shape(L, ellc, kind)
-    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), kind == PER)
+    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), _per_kind(kind))
     st = _hip.stream_ptr(dev)
     factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
     L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
@@ -534,7 +565,7 @@ class ExactLooLogProb(torch.autograd.Function):
         _check_kernel_shape(L, ell, kind)
         need_grad = any(ctx.needs_input_grad[1:5])
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), kind == PER)
+        ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), _per_kind(kind))
         st = _hip.stream_ptr(dev)
         factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
         L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)

@@ -26,12 +26,14 @@ _TYPED = {
     "plmc_assemble": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_add": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_per": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    "plmc_assemble_lper": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_rq": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_sm": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_write_rhs": [_P, _I, _I, _P, _L, _L, _I, _I, _I, _P],
     "plmc_assemble_cross": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "plmc_assemble_cross_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_potrf": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P],
@@ -39,6 +41,7 @@ _TYPED = {
     "plmc_factorize_ex": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_add_ex": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_per_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
+    "plmc_factorize_lper_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_rq_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_sm_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
@@ -53,11 +56,13 @@ _TYPED = {
     "plmc_kinv_grad_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_add_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_per_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
+    "plmc_kinv_grad_lper_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_rq_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_per": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_lper": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_rq": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
@@ -86,6 +91,8 @@ _PLAIN = {
     "plmc_sm_grad_partials_bytes": ([_L, _I, _I, _I], _L),
     "plmc_per_max_dim": ([], _I),
     "plmc_per_grad_partials_bytes": ([_L, _I, _I], _L),
+    "plmc_lper_max_dim": ([], _I),
+    "plmc_lper_grad_partials_bytes": ([_L, _I, _I], _L),
     "plmc_rq_max_dim": ([], _I),
     "plmc_qr_max": ([], _I),
     "plmc_last_error": ([], _c.c_char_p),

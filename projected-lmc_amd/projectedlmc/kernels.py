@@ -60,6 +60,9 @@ class Kernel(torch.nn.Module):
         kind, ell, osc = self._pieces(x1.shape[-1], x1)
         return LazyKernel(kind, x1, x2, ell, osc, self.batch_shape)
 
+    def __mul__(self, other):
+        return ProductKernel(self, other)
+
 
 class RBFKernel(Kernel):
     has_lengthscale = True
@@ -231,6 +234,39 @@ class RQKernel(Kernel):
         return self.kind, torch.cat([self._ell(d, like), self.alpha.reshape(-1, 1)], 1), None
 
 
+class ProductKernel(Kernel):
+    """Product of kernels [gpytorch-knowledge: ProductKernel, the elementwise product of its factors, unverified offline] -- what
+    `k1 * k2` returns.  One product is served, the LOCALLY PERIODIC kernel PeriodicKernel * RBFKernel (either order):
+        k(x, x') = exp(-2 sum_k sin^2(pi tau_k / p_k) / ell_k - 1/2 sum_k (tau_k / lam_k)^2),   tau = x - x',
+    the model of a periodicity whose shape drifts.  The factors live in `self.kernels` (gpytorch's layout), so state dicts line up:
+    kernels.<i>.raw_lengthscale, kernels.<i>.raw_period_length.  Both factors are bare (no ScaleKernel inside; wrap the product) and
+    agree in active_dims, ard_num_dims and batch_shape; anything else raises NotImplementedError.  No lengthscale of its own.  On the
+    HIP path it is kernel kind "locally_periodic" of the batched exact engine (include/plmc.h, "Locally periodic kernel"); the additive
+    kernel, SGPR, the dense LMC / ICM and the variational models refuse it."""
+    has_lengthscale = False
+    kind = "locally_periodic"
+    is_stationary = True
+
+    def __init__(self, *kernels):
+        given = "ProductKernel(%s)" % ", ".join(type(k).__name__ for k in kernels)
+        per = [k for k in kernels if type(k) is PeriodicKernel]
+        rbf = [k for k in kernels if type(k) is RBFKernel]
+        if len(kernels) != 2 or len(per) != 1 or len(rbf) != 1:
+            raise NotImplementedError("ProductKernel serves the product of one PeriodicKernel and one RBFKernel only, got %s" % given)
+        for name in ("active_dims", "ard_num_dims", "batch_shape"):
+            if getattr(per[0], name) != getattr(rbf[0], name):
+                raise NotImplementedError("ProductKernel needs factors with equal %s, got %s with %r and %r"
+                                          % (name, given, getattr(kernels[0], name), getattr(kernels[1], name)))
+        super().__init__(ard_num_dims=per[0].ard_num_dims, batch_shape=per[0].batch_shape, active_dims=per[0].active_dims)
+        self.kernels = torch.nn.ModuleList(kernels)
+        self._per, self._rbf = (0, 1) if kernels[0] is per[0] else (1, 0)
+
+    def _pieces(self, d, like=None):
+        """The table (q, 3, d) = [periodic lengthscale | period | RBF lengthscale] and no output scale."""
+        _, table, _ = self.kernels[self._per]._pieces(d, like)
+        return self.kind, torch.cat([table, self.kernels[self._rbf]._ell(d, like).unsqueeze(1)], 1), None
+
+
 def _refuse(cls, name, kernel, model):
     k = kernel
     while k is not None and not isinstance(k, cls):
@@ -243,6 +279,12 @@ def _refuse(cls, name, kernel, model):
 def refuse_periodic(kernel, model):
     """The periodic kernel runs on the batched exact engine only: name the model that cannot take it."""
     _refuse(PeriodicKernel, "PeriodicKernel", kernel, model)
+
+
+def refuse_product(kernel, model):
+    """The locally periodic kernel (ProductKernel) runs on the batched exact engine only: name the model that cannot take it.  `kernel`
+    is an instance, bare or inside a ScaleKernel: `kernel_type` may be a factory function, which only shows its product once called."""
+    _refuse(ProductKernel, "ProductKernel (PeriodicKernel * RBFKernel)", kernel, model)
 
 
 def refuse_rq(kernel, model):
@@ -300,7 +342,8 @@ class LazyKernel:
     kernel sum_g os_g k(x1, x2; ell_g) (additive.py), +inf on the dimensions a component ignores -- `inv_ell` is 0 there.
     kind "sm": ell (q, 2, M, d) holds the scales and the means of a spectral mixture, oscale (q, M) its weights (`scales`, `means`,
     `weights`).  kind "periodic": ell (q, 2, d) holds the lengthscales and the periods, oscale (q) | None.  kind "rq": ell (q, d + 1) holds
-    the lengthscales and, in its last column, alpha; oscale (q) | None."""
+    the lengthscales and, in its last column, alpha; oscale (q) | None.  kind "locally_periodic": ell (q, 3, d) holds the periodic
+    lengthscales, the periods and the RBF lengthscales, oscale (q) | None."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise

@@ -233,6 +233,7 @@ class VariationalMultitaskGPModel(torch.nn.Module):
         self.covar_module = handle_covar_(kernel_type, dim=self.dim, decomp=decomp, prior_scales=prior_scales,
                                           prior_width=prior_width, n_funcs=n_latents, ker_kwargs=ker_kwargs,
                                           outputscales=outputscales)
+        _k.refuse_product(self.covar_module, "VariationalMultitaskGPModel")      # (kernel_type may be a factory: look at what it built)
         self.mean_module = _m.ZeroMean(batch_shape=torch.Size([n_latents]))
         self.n_tasks, self.n_latents, self.decomp = n_tasks, n_latents, decomp
         if init_lmc_coeffs and train_y is not None:
