@@ -208,6 +208,31 @@ int plmc_wt_matvec_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t stri
                        double *alpha, int q, void *stream);
 
 /*
+ * Draws from a factorised covariance: Y = shift + U^T Z against the factor where the sweep left it -- the `L z` behind
+ * `MultivariateNormal.rsample` [gpytorch-knowledge, unverified offline], which the reference's synthetic study begins with
+ * (experiments.py:150-151, `MultivariateNormal(zeros, kernel(X)).sample()`):
+ *     Y[b][i][j] = shift[b][i] + sum_{k <= i} U[b][k][i] Z[b][k][j]     for i < n, j < ns, b < q.
+ * A: a factor buffer after plmc_potrf* / plmc_factorize*_ex (n_pad a multiple of plmc_block(), n <= n_pad <= lda); U is the ELEMENT-WISE
+ *   upper triangle of its columns [0, n_pad).  Only U[k][i] with k <= i < n is read: nothing below the diagonal of a diagonal block
+ *   (the sweep leaves the input there), nothing in the tiles below the block diagonal (never written), nothing in the augmented or W
+ *   columns, nothing in rows or columns >= n.  The mask is a select on loads from addresses clamped into the live triangle, not a
+ *   multiplication by 0: a NaN in any of those places does not reach Y.
+ * Z, Y: K-major (q, n, ns) with leading dimensions ldz, ldy >= ns and batch strides strideZ, strideY (strideZ = 0 shares one Z); no
+ *   alignment or padding is asked of them -- ns is padded to the tile inside the call.  Exactly Y[b][i][j] with i < n, j < ns is written.
+ *   Y must not overlap Z (the product is not in-place safe).  shift: (q, n) contiguous, or NULL for 0.
+ * Two paths, chosen from ns alone, both deterministic (fixed summation order, no atomics):
+ *   ns <= 16  HBM-bound, the walk of plmc_wt_matvec_* on the other triangle: U is read once for all ns columns, fp64 accumulators;
+ *   ns > 16   128 x 128 tiles on the matrix instructions of the element type, contraction range [0, 128 (ib + 1)) cut at n.
+ * Per element |Y - exact| <= (i + 4) u (sum_{k <= i} |U_ki| |Z_kj| + |shift_i|), u = 2^-24 / 2^-53 (tests/_trmm_ref.py).
+ * Argument errors (null A, Z or Y; n < 1, n > n_pad, ns < 1, q < 1; ldz < ns or ldy < ns; Y overlapping Z; a batch stride of Y that
+ * lets two latents share elements) fail through plmc_last_error() before anything is launched.  q n^2 ns flop.
+ */
+int plmc_trmm_ut_f32(const float *A, int64_t n_pad, int64_t lda, int64_t strideA, int n, const float *Z, int ns, int64_t ldz,
+                     int64_t strideZ, const float *shift, float *Y, int64_t ldy, int64_t strideY, int q, void *stream);
+int plmc_trmm_ut_f64(const double *A, int64_t n_pad, int64_t lda, int64_t strideA, int n, const double *Z, int ns, int64_t ldz,
+                     int64_t strideZ, const double *shift, double *Y, int64_t ldy, int64_t strideY, int q, void *stream);
+
+/*
  * Batched "TN" product on the tile engine:  C[b] (=, +=, -=) A[b]^T B[b]  with A: K x M and B: K x N, both stored
  * K-major (row index = contraction index), C: M x N; mode 0 store / 1 add / 2 subtract.  M, N multiples of plmc_block(),
  * K a multiple of 16 (callers pad with zeros), 16-byte aligned pointers / strides.  Replaces the torch.matmul (rocBLAS)

@@ -12,8 +12,9 @@ from ._engine import get_workspace
 from ._pivot import PivotCheck
 
 
-def _load(ws, M, R):
-    """M (q,m,m) -> upper-left block of the factor buffers (identity on the padding), R (q,k,m) -> augmented columns."""
+def _load(ws, M, R=None):
+    """M (q,m,m) -> upper-left block of the factor buffers (identity on the padding), R (q,k,m) -> augmented columns (None: a
+    workspace without any)."""
     L = _hip.lib()
     q, m = M.shape[0], M.shape[-1]
     sq = ws.A[:, :, :ws.n_pad]
@@ -22,16 +23,22 @@ def _load(ws, M, R):
     if ws.n_pad > m:
         idx = torch.arange(m, ws.n_pad, device=M.device)
         sq[:, idx, idx] = 1.0
+    if R is None:
+        return None
     Rc = R.contiguous()                  # (a transposed view makes a copy here: it must outlive the launch that reads it)
     L.call("plmc_write_rhs", ws.dtype, _hip.ptr(Rc), R.shape[1], m, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad,
            q, _hip.stream_ptr(ws.device))
     return Rc
 
 
-def _factor(ws, what):
+def _sweep(ws):
     L = _hip.lib()
     L.call("plmc_potrf", ws.dtype, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet),
            _hip.ptr(ws.info), int(ws.with_inverse), ws.q, _hip.stream_ptr(ws.device))
+
+
+def _factor(ws, what):
+    _sweep(ws)
     from . import settings
     if not settings.check_cholesky.on():       # no pivot check wanted: no host sync either
         return
@@ -84,6 +91,38 @@ def spd_half_solve(M, R):
         keep = _load(ws, M.detach(), R.detach().transpose(-1, -2))      # noqa: F841 (the copy lives until the sweep is queued)
         _factor(ws, "spd_half_solve")
         return ws.A[:, :m, ws.n_pad:ws.n_pad + k].clone()
+
+
+def spd_sample(M, Z, shift=None):
+    """Draws shift + U^T Z for dense SPD covariances M = U^T U (q,m,m), Z (q,m,ns) base samples, shift (q,m) | None -> (draws (q,m,ns),
+    jitter): the plain sweep on M, then the product against the factor where it lies (plmc_trmm_ut).  Posterior covariances
+    K** - V^T V of a noise-free latent are nearly singular, so a failed pivot walks the package's jitter ladder (_pivot.walk) on the
+    diagonal; `jitter` is what was added.  No gradient."""
+    from ._engine import trmm_ut
+    from ._pivot import walk
+    from . import settings
+    _hip.require_device(M, Z)
+    dt, dev = M.dtype, M.device
+    q, m = M.shape[0], M.shape[-1]
+    with torch.no_grad():
+        ws = get_workspace(m, q, 0, dt, dev, False)
+        Md, Zc = M.detach(), Z.detach().to(dt).contiguous()
+        sh = None if shift is None else shift.detach().to(dt).contiguous()
+        eye = torch.eye(m, dtype=dt, device=dev)
+
+        def attempt(jit):
+            _load(ws, Md + jit * eye)
+            _sweep(ws)
+            return PivotCheck.eager(ws), None
+
+        jitter = 0.0
+        _load(ws, Md)
+        _sweep(ws)
+        if settings.check_cholesky.on():       # (no pivot check wanted: no host sync either)
+            check = PivotCheck.eager(ws)
+            if check.failed():
+                jitter = walk(dt, check, attempt)[0]
+        return trmm_ut(ws, m, Zc, sh), jitter
 
 
 def _padded(t, rows, cols):

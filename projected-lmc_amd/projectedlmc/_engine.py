@@ -281,9 +281,11 @@ def _split_grad_table(g, ell_shape, os_shape):
     return g[:, :ne].reshape(ell_shape), g[:, ne], (None if os_shape is None else g[:, ne + 1:].reshape(os_shape))
 
 
-def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
+def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
     """Assemble Khat (+ rhs / cross-covariance columns) and run the blocked Cholesky.
-    rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info)."""
+    rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info).
+    eig_lo=False: `noise` is no eigenvalue bound to scale by (a jitter on a noise-free prior, sample_lazy): the fp32 sweep gets
+    eig_lo = NULL and takes the three-plane scheme, which needs none (include/plmc.h, plmc_potrf_ex_*)."""
     L = _hip.lib()
     dt, dev = ws.dtype, ws.device
     st = _hip.stream_ptr(dev)
@@ -304,18 +306,19 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
     # eig_lo = the noise variances: lambda_min(K + s2 I) >= s2 -- the bound the two-plane fp16 split of the bulk fp32 products
     # scales its operands with (include/plmc.h, plmc_potrf_ex_*); ignored by the fp64 entry point
     flags = (1 | (4 if ws.keep_planes else 0)) if ws.with_inverse else 0
+    bound = _hip.ptr(noise) if eig_lo else None
     if fused:
         _kernel_call(L, "plmc_factorize_ex", dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise), _hip.ptr(ws.A), ws.n_pad,
-                     ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st))
+                     ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, bound, st))
     else:
         L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
-               _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, _hip.ptr(noise), st)
+               _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, bound, st)
 
 
-def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
+def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
     """factorize + the jitter ladder (_pivot.walk) with the check read at once: on a non-PD pivot retry with noise + jitter.
     Returns the jitter that was added."""
-    factorize(kind, X, ell, oscale, noise, rhs, ws, Xs)
+    factorize(kind, X, ell, oscale, noise, rhs, ws, Xs, eig_lo)
     if not settings.check_cholesky.on():
         return 0.0
     check = PivotCheck.eager(ws)
@@ -323,7 +326,7 @@ def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None):
         return 0.0
 
     def attempt(jit):
-        factorize(kind, X, ell, oscale, noise + jit, rhs, ws, Xs)
+        factorize(kind, X, ell, oscale, noise + jit, rhs, ws, Xs, eig_lo)
         return PivotCheck.eager(ws), None
 
     return walk(ws.dtype, check, attempt)[0]
@@ -704,6 +707,42 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     from .kernels import prior_diagonal
     var = prior_diagonal(kind, Xsc, osc, q) - vsq                      # k(x*, x*) = 1 for the stationary kinds (additive: sum_g os_g)
     return mean, var
+
+
+def trmm_ut(ws, n, Z, shift=None):
+    """shift + U^T Z against the factor in ws.A where the sweep left it (plmc_trmm_ut): Z (q, n, ns) K-major, shift (q, n) | None ->
+    (q, n, ns).  Only the element-wise upper triangle of the leading n x n of the square part is read."""
+    L = _hip.lib()
+    q, ns = Z.shape[0], Z.shape[-1]
+    Y = torch.empty(q, n, ns, dtype=ws.dtype, device=ws.device)
+    L.call("plmc_trmm_ut", ws.dtype, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, n, _hip.ptr(Z), ns, ns, n * ns, _hip.ptr(shift),
+           _hip.ptr(Y), ns, n * ns, q, _hip.stream_ptr(ws.device))
+    return Y
+
+
+def sample_lazy(kind, X, ell, oscale, noise, Z, shift=None):
+    """Draws from q GP priors N(shift_i, os_i k(X, X; ell_i) + noise_i I) given base samples: factorise Khat = U^T U on the engine (any
+    kernel family _kernel_call serves), then shift + U^T Z (plmc_trmm_ut) -- the `MultivariateNormal(mean, kernel(X)).sample()` the
+    reference's synthetic study begins with (experiments.py:150-151).  Z (q, n, ns), shift (q, n) | None -> (draws (q, n, ns), jitter).
+    noise None (the reference's own call, a noise-free prior): settings.cholesky_jitter stands on the diagonal from the first attempt,
+    and the fp32 sweep is given no eigenvalue bound -- a jitter of 1e-6 is not one the two-plane fp16 scaling should be fed.  Further
+    rungs come from the one ladder (_pivot.walk).  `jitter` is everything that was added to the caller's diagonal.  No gradient."""
+    _hip.require_device(X, ell, Z)
+    L = _hip.lib()
+    dt, dev = Z.dtype, Z.device
+    q, n = Z.shape[0], Z.shape[1]
+    with torch.no_grad():
+        Xc, ellc, osc, nzc, Zc, sh = (_contig(t, dt) for t in (X, ell, oscale, noise, Z, shift))
+        _check_kernel_shape(L, ellc, kind)
+        ws = get_workspace(n, q, 0, dt, dev, False)
+        base = 0.0
+        if nzc is None:
+            base = settings.cholesky_jitter.value(dt)
+            nzc = torch.full((q,), base, dtype=dt, device=dev)
+        else:
+            nzc = nzc.reshape(-1)
+        jitter = base + factorize_checked(kind, Xc, ellc, osc, nzc, None, ws, eig_lo=noise is not None)
+        return trmm_ut(ws, n, Zc, sh), jitter
 
 
 def mix_posterior(mean_lat, var_lat, Ht, eps=0.0):
