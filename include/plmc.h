@@ -623,6 +623,80 @@ int plmc_loo_grad_lper_f64(const double *Xop, int64_t n_pad, int64_t krows, int6
                            void *partials, int q, void *stream);
 
 /*
+ * Sums of kernel families (what `k1 + k2` builds: trend + a seasonality that drifts + medium-term irregularity, two periodicities, ...)
+ * on the batched exact engine, the heterogeneous sum
+ *     Khat_i = sum_{g < ncomp} os[i][g] k_{fam[g]}(x, x'; table[i][g]) + noise[i] I,
+ *     1 <= ncomp <= plmc_sum_max_components() (4),   1 <= d <= plmc_sum_max_dim() (8, the smallest of the members' limits).
+ * Members.  `fam`: a HOST array of ncomp ints, read during the call and shared by the q latents: the kind codes 0 .. 3 (RBF, Matern 1/2,
+ *   3/2, 5/2) or one of the three codes below, which are disjoint from the kind codes.  The spline kind (4: not stationary, no bound
+ *   |K_ij| <= diagonal for the fp16 scales) and the spectral mixture (already a sum with its own weights) are not members.
+ * Table.  `table`: q x ncomp x (3 d + 1), contiguous, one record per latent and component:
+ *     [ ell: d | period: d | rbf_ell: d | alpha: 1 ]
+ *   A member reads only the slots it owns -- the ARD kinds ell; rational quadratic ell and alpha; periodic ell and period; locally periodic
+ *   ell, period and rbf_ell -- with the meaning they have in that family's own section above.  The other slots are NEVER READ (they may
+ *   hold NaN).  An owned lengthscale of +inf (1 / ell = 0 exactly) switches that dimension off for that component, as in the additive
+ *   table: it adds exactly 0 to the exponent or distance and its gradient entries are exactly 0, its period's included (for the locally
+ *   periodic member set ell and rbf_ell of that dimension).  `oscale`: q x ncomp, or NULL for all ones.  noise: q.
+ * Every entry point takes the arguments of its `_add` form with (kind, ..., ncomp, ell, oscale, ...) replaced by
+ * (..., ncomp, fam, table, oscale, ...) and does what that form does:
+ *   plmc_assemble_sum_*        plmc_assemble_cross_sum_*        plmc_factorize_sum_ex_*  (bit-identical to plmc_assemble_sum_* followed by
+ *   plmc_potrf_ex_*: factor buffer, log det, info)              plmc_kinv_grad_sum_vd_*  plmc_loo_grad_sum_*
+ * Values.  Each component's value comes from its family's own function (so the phase reduction, the raw-difference scaling and the single
+ *   accurate exponential of those sections carry over; x - x' is formed once per element) and the components are added in table order in
+ *   the element type: the fp32 assembly is within the sum of the members' bounds, each times its os, plus (ncomp - 1) 2^-24 sum_g os_g, of
+ *   the fp64 formula at the fp32 inputs.  The diagonal is sum_g os_g + noise, which is also the bound the sweep's fp16
+ *   scales need; eig_lo is treated as for every other family.
+ * One component.  ncomp = 1 IS the member's family: its own kernels run, so K, the factor buffer, values and gradients are bit-identical to
+ *   the single-family entry point (the gradient after the slots are re-laid), and the arithmetic of the fp32 gradient call is that
+ *   family's.
+ * Gradient table of plmc_kinv_grad_sum_vd_* and plmc_loo_grad_sum_* (double), ncomp (3 d + 2) + 1 entries per latent:
+ *     grad[latent] = [ d / d table: ncomp x (3 d + 1), in table layout | d / d noise | d / d oscale: ncomp ]
+ *   Every slot a member does not own is exactly 0.
+ *   plmc_kinv_grad_sum_vd_f32 with ncomp > 1 and d > 1 forms K^-1 with the fp32 matrix instructions whatever PLMC_SPLIT says, because the
+ *   periodic-phase members do (the knob and eig_lo are not looked at; no planes of W are needed); d = 1 follows the knob.
+ * Scratch.  `Vd`: as for plmc_kinv_grad_vd_*.  `partials`: plmc_sum_grad_partials_bytes(n_pad, q, ncomp, elem bytes) bytes, one row of
+ *   partial sums per tile and component plus 512 bytes per latent (the re-laid rows of a one-member sum); a function of its arguments
+ *   only, never of a dev knob.  The fp32 split engine takes the planes of W from the Vd of the sweep that produced W and refuses a call
+ *   without them; fp64 and PLMC_SPLIT=0 need no planes.
+ * Argument errors (plmc_last_error(), nothing is launched): ncomp or d beyond the limits, an unknown or spline member code, null `fam` or
+ *   `table`.
+ */
+#define PLMC_FAM_PERIODIC 16                  /* member codes of a sum beside the kind codes 0 .. 3 */
+#define PLMC_FAM_RQ 17
+#define PLMC_FAM_LPER 18
+int plmc_sum_max_components(void);            /* most members of a sum (4) */
+int plmc_sum_max_dim(void);                   /* largest input dimension of a sum (8) */
+int64_t plmc_sum_grad_partials_bytes(int64_t n_pad, int q, int ncomp, int elem_bytes);
+int plmc_assemble_sum_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, const float *noise,
+                          float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_sum_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
+                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_sum_f32(const float *X, int n, const float *Xs, int ns, int d, int ncomp, const int *fam, const float *table,
+                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_assemble_cross_sum_f64(const double *X, int n, const double *Xs, int ns, int d, int ncomp, const int *fam, const double *table,
+                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_factorize_sum_ex_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, const float *noise,
+                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_sum_ex_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
+                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_sum_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              int ncomp, const int *fam, const float *table, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_sum_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              int ncomp, const int *fam, const double *table, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+int plmc_loo_grad_sum_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                          int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, double *grad, void *partials,
+                          int q, void *stream);
+int plmc_loo_grad_sum_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                          int n, int d, int ncomp, const int *fam, const double *table, const double *oscale, double *grad, void *partials,
+                          int q, void *stream);
+
+/*
  * Leave-one-out objective (LeaveOneOutPseudoLikelihood, projected_lmc.py:86-105): with P = Khat^-1, alpha = P y, p_i = P_ii,
  *     L = sum_i [ 1/2 log p_i - 1/2 alpha_i^2 / p_i ] - n/2 log 2 pi,
  *     c_i = 1/2 / p_i + 1/2 alpha_i^2 / p_i^2,   g_i = -alpha_i / p_i,   u = P g = dL / dy,

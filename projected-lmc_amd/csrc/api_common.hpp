@@ -17,6 +17,11 @@ constexpr int SM_MAX_DIM = 8;        // largest input dimension of a spectral-mi
 constexpr int PER_MAX_DIM = 8;       // largest input dimension of a periodic kernel (plmc_per_max_dim())
 constexpr int RQ_MAX_DIM = 16;       // largest input dimension of a rational-quadratic kernel (plmc_rq_max_dim())
 constexpr int LPER_MAX_DIM = 8;      // largest input dimension of a locally periodic kernel (plmc_lper_max_dim())
+constexpr int SUM_MAX_DIM = 8;       // largest input dimension of a heterogeneous sum (plmc_sum_max_dim()): the smallest of its members' limits
+// member families of a heterogeneous sum beside the stationary kinds K_RBF .. K_MATERN52: the public codes of include/plmc.h
+// (PLMC_FAM_*) and the 4-bit codes the kernels get, packed one nibble per component
+constexpr int FAM_PUBLIC_BASE = 16;  // PLMC_FAM_PERIODIC; PLMC_FAM_RQ and PLMC_FAM_LPER follow
+enum { F_PER = 5, F_RQ = 6, F_LPER = 7 };
 
 char *err_buf();                     // thread-local, defined in api.hip
 
@@ -77,13 +82,19 @@ const Knobs &knobs();
 //   RQ     rational quadratic: ell = its lengthscales (q, d), second = its alpha (q), oscale (q) | null
 //   LPER   locally periodic (periodic x RBF): ell = its periodic lengthscales, second = its periods, third = its RBF lengthscales (q, d
 //          each), oscale (q) | null
-// `kind` is not looked at for SM, PER, RQ and LPER; the pointers are of the call's element type.  `third` is null for every other family.
-enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER };
+//   SUM    heterogeneous sum of ncomp <= MAX_COMP members: ell = its table (q, ncomp, 3 d + 1), one record [ell | period | rbf_ell: d each |
+//          alpha] per component, oscale (q, ncomp) | null; `fams` = the members' 4-bit codes (K_RBF .. K_MATERN52, F_PER, F_RQ, F_LPER), component g
+//          in bits 4 g .. 4 g + 3, read from the caller's host array when the table is built (CovTable::sum)
+// `kind` is not looked at for SM, PER, RQ, LPER and SUM; the pointers are of the call's element type.  `third` is null for every other family.
+enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER, COV_SUM };
 struct CovTable {
   CovFamily family;
   int kind, d, ncomp;
   const void *ell, *second, *oscale;
   const void *third = nullptr;
+  int fams = 0;                      // SUM only; < 0: the member list was refused (check()): -1 unknown code, -2 spline, -3 no list
+  bool of_sum = false;               // the one member of a one-component sum, routed to its own family (member()): its gradient calls keep
+                                     // scratch behind the partial sums, so they take the planes of W from the sweep's Vd only
   static CovTable plain(int kind, int d, const void *ell, const void *oscale) { return {COV_PLAIN, kind, d, 1, ell, nullptr, oscale}; }
   static CovTable add(int kind, int d, int ncomp, const void *ell, const void *oscale) { return {COV_ADD, kind, d, ncomp, ell, nullptr, oscale}; }
   static CovTable sm(int d, int nmix, const void *scales, const void *means, const void *weights) { return {COV_SM, 0, d, nmix, scales, means, weights}; }
@@ -92,8 +103,46 @@ struct CovTable {
   static CovTable lper(int d, const void *ell, const void *period, const void *rbf_ell, const void *oscale) {
     return {COV_LPER, 0, d, 1, ell, period, oscale, rbf_ell};
   }
+  // `fam`: HOST array of ncomp public codes (kind codes 0 .. 3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER)
+  static CovTable sum(int d, int ncomp, const int *fam, const void *table, const void *oscale) {
+    CovTable t{COV_SUM, 0, d, ncomp, table, nullptr, oscale};
+    if (!fam) t.fams = -3;
+    if (!fam || ncomp < 1 || ncomp > MAX_COMP) return t;          // (check() names what is wrong)
+    for (int g = 0; g < ncomp; ++g) {
+      const int f = fam[g];
+      int code;
+      if (f >= K_RBF && f <= K_MATERN52) code = f;
+      else if (f >= FAM_PUBLIC_BASE && f <= FAM_PUBLIC_BASE + 2) code = F_PER + (f - FAM_PUBLIC_BASE);
+      else { t.fams = f == K_SPLINE ? -2 : -1; return t; }
+      t.fams |= code << (4 * g);
+    }
+    return t;
+  }
+  int fam_of(int g) const { return (fams >> (4 * g)) & 15; }
+  // a one-component sum IS its member: that family's table for q latents whose rows are `stride` elements apart -- (q, d) contiguous rows
+  // need stride = d, so the sum's own records (stride 3 d + 1) serve one latent at a time (lat0, q = 1) and re-laid rows serve all
+  CovTable member(const void *ell_, const void *period_, const void *rbf_, const void *alpha_, const void *os_) const {
+    const int f = fam_of(0);
+    CovTable t = f == F_PER ? per(d, ell_, period_, os_) : f == F_RQ ? rq(d, ell_, alpha_, os_) : f == F_LPER ? lper(d, ell_, period_, rbf_, os_)
+                                                                                                          : plain(f, d, ell_, os_);
+    t.of_sum = true;
+    return t;
+  }
+  template <typename T> CovTable member_of_latent(int lat) const {
+    const T *rec = (const T *)ell + (int64_t)lat * (3 * d + 1);
+    return member(rec, rec + d, rec + 2 * d, rec + 3 * d, oscale ? (const T *)oscale + lat : nullptr);
+  }
+  bool single_member() const { return family == COV_SUM && ncomp == 1; }
   // the family's limits: the message of the first one missed, or null
   const char *check() const {
+    if (family == COV_SUM) {
+      if (ncomp < 1 || ncomp > MAX_COMP) return "need 1 <= components <= plmc_sum_max_components()";
+      if (d <= 0 || d > SUM_MAX_DIM) return "need 0 < d <= plmc_sum_max_dim()";
+      if (fams == -3 || !ell) return "null pointer";
+      if (fams == -2) return "the spline kernel is not a member of a sum (members: the stationary kinds 0..3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER)";
+      if (fams < 0) return "unknown member family code (members: the stationary kinds 0..3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER; no spectral mixture)";
+      return nullptr;
+    }
     if (family == COV_ADD) {
       if (kind < 0 || kind > K_MATERN52) return "additive kernels take the stationary kinds only (no spline kernel)";
       if (ncomp < 1 || ncomp > MAX_COMP) return "need 1 <= components <= plmc_max_components()";
@@ -114,7 +163,7 @@ struct CovTable {
   // plain instantiations, bit for bit
   CovFamily route() const { return family == COV_ADD && ncomp == 1 ? COV_PLAIN : family; }
   // rows of GP partial-sum slots per tile that the K^-1 + gradient kernels write (potri_grad.hip)
-  int partials_rows() const { return family == COV_ADD || family == COV_SM ? ncomp : 1; }
+  int partials_rows() const { return family == COV_ADD || family == COV_SM || family == COV_SUM ? ncomp : 1; }
 };
 #define PLMC_REQUIRE_TABLE(t) \
   do { if (const char *why_ = (t).check()) return plmc::fail(__func__, why_); } while (0)

@@ -495,8 +495,105 @@ template <typename T, int DCAP> struct LperTable {
   }
 };
 
+// The heterogeneous sum (CovTable SUM): per latent and component one record [ell | period | rbf_ell: d each | alpha] and an output scale |
+// null; `fams` holds the members' 4-bit codes.  A member reads only the slots it owns (ARD kinds: ell; rational quadratic: ell, alpha;
+// periodic: ell, period; locally periodic: ell, period, rbf_ell), the others may hold anything.  In LDS, per component (stride REC):
+// ip = 1 / p, its residual ipr, w = 1 / ell, v = 1 / rbf_ell [DCAP] each (0 where not owned and beyond d), alpha, 1 / (2 alpha), os.
+// Every component's value comes from its own family's function (kern_value*, rq_profile, per_value, lper_value); the components are added
+// in table order.
+template <typename T, int DCAP> struct SumPairValue {
+  static constexpr int REC = 4 * DCAP + 3;
+  const T *par;
+  int fams, G;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    typedef Pair<T> T2;
+    T2 sum = {T(0), T(0)};
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      const int f = (fams >> (4 * g)) & 15;
+      const T *pg = par + g * REC;
+      const T os = pg[4 * DCAP + 2];
+      if (f == F_PER || f == F_LPER) {
+        T b0[DCAP], b1[DCAP];
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) { b0[k] = xc[k].x; b1[k] = xc[k].y; }
+        if (f == F_PER) sum += os * T2{per_value<T, DCAP>(xr, b0, pg, pg + DCAP, pg + 2 * DCAP), per_value<T, DCAP>(xr, b1, pg, pg + DCAP, pg + 2 * DCAP)};
+        else sum += os * T2{lper_value<T, DCAP>(xr, b0, pg, pg + DCAP, pg + 2 * DCAP, pg + 3 * DCAP),
+                            lper_value<T, DCAP>(xr, b1, pg, pg + DCAP, pg + 2 * DCAP, pg + 3 * DCAP)};
+      } else {
+        T2 r2 = {T(0), T(0)};
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) {
+          const T2 sd = (xr[k] - xc[k]) * pg[2 * DCAP + k];
+          r2 += sd * sd;
+        }
+        if (f == F_RQ) sum += os * T2{rq_profile(r2.x, pg[4 * DCAP], pg[4 * DCAP + 1]), rq_profile(r2.y, pg[4 * DCAP], pg[4 * DCAP + 1])};
+        else sum += os * kern_value_pair<T>(f, r2);
+      }
+    }
+    return sum;
+  }
+};
+template <typename T, int DCAP> struct SumTable {
+  static constexpr int REC = 4 * DCAP + 3;
+  static constexpr int LDS = MAX_COMP * REC;
+  int fams, G;
+  const T *table, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < G * DCAP) {
+      const int g = tid / DCAP, k = tid % DCAP;
+      const int f = (fams >> (4 * g)) & 15;
+      const T *rec = table + ((int64_t)lat * G + g) * (3 * d + 1);
+      T ip = T(0), ipr = T(0);
+      if (k < d && (f == F_PER || f == F_LPER)) per_inv_period(rec[d + k], ip, ipr);
+      T *pg = par + g * REC;
+      pg[k] = ip;
+      pg[DCAP + k] = ipr;
+      pg[2 * DCAP + k] = k < d ? T(1) / rec[k] : T(0);
+      pg[3 * DCAP + k] = (k < d && f == F_LPER) ? T(1) / rec[2 * d + k] : T(0);
+      if (k == 0) {
+        const T a = f == F_RQ ? rec[3 * d] : T(1);
+        pg[4 * DCAP] = a;
+        pg[4 * DCAP + 1] = T(0.5) / a;
+        pg[4 * DCAP + 2] = oscale ? oscale[(int64_t)lat * G + g] : T(1);
+      }
+    }
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, SumPairValue<T, DCAP>{par, fams, G}, nz, Al, lda, ib, jb, n, edge);
+  }
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T a[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) a[k] = xa[k];
+    T val = T(0);
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+      const int f = (fams >> (4 * g)) & 15;
+      const T *pg = par + g * REC;
+      T v;
+      if (f == F_PER) v = per_value<T, DCAP>(a, xs, pg, pg + DCAP, pg + 2 * DCAP);
+      else if (f == F_LPER) v = lper_value<T, DCAP>(a, xs, pg, pg + DCAP, pg + 2 * DCAP, pg + 3 * DCAP);
+      else if (f == F_RQ) v = rq_value<T, DCAP>(a, xs, pg + 2 * DCAP, pg[4 * DCAP], pg[4 * DCAP + 1]);
+      else {
+        T r2 = T(0);
+#pragma unroll
+        for (int k = 0; k < DCAP; ++k) {
+          const T sd = (a[k] - xs[k]) * pg[2 * DCAP + k];
+          r2 += sd * sd;
+        }
+        v = kern_value<T>(f, r2);
+      }
+      val += pg[4 * DCAP + 2] * v;
+    }
+    return val;
+  }
+};
+
 // d <= 8 (DCAP in {4, 8}; spectral mixture, periodic, locally periodic and rational quadratic also 1; rational quadratic also 16);
-// P: AddTable / SmTable / PerTable / RqTable / LperTable
+// P: AddTable / SmTable / PerTable / RqTable / LperTable / SumTable
 template <typename T, int DCAP, class P>
 __global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
                                                                     const T *__restrict__ noise, T *__restrict__ A,
@@ -632,6 +729,7 @@ template <typename T, int DC> RqTable<T, DC> rq_table(const CovTable &t) { retur
 template <typename T, int DC> LperTable<T, DC> lper_table(const CovTable &t) {
   return {(const T *)t.ell, (const T *)t.second, (const T *)t.third, (const T *)t.oscale};
 }
+template <typename T, int DC> SumTable<T, DC> sum_table(const CovTable &t) { return {t.fams, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
 
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
@@ -639,9 +737,17 @@ template <typename T>
 int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, int64_t lda, int64_t strideA, int q, void *stream,
                   int ib0 = 0, int nrows = -1, int ncols = -1, int skip = 0) {
   PLMC_REQUIRE_TABLE(t);
+  if (t.single_member()) {            // a sum of one member IS that member: its own kernels, one latent at a time (the records are 3 d + 1 apart)
+    PLMC_REQUIRE(noise && A && q > 0, "null pointer");
+    for (int lat = 0; lat < q; ++lat)
+      if (int rc = assemble_impl<T>(t.member_of_latent<T>(lat), X, n, noise + lat, A + (int64_t)lat * strideA, lda, strideA, 1, stream, ib0, nrows,
+                                    ncols, skip))
+        return rc;
+    return 0;
+  }
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
-  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER;   // d <= 8 (rational quadratic: 16) by the family's limit
+  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER || t.family == COV_SUM;   // d <= 8 (rational quadratic: 16) by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
   PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
@@ -696,6 +802,11 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
       else if (d <= 4) table(lper_table<T, 4>(t));
       else table(lper_table<T, 8>(t));
       break;
+    case COV_SUM:
+      if (d == 1) table(sum_table<T, 1>(t));
+      else if (d <= 4) table(sum_table<T, 4>(t));
+      else table(sum_table<T, 8>(t));
+      break;
   }
   return launch_status(__func__);
 }
@@ -721,6 +832,13 @@ template <typename T>
 int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int ns, T *Out, int64_t ldo, int64_t strideO, int64_t col0,
                         int64_t n_rows, int q, void *stream) {
   PLMC_REQUIRE_TABLE(t);
+  if (t.single_member()) {            // (see assemble_impl)
+    PLMC_REQUIRE(Out && q > 0, "null pointer");
+    for (int lat = 0; lat < q; ++lat)
+      if (int rc = assemble_cross_impl<T>(t.member_of_latent<T>(lat), X, n, Xs, ns, Out + (int64_t)lat * strideO, ldo, strideO, col0, n_rows, 1, stream))
+        return rc;
+    return 0;
+  }
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
@@ -768,6 +886,11 @@ int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int n
       if (d == 1) table(lper_table<T, 1>(t));
       else if (d <= 4) table(lper_table<T, 4>(t));
       else table(lper_table<T, 8>(t));
+      break;
+    case COV_SUM:
+      if (d == 1) table(sum_table<T, 1>(t));
+      else if (d <= 4) table(sum_table<T, 4>(t));
+      else table(sum_table<T, 8>(t));
       break;
   }
   return launch_status(__func__);
@@ -880,6 +1003,20 @@ int plmc_lper_max_dim(void) { return plmc::LPER_MAX_DIM; }
 PLMC_LPER_ENTRY(f32, float)
 PLMC_LPER_ENTRY(f64, double)
 #undef PLMC_LPER_ENTRY
+int plmc_sum_max_components(void) { return plmc::MAX_COMP; }
+int plmc_sum_max_dim(void) { return plmc::SUM_MAX_DIM; }
+#define PLMC_SUM_ENTRY(SUF, T)                                                                                                                 \
+  int plmc_assemble_sum_##SUF(const T *X, int n, int d, int ncomp, const int *fam, const T *table, const T *oscale, const T *noise, T *A,      \
+                              int64_t lda, int64_t strideA, int q, void *stream) {                                                             \
+    return plmc::assemble_impl<T>(CovTable::sum(d, ncomp, fam, table, oscale), X, n, noise, A, lda, strideA, q, stream);                       \
+  }                                                                                                                                            \
+  int plmc_assemble_cross_sum_##SUF(const T *X, int n, const T *Xs, int ns, int d, int ncomp, const int *fam, const T *table, const T *oscale, \
+                                    T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                 \
+    return plmc::assemble_cross_impl<T>(CovTable::sum(d, ncomp, fam, table, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream); \
+  }
+PLMC_SUM_ENTRY(f32, float)
+PLMC_SUM_ENTRY(f64, double)
+#undef PLMC_SUM_ENTRY
 int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
                           const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
   return plmc::assemble_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);

@@ -4,6 +4,8 @@
 #include "kinv_epilogue_per.inc"
   } else if constexpr (F == COV_LPER) {
 #include "kinv_epilogue_lper.inc"
+  } else if constexpr (F == COV_SUM) {
+#include "kinv_epilogue_sum.inc"
   } else if constexpr (F == COV_RQ) {
 #include "kinv_epilogue_rq.inc"
   } else if constexpr (F == COV_SM) {

@@ -1544,6 +1544,24 @@ int plmc_factorize_lper_ex_f64(const double *X, int n, int d, const double *ell,
   PLMC_REQUIRE_TABLE(job.table);
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
+// The same for a heterogeneous sum (plmc_assemble_sum_*): the job carries the table and the members read from the host array `fam`
+int plmc_factorize_sum_ex_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, const float *noise,
+                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
+                              int with_inverse, int q, const float *eig_lo, void *stream) {
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  const plmc::AssembleJob job{plmc::CovTable::sum(d, ncomp, fam, table, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
+  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
+}
+int plmc_factorize_sum_ex_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
+                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
+  (void)eig_lo;
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  const plmc::AssembleJob job{plmc::CovTable::sum(d, ncomp, fam, table, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
+  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
+}
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

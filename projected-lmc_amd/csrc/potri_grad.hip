@@ -249,6 +249,8 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // COV_LPER: a locally periodic kernel of up to DC (1, 4, 8) input dimensions (kinv_epilogue_lper.inc): ell = its periodic lengthscales,
 // `means` its periods, `third` its RBF lengthscales, oscale (q) or null; `kind` and ncomp (1) are not looked at.  No other family reads
 // `third`.
+// COV_SUM: a heterogeneous sum of ncomp (2 .. MAX_COMP) members on up to DC (1, 4, 8) input dimensions (kinv_epilogue_sum.inc): `kind` =
+// the members' 4-bit codes, ell = its table (q, ncomp, 3 d + 1), oscale (q, ncomp) or null; `means` and `third` are not looked at.
 template <typename T, CovFamily F, int DC>
 __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *smem, const int tid, const bool live, int kind, int ncomp, int ib, int jb,
                                                        int lat, int m, int64_t n_pad, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
@@ -260,7 +262,7 @@ __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *sme
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || ((F == COV_PER || F == COV_LPER) && DC > 1)) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
@@ -423,6 +425,47 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_lper(const double *__res
   }
 }
 
+// The reduction for the heterogeneous sum: the tile's partials are `ncomp` rows of GP slots, each in the slot layout of its member's
+// family (kinv_epilogue_sum.inc; for one component: the row that family's own kernel writes).  grid (q, ncomp).
+// grad[lat]: [ d/d table (ncomp x (3 d + 1), in table layout) | d/d noise | d/d oscale (ncomp) ], each entry with the scaling of its
+// family's reduction (k_reduce_grad, _per, _rq, _lper); a slot its member does not own is written as exactly 0.
+template <typename T>
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_sum(const double *__restrict__ partials, int m, int d, int ncomp, int fams,
+                                                            const T *__restrict__ table, double *__restrict__ grad) {
+  const int g = blockIdx.y;
+  const int64_t tstride = (int64_t)ncomp * GP;
+  PLMC_REDUCE_TILES(tstride, (int64_t)g * GP);
+  const int f = (fams >> (4 * g)) & 15;
+  const int rec = 3 * d + 1, j = threadIdx.x;
+  double *gl = grad + (int64_t)lat * (ncomp * (rec + 1) + 1);
+  const T *tb = table + ((int64_t)lat * ncomp + g) * rec;
+  const auto total = [&](int slot) {
+    double tot = 0.0;
+    for (int gq = 0; gq < RED_NT / GP; ++gq) tot += red[gq * GP + slot];
+    return tot;
+  };
+  if (j < rec) {                         // one table slot per thread: row 0 ell, 1 period, 2 rbf_ell (d each), then alpha
+    const int row = j / d, kk = j - row * d;
+    double v = 0.0;
+    if (row == 0) {
+      const double tot = total(kk), l = (double)tb[kk];
+      v = (f == F_PER || f == F_LPER) ? 0.5 * tot / (l * l) : 0.5 * tot / l;
+    } else if (row == 1 && (f == F_PER || f == F_LPER)) {
+      const double tot = total(SUM_MAX_DIM + kk), l = (double)tb[kk], p = (double)tb[d + kk];
+      v = 0.5 * tot * SM_2PI / (l * p * p);
+    } else if (row == 2 && f == F_LPER) {
+      v = 0.5 * total(2 * SUM_MAX_DIM + kk) / (double)tb[2 * d + kk];
+    } else if (row == 3 && f == F_RQ) {
+      v = -0.5 * total(RQ_MAX_DIM);
+    }
+    gl[g * rec + j] = v;
+  } else if (j == MAX_DIM) {
+    if (g == 0) gl[ncomp * rec] = 0.5 * total(MAX_DIM);
+  } else if (j == MAX_DIM + 1) {
+    gl[ncomp * rec + 1 + g] = 0.5 * total(MAX_DIM + 1);
+  }
+}
+
 // Split of the inverse factor for the split-engine gradient kernel: W (fp32, lower block triangle: block (lb, cb) with
 // cb <= lb) -> k8-ordered planes Wp[latent][k / 8][plane][n_pad columns][k % 8] (bf3_engine.hpp), every value times the
 // latent's scale `wscale` (SplitH2: 2^13 / bound of |W|, written by k_w_scale; SplitB3: 1).
@@ -452,15 +495,16 @@ __global__ void k_w_scale(const float *__restrict__ eig_lo, float *__restrict__ 
 
 // S: split scheme of the W^T W products (void: MFMA of the element type); eig_lo: see potrf_impl.
 // `partials` is table.partials_rows() rows of GP slots per tile and `grad` as wide as the family's reduction kernel writes it.
+// check_only: return after the argument checks, before the first launch (sum_single_member).
 template <typename T, class S>
 int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n, double *grad,
                    T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag, void *partials, int q, const float *eig_lo, void *stream,
-                   const float *Vd = nullptr, int64_t lda_vd = 0) {
+                   const float *Vd = nullptr, int64_t lda_vd = 0, bool check_only = false) {
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
-  const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
+  const int kind = table.family == COV_SUM ? table.fams : table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();   // (SUM: the kernels' `kind` carries the members)
   const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
-  PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
+  PLMC_REQUIRE(table.kind >= 0 && table.kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ldw % NB == 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
   PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
@@ -479,12 +523,16 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     const unsigned short *wp = nullptr;
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
-    if (!(Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat))) {
-      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER,
-                   family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+    const bool from_vd = Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat);
+    if (!from_vd)
+      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER && family != COV_SUM && !table.of_sum,
+                   family == COV_SUM || table.of_sum ? "the sum gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                   : family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_LPER ? "the locally periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_RQ ? "the rational-quadratic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                                       : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
+    if (check_only) return 0;
+    if (!from_vd) {
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * rows * GP * (int64_t)sizeof(double);
       unsigned short *wpo = reinterpret_cast<unsigned short *>(pb);
       float *wsco = reinterpret_cast<float *>(pb + (int64_t)q * b3_elems<SplitB3>(n_pad, n_pad) * 2);
@@ -508,6 +556,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     switch (family) {
       case COV_PER: PLMC_LAUNCH_TB(COV_PER, 1); break;     // (d = 1 only: kinv_grad_f32_any)
       case COV_LPER: PLMC_LAUNCH_TB(COV_LPER, 1); break;   // (d = 1 only: kinv_grad_f32_any)
+      case COV_SUM: PLMC_LAUNCH_TB(COV_SUM, 1); break;     // (d = 1 only: kinv_grad_f32_any)
       case COV_RQ:                                         // (three planes: d = 1 only, kinv_grad_f32_any -- DC = 4 / 8 would spill there)
         if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_RQ, 1);
         else if (d == 1) PLMC_LAUNCH_TB(COV_RQ, 1);
@@ -526,6 +575,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
 #undef PLMC_LAUNCH_TB
 #undef PLMC_LAUNCH_KB
   } else {
+    if (check_only) return 0;
     const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);          // longest tiles first (see the kernel)
 #define PLMC_LAUNCH_KG(DC, SP)                                                                                       \
   hipLaunchKernelGGL((k_kinv_grad<T, DC, SP>), grid, block, 0, st, kind, W, n_pad, ldw, strideW, alpha, X, n, d, ell, \
@@ -537,6 +587,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_TG(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_PER, 4); else PLMC_LAUNCH_TG(COV_PER, 8); break;
       case COV_LPER: if (d == 1) PLMC_LAUNCH_TG(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_LPER, 4); else PLMC_LAUNCH_TG(COV_LPER, 8); break;
+      case COV_SUM: if (d == 1) PLMC_LAUNCH_TG(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SUM, 4); else PLMC_LAUNCH_TG(COV_SUM, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_TG(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_RQ, 8); else PLMC_LAUNCH_TG(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
@@ -554,6 +605,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
       case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
+      case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
@@ -603,7 +655,7 @@ __global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, (sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || ((F == COV_PER || F == COV_LPER) && DC > 1)) ? 1 : 2)) void k_loo_grad_add(
+__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_loo_grad_add(
     int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
     const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
     const T *__restrict__ means, const T *__restrict__ third) {
@@ -666,12 +718,12 @@ __global__ __launch_bounds__(NTHREADS) void k_loo_operand(const T *__restrict__ 
 // The sibling of kinv_grad_impl<T, void> for the leave-one-out gradient: the same table, the same partial sums, the same reductions.
 template <typename T>
 int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,
-                  double *grad, void *partials, int q, void *stream) {
+                  double *grad, void *partials, int q, void *stream, bool check_only = false) {
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
-  const int kind = table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
+  const int kind = table.family == COV_SUM ? table.fams : table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();   // (SUM: the kernels' `kind` carries the members)
   const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
-  PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
+  PLMC_REQUIRE(table.kind >= 0 && table.kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(Xop && beta && X && ell && grad && partials, "null pointer");
   PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && n > 0 && n <= n_pad && n > n_pad - NB, "n_pad must be plmc_pad(n)");
   PLMC_REQUIRE(krows > 0 && krows % BK == 0 && krows < ((int64_t)1 << 31), "krows must be a positive multiple of 16");
@@ -679,6 +731,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
   PLMC_REQUIRE(q == 1 || strideX >= krows * ldx, "strideX too small");
   PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
   PLMC_REQUIRE(aligned16(Xop) && strideX % (16 / (int64_t)sizeof(T)) == 0, "unaligned Xop");
+  if (check_only) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int m = (int)(n_pad / NB);
   double *part = reinterpret_cast<double *>(partials);
@@ -694,6 +747,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
     switch (family) {
       case COV_PER: if (d == 1) PLMC_LAUNCH_LT(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_PER, 4); else PLMC_LAUNCH_LT(COV_PER, 8); break;
       case COV_LPER: if (d == 1) PLMC_LAUNCH_LT(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_LPER, 4); else PLMC_LAUNCH_LT(COV_LPER, 8); break;
+      case COV_SUM: if (d == 1) PLMC_LAUNCH_LT(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SUM, 4); else PLMC_LAUNCH_LT(COV_SUM, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_LT(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_RQ, 8); else PLMC_LAUNCH_LT(COV_RQ, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
@@ -711,6 +765,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
     switch (family) {
       case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
       case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
+      case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
@@ -737,6 +792,56 @@ int loo_operand_impl(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK,
   return launch_status(__func__);
 }
 
+// ---- a heterogeneous sum of ONE member is that member's family: its own kernels run on the whole batch, bit for bit.  They read (q, d)
+// rows, the sum's records are 3 d + 1 apart, so the owned slots are re-laid behind the partial sums (SUM_TAIL_BYTES per latent, counted
+// by plmc_sum_grad_partials_bytes): rows [ell | period | rbf_ell: q x d each | alpha: q], then the family's gradient table, which
+// k_sum_member_grad copies into the sum's layout.  A slot the member does not own is neither read nor left unwritten (exactly 0).
+constexpr int64_t SUM_TAIL_BYTES = 512;
+static_assert((3 * SUM_MAX_DIM + 1) * 8 <= 256 && (3 * SUM_MAX_DIM + 2) * 8 <= 256, "one-member scratch of a sum");
+template <typename T>
+__global__ void k_sum_member_rows(int f, int d, int q, const T *__restrict__ table, T *__restrict__ rows) {
+  const int rec = 3 * d + 1;
+  for (int e = threadIdx.x; e < q * rec; e += blockDim.x) {
+    const int lat = e / rec, j = e - lat * rec, row = j / d, kk = j - row * d;
+    const bool owned = row == 0 || (row == 1 && (f == F_PER || f == F_LPER)) || (row == 2 && f == F_LPER) || (row == 3 && f == F_RQ);
+    T *dst = row < 3 ? rows + ((int64_t)row * q + lat) * d + kk : rows + (int64_t)3 * q * d + lat;
+    *dst = owned ? table[e] : T(0);
+  }
+}
+// family layouts: [ell: d | noise | os], periodic [ell | period | noise | os], rational quadratic [ell | alpha | noise | os], locally periodic
+// [ell | period | rbf_ell | noise | os]  ->  [ell | period | rbf_ell | alpha | noise | os]
+__global__ void k_sum_member_grad(int f, int d, int q, const double *__restrict__ fg, double *__restrict__ grad) {
+  const int wf = f == F_PER ? 2 * d + 2 : f == F_RQ ? d + 3 : f == F_LPER ? 3 * d + 2 : d + 2, ws = 3 * d + 3;
+  for (int e = threadIdx.x; e < q * ws; e += blockDim.x) {
+    const int lat = e / ws, j = e - lat * ws;
+    int src = -1;
+    if (j < d) src = j;
+    else if (j < 2 * d) src = (f == F_PER || f == F_LPER) ? j : -1;
+    else if (j < 3 * d) src = f == F_LPER ? j : -1;
+    else if (j == 3 * d) src = f == F_RQ ? d : -1;
+    else src = wf - 2 + (j - (3 * d + 1));
+    grad[e] = src >= 0 ? fg[(int64_t)lat * wf + src] : 0.0;
+  }
+}
+// `call(member table, its gradient table, check_only)` runs the member family's gradient path, or its argument checks alone: they run
+// first, so a refused call has launched nothing
+template <typename T, class Call>
+int sum_single_member(const CovTable &t, int64_t n_pad, int q, double *grad, void *partials, void *stream, Call call) {
+  PLMC_REQUIRE_TABLE(t);
+  PLMC_REQUIRE(grad && partials && q > 0 && n_pad > 0, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int f = t.fam_of(0), d = t.d;
+  char *tail = reinterpret_cast<char *>(partials) + (n_pad / NB) * (n_pad / NB) * (int64_t)q * GP * (int64_t)sizeof(double);
+  T *rows = reinterpret_cast<T *>(tail);
+  double *fg = reinterpret_cast<double *>(tail + (SUM_TAIL_BYTES / 2) * q);
+  const CovTable mt = t.member(rows, rows + (int64_t)q * d, rows + (int64_t)2 * q * d, rows + (int64_t)3 * q * d, t.oscale);
+  if (int rc = call(mt, fg, true)) return rc;
+  hipLaunchKernelGGL(k_sum_member_rows<T>, dim3(1), dim3(256), 0, st, f, d, q, (const T *)t.ell, rows);
+  if (int rc = call(mt, fg, false)) return rc;
+  hipLaunchKernelGGL(k_sum_member_grad, dim3(1), dim3(256), 0, st, f, d, q, (const double *)fg, grad);
+  return launch_status(__func__);
+}
+
 }  // namespace plmc
 
 extern "C" {
@@ -755,7 +860,7 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
 // the fp32 call by the arithmetic of its products (PLMC_SPLIT); Vd: the scratch of the sweep that produced W, or null
 static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
                              const float *X, int n, double *grad, float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                             const float *eig_lo, void *stream, const float *Vd = nullptr) {
+                             const float *eig_lo, void *stream, const float *Vd = nullptr, bool check_only = false) {
   const int split = plmc::knobs().split;
   // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
   // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
@@ -763,20 +868,23 @@ static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_
   // complements and 2 d sums live and follows the same rule, and so does the locally periodic kernel (3 d sums).  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
   // every d; beside the three bf16 planes (PLMC_SPLIT=3, or no eig_lo) it fits at d = 1 only, so d > 1 takes the fp32 products there.
   const bool three_planes = !(split == 2 && eig_lo);
-  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER || table.family == plmc::COV_LPER) && table.d > 1) ||
+  // A heterogeneous sum may hold a periodic or a locally periodic member and follows their rule whatever its members are.
+  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER || table.family == plmc::COV_LPER || table.family == plmc::COV_SUM) && table.d > 1) ||
       (table.family == plmc::COV_RQ && table.d > 1 && three_planes))
-    return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
+    return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream,
+                                             nullptr, 0, check_only);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
   if (split == 2 && eig_lo)
     return plmc::kinv_grad_impl<float, plmc::SplitH2>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo,
-                                                      stream, Vd, ldw);
+                                                      stream, Vd, ldw, check_only);
   return plmc::kinv_grad_impl<float, plmc::SplitB3>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr,
-                                                    stream, Vd, ldw);
+                                                    stream, Vd, ldw, check_only);
 }
 static int kinv_grad_f64(const plmc::CovTable &table, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                          const double *X, int n, double *grad, double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                         void *stream) {
-  return plmc::kinv_grad_impl<double, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream);
+                         void *stream, bool check_only = false) {
+  return plmc::kinv_grad_impl<double, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream,
+                                            nullptr, 0, check_only);
 }
 // the entry points: the only place the covariance tables of this file are built from flat arguments
 using plmc::CovTable;
@@ -902,6 +1010,34 @@ int plmc_kinv_grad_lper_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int6
   return kinv_grad_f64(CovTable::lper(d, ell, period, rbf_ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
                        partials, q, stream);
 }
+// heterogeneous sum: plmc_kinv_grad_add_vd_* with the members (host array `fam`) and their table (include/plmc.h); `partials` is sized by
+// plmc_sum_grad_partials_bytes.  One member: that family's own path (sum_single_member)
+int64_t plmc_sum_grad_partials_bytes(int64_t n_pad, int q, int ncomp, int elem_bytes) {
+  (void)elem_bytes;                                   // one row of fp64 partial sums per tile and component, whatever the element type
+  return plmc_grad_partials_bytes(n_pad, q * ncomp) + plmc::SUM_TAIL_BYTES * q;
+}
+int plmc_kinv_grad_sum_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              int ncomp, const int *fam, const float *table, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
+  const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);
+  if (t.single_member())
+    return plmc::sum_single_member<float>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {
+      return kinv_grad_f32_any(mt, W, n_pad, ldw, strideW, alpha, X, n, fg, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd, check_only);
+    });
+  return kinv_grad_f32_any(t, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd);
+}
+int plmc_kinv_grad_sum_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              int ncomp, const int *fam, const double *table, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);
+  if (t.single_member())
+    return plmc::sum_single_member<double>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {
+      return kinv_grad_f64(mt, W, n_pad, ldw, strideW, alpha, X, n, fg, Kinv, ldk, strideK, kinv_diag, partials, q, stream, check_only);
+    });
+  return kinv_grad_f64(t, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
+}
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
@@ -940,6 +1076,16 @@ int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
                                void *stream) {                                                                                                  \
     return plmc::loo_grad_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, \
                                   q, stream);                                                                                                   \
+  }                                                                                                                                             \
+  int plmc_loo_grad_sum_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
+                              int d, int ncomp, const int *fam, const T *table, const T *oscale, double *grad, void *partials, int q,          \
+                              void *stream) {                                                                                                   \
+    const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);                                                                             \
+    if (t.single_member())                                                                                                                      \
+      return plmc::sum_single_member<T>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {              \
+        return plmc::loo_grad_impl<T>(mt, Xop, n_pad, krows, ldx, strideX, beta, X, n, fg, partials, q, stream, check_only);                    \
+      });                                                                                                                                       \
+    return plmc::loo_grad_impl<T>(t, Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);                                   \
   }                                                                                                                                             \
   int plmc_loo_grad_rq_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,        \
                              int d, const T *ell, const T *alpha, const T *oscale, double *grad, void *partials, int q, void *stream) {         \

@@ -6,6 +6,7 @@ What it replaces in the reference: the gpytorch evaluation chain behind
 `latent_output.log_prob(proj_target)` (projected_lmc.py:1200-1201), ExactMarginalLogLikelihood
 (experiments.py:233) and `loss.backward()` (experiments.py:270); see SURVEY.md 8a rows a1-a4.
 """
+import ctypes
 import math
 import os
 
@@ -59,6 +60,7 @@ class Workspace:
             # (a spectral-mixture table: the library's own size call for it, include/plmc.h "Spectral-mixture kernel")
             # (a periodic table likewise: "Periodic kernel"; `per` is that kind or the locally periodic one, which has its own size call)
             nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(self.n_pad, q, ncomp, esz) if sm
+                         else L.cdll.plmc_sum_grad_partials_bytes(self.n_pad, q, ncomp, esz) if per == SUM
                          else L.cdll.plmc_lper_grad_partials_bytes(self.n_pad, q, esz) if per == LPER
                          else L.cdll.plmc_per_grad_partials_bytes(self.n_pad, q, esz) if per
                          else L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
@@ -86,7 +88,7 @@ def _drop_all():
 def get_workspace(n, q, naug, dtype, device, need_grad, ncomp=1, sm=False, per=False):
     ncomp = ncomp if need_grad else 1                   # (only the partial sums of the gradient kernel depend on it)
     sm = bool(sm) and bool(need_grad)
-    per = per if (per and need_grad) else False       # False, PER or LPER (_per_kind)
+    per = per if (per and need_grad) else False       # False, PER, LPER or SUM (_per_kind)
     key = (n, q, naug, dtype, device.index, bool(need_grad), ncomp, sm, per)
     ws = _ws_cache.get(key)
     if ws is None:
@@ -147,9 +149,18 @@ def _contig(t, dtype=None):
 # kind and (ell, period, rbf_ell) in the place of ell (include/plmc.h, "Locally periodic kernel").  Like the periodic table it has the
 # rank of an additive one and travels with its kind.  The gradient table [d lengthscales | d periods | d RBF lengthscales | d noise |
 # d oscale] splits like the others.
+# Kind "sum(<member>,<member>,...)" (additive.AdditiveKernel with mixed members): the member kinds travel in the kind string, `ell` is
+# the table (q, G, 3 d + 1) of records [lengthscales | periods | RBF lengthscales: d each | alpha] of which a member reads its own slots
+# only, `oscale` (q, G); it goes to the `_sum` entry points, which take no kind and (G, fam, table) in the place of ell, `fam` a host array
+# of the members' codes (include/plmc.h, "Sums of kernel families").  The table has the rank of an additive one; its gradient table
+# [d table | d noise | d oscale] splits like the others.
 PER = "periodic"
 LPER = "locally_periodic"
 RQ = "rq"
+SUM = "sum"
+_SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
+        "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
+        "plmc_loo_grad": "plmc_loo_grad_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
          "plmc_loo_grad": "plmc_loo_grad_lper"}
@@ -167,13 +178,27 @@ _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assem
         "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add"}
 
 
+def sum_kind(members):
+    """The kind string of a heterogeneous sum of these member kinds."""
+    return "%s(%s)" % (SUM, ",".join(members))
+
+
+def is_sum(kind):
+    return isinstance(kind, str) and kind.startswith(SUM + "(")
+
+
+def sum_members(kind):
+    return kind[len(SUM) + 1:-1].split(",")
+
+
 def is_sm(ell):
     return ell.dim() == 4
 
 
 def _per_kind(kind):
-    """The kind if its table is a stack of (q, d) rows with one row of partial sums per tile (periodic, locally periodic), else False."""
-    return kind if kind in (PER, LPER) else False
+    """The kind if its table is a stack of (q, d) rows with one row of partial sums per tile (periodic, locally periodic), SUM for a
+    heterogeneous sum (whatever its members: the key of its workspace), else False."""
+    return SUM if is_sum(kind) else (kind if kind in (PER, LPER) else False)
 
 
 def n_components(ell, kind=None):
@@ -185,7 +210,7 @@ def n_components(ell, kind=None):
 def kind_code(kind):
     """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic, the locally
     periodic and the rational-quadratic kernel likewise: their name stands in the code's place and sends _kernel_call to them."""
-    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) else _hip.KIND[kind])
+    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) or is_sum(kind) else _hip.KIND[kind])
 
 
 def grad_table_width(ell, kind=None):
@@ -198,6 +223,17 @@ def grad_table_width(ell, kind=None):
 
 
 def _check_kernel_shape(L, ell, kind=None):
+    if is_sum(kind):
+        members, d = sum_members(kind), (ell.shape[-1] - 1) // 3
+        if ell.dim() != 3 or ell.shape[-1] != 3 * d + 1 or d < 1 or ell.shape[1] != len(members):
+            raise ValueError("the table of a sum of G kernels is (q, G, 3 d + 1) = [lengthscales | periods | RBF lengthscales | alpha] per member")
+        unknown = [m_ for m_ in members if m_ not in _hip.FAM]
+        if unknown:
+            raise ValueError("a sum takes the stationary kinds, periodic, rq and locally_periodic members, not %s" % ", ".join(unknown))
+        if d > L.cdll.plmc_sum_max_dim() or len(members) > L.cdll.plmc_sum_max_components():
+            raise ValueError("sum of %d kernels on %d dimensions exceeds plmc_sum_max_components()=%d / plmc_sum_max_dim()=%d"
+                             % (len(members), d, L.cdll.plmc_sum_max_components(), L.cdll.plmc_sum_max_dim()))
+        return
     d = ell.shape[-1] - (1 if kind == RQ else 0)
     if kind == RQ:
         if ell.dim() != 2 or d < 1:
@@ -230,7 +266,15 @@ def _kernel_call(L, base, dt, head, ell, tail, stream=None):
     form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER, or its
     locally periodic form (*head[1:], lengthscales, periods, RBF lengthscales, *tail) when head[0] is LPER, or its rational-quadratic form
     (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ.
+    A heterogeneous sum (head[0] a "sum(...)" kind) goes to its form (*head[1:], G, fam, table, *tail); it copies nothing.
     `stream`: the side stream the call is queued on, if not the current one."""
+    if is_sum(head[0]):
+        fam = getattr(ell, "_sum_fam", None)                 # the host array of member codes, read by the library during the call
+        if fam is None or fam[0] != head[0]:
+            codes = [_hip.FAM[m_] for m_ in sum_members(head[0])]
+            fam = ell._sum_fam = (head[0], (ctypes.c_int * len(codes))(*codes))
+        L.call(_SUM[base], dt, *head[1:], ell.shape[1], ctypes.addressof(fam[1]), _hip.ptr(ell), *tail)
+        return
     if isinstance(head[0], str) and head[0] == RQ:
         rows = getattr(ell, "_rq_rows", None)                # split once per table, as the periodic kernel's rows below
         if rows is None:
@@ -659,6 +703,8 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     yc = _contig(y).reshape(q, 1, n)
     st = _hip.stream_ptr(dev)
     mode = settings.prediction_cache.value() if cache is not None else "off"
+    if key is not None and is_sum(kind):
+        key = key + (kind,)                                # the members are part of the state a cached factorisation belongs to
     hit = False
     if cache is not None and mode != "off":
         ws = cache.ws

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("PLMC_LIB") or os.path.join(_HERE, "libplmc_hip.so")
 
 ABI_VERSION = 4          # include/plmc.h: plmc_version()
 KIND = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "spline": 4}
+# member codes of a heterogeneous sum (include/plmc.h, PLMC_FAM_*): the stationary kind codes and three more
+FAM = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "periodic": 16, "rq": 17, "locally_periodic": 18}
 
 _c = ctypes
 _P = _c.c_void_p
@@ -27,6 +29,7 @@ _TYPED = {
     "plmc_assemble_add": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_per": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_lper": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    "plmc_assemble_sum": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_rq": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_sm": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_write_rhs": [_P, _I, _I, _P, _L, _L, _I, _I, _I, _P],
@@ -34,6 +37,7 @@ _TYPED = {
     "plmc_assemble_cross_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "plmc_assemble_cross_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_potrf": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P],
@@ -42,6 +46,7 @@ _TYPED = {
     "plmc_factorize_add_ex": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_per_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_lper_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
+    "plmc_factorize_sum_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_rq_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_sm_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
@@ -58,12 +63,14 @@ _TYPED = {
     "plmc_kinv_grad_add_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_per_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_lper_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
+    "plmc_kinv_grad_sum_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_rq_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_per": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_lper": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_sum": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_rq": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
@@ -94,6 +101,9 @@ _PLAIN = {
     "plmc_per_grad_partials_bytes": ([_L, _I, _I], _L),
     "plmc_lper_max_dim": ([], _I),
     "plmc_lper_grad_partials_bytes": ([_L, _I, _I], _L),
+    "plmc_sum_max_components": ([], _I),
+    "plmc_sum_max_dim": ([], _I),
+    "plmc_sum_grad_partials_bytes": ([_L, _I, _I, _I], _L),
     "plmc_rq_max_dim": ([], _I),
     "plmc_qr_max": ([], _I),
     "plmc_last_error": ([], _c.c_char_p),

@@ -63,6 +63,11 @@ class Kernel(torch.nn.Module):
     def __mul__(self, other):
         return ProductKernel(self, other)
 
+    def __add__(self, other):
+        """k1 + k2: additive.AdditiveKernel [gpytorch-knowledge: AdditiveKernel, `kernels` ModuleList, unverified offline], flattened."""
+        from .additive import AdditiveKernel
+        return AdditiveKernel(self, *(other.kernels if isinstance(other, AdditiveKernel) else [other]))
+
 
 class RBFKernel(Kernel):
     has_lengthscale = True
@@ -292,6 +297,19 @@ def refuse_rq(kernel, model):
     _refuse(RQKernel, "RQKernel", kernel, model)
 
 
+def refuse_sum(kernel, model):
+    """A sum of different kernel families (additive.AdditiveKernel with mixed members, kind "sum(...)") runs on the batched exact engine
+    only: name the model that cannot take it, and the members.  A sum of one stationary kind goes wherever it went.  `kernel` is an
+    instance, bare or inside a ScaleKernel: `kernel_type` may be a factory function, which only shows its sum once called."""
+    from .additive import AdditiveKernel
+    k = kernel
+    while k is not None and not isinstance(k, AdditiveKernel):
+        k = getattr(k, "base_kernel", None)
+    if k is not None and k.is_heterogeneous():
+        raise NotImplementedError("%s does not take the sum %s: a sum of different kernel families is served by the batched exact engine "
+                                  "only (ExactGPModel without inducing points, ProjectedGPModel)" % (model, k.describe()))
+
+
 def refuse_sm(kernel, model):
     """The spectral-mixture kernel runs on the batched exact engine only: name the model that cannot take it."""
     _refuse(SpectralMixtureKernel, "SpectralMixtureKernel", kernel, model)
@@ -315,7 +333,7 @@ class ScaleKernel(Kernel):
                  **kwargs):
         super().__init__(batch_shape=batch_shape, active_dims=base_kernel.active_dims)
         self.base_kernel = base_kernel
-        self.register_parameter("raw_outputscale", torch.nn.Parameter(torch.zeros(*self.batch_shape)))
+        self.register_parameter("raw_outputscale", torch.nn.Parameter(torch.zeros(self.batch_shape)))
         self.raw_outputscale_constraint = outputscale_constraint or Positive()
 
     @property
@@ -332,6 +350,8 @@ class ScaleKernel(Kernel):
         kind, ell, inner = self.base_kernel._pieces(d, like if like is not None else self.raw_outputscale)
         if kind == "sm":                                       # the output scale folds into the mixture weights (q, M)
             return kind, ell, self.outputscale.reshape(-1, 1) * inner
+        if kind.startswith("sum("):                            # ... and into the component output scales (q, G) of a heterogeneous sum
+            return kind, ell, self.outputscale.reshape(-1, 1) * inner
         return kind, ell, self.outputscale.reshape(-1)
 
 
@@ -343,7 +363,9 @@ class LazyKernel:
     kind "sm": ell (q, 2, M, d) holds the scales and the means of a spectral mixture, oscale (q, M) its weights (`scales`, `means`,
     `weights`).  kind "periodic": ell (q, 2, d) holds the lengthscales and the periods, oscale (q) | None.  kind "rq": ell (q, d + 1) holds
     the lengthscales and, in its last column, alpha; oscale (q) | None.  kind "locally_periodic": ell (q, 3, d) holds the periodic
-    lengthscales, the periods and the RBF lengthscales, oscale (q) | None."""
+    lengthscales, the periods and the RBF lengthscales, oscale (q) | None.  kind "sum(<member>,...)": a sum of different families
+    (additive.py); the member kinds travel in the kind string (so through add_noise and into the prediction cache's key), ell
+    (q, G, 3 d + 1) holds one record [lengthscales | periods | RBF lengthscales | alpha] per member, oscale (q, G)."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise

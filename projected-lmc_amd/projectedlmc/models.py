@@ -65,6 +65,7 @@ def handle_covar_(kernel, dim, decomp=None, n_funcs=1, prior_scales=None, prior_
             kg = kernel(ard_num_dims=len(idx_g), active_dims=idx_g, lengthscale_prior=l_priors[i_ker],
                         batch_shape=torch.Size([n_funcs]), **ker_kwargs)
             _k.refuse_product(kg, "handle_covar_(decomp=...) with several groups (the additive kernel)")   # (a factory shows it only now)
+            _k.refuse_sum(kg, "handle_covar_(decomp=...) with several groups (the additive kernel)")
             init_from_prior(kg, l_priors[i_ker])
             subs.append(_k.ScaleKernel(kg, batch_shape=torch.Size([n_funcs])))
         return AdditiveKernel(*subs)
@@ -279,6 +280,7 @@ class ExactGPModel(ExactGP):
             _k.refuse_periodic(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_rq(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_product(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
+            _k.refuse_sum(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             from .sgpr import InducingPointKernel
             self.covar_module = InducingPointKernel(self.covar_module, torch.randn(n_inducing_points, self.dim),
                                                     likelihood)

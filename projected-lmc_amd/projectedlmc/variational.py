@@ -234,6 +234,7 @@ class VariationalMultitaskGPModel(torch.nn.Module):
                                           prior_width=prior_width, n_funcs=n_latents, ker_kwargs=ker_kwargs,
                                           outputscales=outputscales)
         _k.refuse_product(self.covar_module, "VariationalMultitaskGPModel")      # (kernel_type may be a factory: look at what it built)
+        _k.refuse_sum(self.covar_module, "VariationalMultitaskGPModel")
         self.mean_module = _m.ZeroMean(batch_shape=torch.Size([n_latents]))
         self.n_tasks, self.n_latents, self.decomp = n_tasks, n_latents, decomp
         if init_lmc_coeffs and train_y is not None:
