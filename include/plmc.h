@@ -623,6 +623,70 @@ int plmc_loo_grad_lper_f64(const double *Xop, int64_t n_pad, int64_t krows, int6
                            void *partials, int q, void *stream);
 
 /*
+ * Dot-product kernels [gpytorch-knowledge: LinearKernel, PolynomialKernel, unverified offline] on the batched exact engine:
+ *     Khat_i = os[i] (c[i] + sum_k v[i][k] x_k x'_k)^P + noise[i] I,   v > 0, c >= 0, P an integer,
+ *     1 <= d <= plmc_dot_max_dim(), 1 <= P <= plmc_dot_max_power()   (LinearKernel: P = 1, c = 0; PolynomialKernel: v = 1).
+ *     Exceeding a limit, d <= 0, P <= 0 or a null `offset` is an argument error (plmc_last_error()); nothing is launched.
+ * Table, per latent i:  variances v (q x d, contiguous), offset c (q), output scale os (q) or NULL (all ones); ONE power for the batch,
+ * a host int.  noise: q.
+ * Every entry point takes the arguments of its rational-quadratic form with (ell, alpha) replaced by (var, offset, power) and does what
+ * that form does:
+ *   plmc_assemble_dot_*        plmc_assemble_rq_*        (upper tiles of Khat, identity padding)
+ *   plmc_assemble_cross_dot_*  plmc_assemble_cross_rq_*  (prediction columns; the dense K** of a full posterior covariance)
+ *   plmc_factorize_dot_ex_*    plmc_factorize_rq_ex_*    (assembly overlapped with the sweep; bit-identical to plmc_assemble_dot_*
+ *                                                         followed by plmc_potrf_ex_*)
+ *   plmc_kinv_grad_dot_vd_*    plmc_kinv_grad_rq_vd_*    (K^-1 = W^T W with the gradient reduced in the epilogue)
+ *   plmc_loo_grad_dot_*        plmc_loo_grad_rq_*        (the gradient table of the leave-one-out objective, below)
+ * NOT stationary: k(x, x) = os (c + sum_k v_k x_k^2)^P depends on x.  The diagonal of Khat is that value plus the noise, an all-zero input
+ * row gives os c^P + noise (P = 1, c = 0: a row of exact zeros and the noise), and the prior variance at a test point is NOT os.
+ * The matrix is positive semi-definite of rank <= C(d + P, P), so Khat >= noise I as for every other family; without noise it is
+ * singular as soon as n exceeds that rank.
+ * The value is an FMA chain s = c + sum_k (v_k x_k) x'_k over the raw inputs and P - 1 multiplications; no pow, exp or log, so a negative s
+ * keeps its sign under an odd P.  The fp32 assembly is within P (d + 3) 2^-24 os S^P, S = c + sum_k |v_k x_k x'_k|, of the fp64 formula at
+ * the fp32 inputs per element.
+ * Gradient table of plmc_kinv_grad_dot_vd_* and plmc_loo_grad_dot_* (double), d + 3 entries per latent:
+ *     grad[latent] = [ d logp / d v: d | d / d c | d / d noise | d / d os ]
+ *   with d k / d v_k = os P s^(P - 1) x_k x'_k, d k / d c = os P s^(P - 1), d k / d os = s^P.  The diagonal element contributes to EVERY
+ *   entry (weight 1; the pairs off the diagonal 2).
+ *   plmc_kinv_grad_dot_vd_f32 follows the rule of plmc_kinv_grad_rq_vd_f32: d = 1 follows PLMC_SPLIT; d > 1 runs on the two fp16 planes
+ *   where the knob selects them (the default with eig_lo given) and on the fp32 matrix instructions where the three bf16 planes would
+ *   run (PLMC_SPLIT=3, or no eig_lo).
+ * Scratch.  `Vd`: as for plmc_kinv_grad_vd_*.  `partials`: plmc_grad_partials_bytes(n_pad, q) bytes, one row of partial sums per tile.
+ *   The fp32 split engine takes the planes of W from the Vd of the sweep that produced W and refuses a call without them; fp64 and
+ *   PLMC_SPLIT=0 need no planes.
+ */
+int plmc_dot_max_dim(void);                   /* largest input dimension of a dot-product kernel (16) */
+int plmc_dot_max_power(void);                 /* largest power of a dot-product kernel (8) */
+int plmc_assemble_dot_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale,
+                          const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_dot_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
+                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_cross_dot_f32(const float *X, int n, const float *Xs, int ns, int d, const float *var, const float *offset, int power,
+                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_assemble_cross_dot_f64(const double *X, int n, const double *Xs, int ns, int d, const double *var, const double *offset, int power,
+                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
+                                void *stream);
+int plmc_factorize_dot_ex_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale,
+                              const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_dot_ex_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
+                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_kinv_grad_dot_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              const float *var, const float *offset, int power, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream);
+int plmc_kinv_grad_dot_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              const double *var, const double *offset, int power, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream);
+int plmc_loo_grad_dot_f32(const float *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const float *beta, const float *X,
+                          int n, int d, const float *var, const float *offset, int power, const float *oscale, double *grad, void *partials,
+                          int q, void *stream);
+int plmc_loo_grad_dot_f64(const double *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const double *beta, const double *X,
+                          int n, int d, const double *var, const double *offset, int power, const double *oscale, double *grad, void *partials,
+                          int q, void *stream);
+
+/*
  * Sums of kernel families (what `k1 + k2` builds: trend + a seasonality that drifts + medium-term irregularity, two periodicities, ...)
  * on the batched exact engine, the heterogeneous sum
  *     Khat_i = sum_{g < ncomp} os[i][g] k_{fam[g]}(x, x'; table[i][g]) + noise[i] I,

@@ -17,6 +17,8 @@ constexpr int SM_MAX_DIM = 8;        // largest input dimension of a spectral-mi
 constexpr int PER_MAX_DIM = 8;       // largest input dimension of a periodic kernel (plmc_per_max_dim())
 constexpr int RQ_MAX_DIM = 16;       // largest input dimension of a rational-quadratic kernel (plmc_rq_max_dim())
 constexpr int LPER_MAX_DIM = 8;      // largest input dimension of a locally periodic kernel (plmc_lper_max_dim())
+constexpr int DOT_MAX_DIM = 16;      // largest input dimension of a dot-product kernel (plmc_dot_max_dim())
+constexpr int DOT_MAX_POWER = 8;     // largest power of a dot-product kernel (plmc_dot_max_power())
 constexpr int SUM_MAX_DIM = 8;       // largest input dimension of a heterogeneous sum (plmc_sum_max_dim()): the smallest of its members' limits
 // member families of a heterogeneous sum beside the stationary kinds K_RBF .. K_MATERN52: the public codes of include/plmc.h
 // (PLMC_FAM_*) and the 4-bit codes the kernels get, packed one nibble per component
@@ -85,8 +87,10 @@ const Knobs &knobs();
 //   SUM    heterogeneous sum of ncomp <= MAX_COMP members: ell = its table (q, ncomp, 3 d + 1), one record [ell | period | rbf_ell: d each |
 //          alpha] per component, oscale (q, ncomp) | null; `fams` = the members' 4-bit codes (K_RBF .. K_MATERN52, F_PER, F_RQ, F_LPER), component g
 //          in bits 4 g .. 4 g + 3, read from the caller's host array when the table is built (CovTable::sum)
-// `kind` is not looked at for SM, PER, RQ, LPER and SUM; the pointers are of the call's element type.  `third` is null for every other family.
-enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER, COV_SUM };
+//   DOT    dot product (linear / polynomial): ell = its variances v (q, d), second = its offset c (q), oscale (q) | null; ncomp = its
+//          power P (power()), 1 <= P <= DOT_MAX_POWER -- one component, so the slot is free
+// `kind` is not looked at for SM, PER, RQ, LPER, SUM and DOT; the pointers are of the call's element type.  `third` is null for every other family.
+enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER, COV_SUM, COV_DOT };
 struct CovTable {
   CovFamily family;
   int kind, d, ncomp;
@@ -103,6 +107,8 @@ struct CovTable {
   static CovTable lper(int d, const void *ell, const void *period, const void *rbf_ell, const void *oscale) {
     return {COV_LPER, 0, d, 1, ell, period, oscale, rbf_ell};
   }
+  static CovTable dot(int d, int power, const void *v, const void *c, const void *oscale) { return {COV_DOT, 0, d, power, v, c, oscale}; }
+  int power() const { return ncomp; }                             // DOT only
   // `fam`: HOST array of ncomp public codes (kind codes 0 .. 3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER)
   static CovTable sum(int d, int ncomp, const int *fam, const void *table, const void *oscale) {
     CovTable t{COV_SUM, 0, d, ncomp, table, nullptr, oscale};
@@ -156,8 +162,11 @@ struct CovTable {
     } else if (family == COV_LPER) {
       if (d <= 0 || d > LPER_MAX_DIM) return "need 0 < d <= plmc_lper_max_dim()";
       if (!third) return "null pointer";
+    } else if (family == COV_DOT) {
+      if (d <= 0 || d > DOT_MAX_DIM) return "need 0 < d <= plmc_dot_max_dim()";
+      if (ncomp < 1 || ncomp > DOT_MAX_POWER) return "need 1 <= power <= plmc_dot_max_power()";
     }
-    return (family == COV_SM || family == COV_PER || family == COV_RQ || family == COV_LPER) && !second ? "null pointer" : nullptr;
+    return (family == COV_SM || family == COV_PER || family == COV_RQ || family == COV_LPER || family == COV_DOT) && !second ? "null pointer" : nullptr;
   }
   // the family whose kernels run: an additive table of one component IS the plain kernel (ell (q, 1, d) is ell (q, d)) and takes the
   // plain instantiations, bit for bit

@@ -454,6 +454,45 @@ template <typename T, int DCAP> struct RqTable {
   }
 };
 
+// The dot-product table (covariance.hpp): per latent variances v (d), offset c, output scale | null; the power P is the same for every
+// latent.  In LDS: v [DCAP] (0 beyond d: that dimension adds exactly 0 to s), c, os.  The diagonal is a value like any other
+// (k(x, x) = os (c + sum_k v_k x_k^2)^P); the tile walk adds the noise to it and writes the identity padding.
+template <typename T, int DCAP> struct DotPairValue {
+  const T *v;
+  T c, os;
+  int P;
+  __device__ __forceinline__ Pair<T> operator()(const T (&xr)[DCAP], const Pair<T> (&xc)[DCAP]) const {
+    T ta[DCAP], b0[DCAP], b1[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) { ta[k] = v[k] * xr[k]; b0[k] = xc[k].x; b1[k] = xc[k].y; }
+    return Pair<T>{os * dot_value<T, DCAP>(ta, b0, c, P), os * dot_value<T, DCAP>(ta, b1, c, P)};
+  }
+};
+template <typename T, int DCAP> struct DotTable {
+  static constexpr int LDS = DCAP + 2;
+  int P;
+  const T *var, *offset, *oscale;
+  __device__ __forceinline__ void stage(int lat, int d, T *par) const {
+    const int tid = threadIdx.x;
+    if (tid < DCAP) par[tid] = tid < d ? var[(int64_t)lat * d + tid] : T(0);
+    if (tid == 0) {
+      par[DCAP] = offset[lat];
+      par[DCAP + 1] = oscale ? oscale[lat] : T(1);
+    }
+  }
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+                                       bool edge) const {
+    assemble_tile_table<T, DCAP>(xi, xj, ldu, DotPairValue<T, DCAP>{par, par[DCAP], par[DCAP + 1], P}, nz, Al, lda, ib, jb, n, edge);
+  }
+  // the training row is the scaled side, as the tile's row is
+  __device__ __forceinline__ T value(const T *xa, const T (&xs)[DCAP], const T *par) const {
+    T ta[DCAP];
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) ta[k] = par[k] * xa[k];
+    return par[DCAP + 1] * dot_value<T, DCAP>(ta, xs, par[DCAP], P);
+  }
+};
+
 // The locally periodic table (covariance.hpp): per latent periodic lengthscales, periods, RBF lengthscales (d each), output scale | null.
 // In LDS: ip = 1 / p, its residual ipr, w = 1 / ell, v = 1 / lam [DCAP] each (0 beyond d: that dimension adds exactly 0 to both
 // exponents), os.
@@ -593,7 +632,7 @@ template <typename T, int DCAP> struct SumTable {
 };
 
 // d <= 8 (DCAP in {4, 8}; spectral mixture, periodic, locally periodic and rational quadratic also 1; rational quadratic also 16);
-// P: AddTable / SmTable / PerTable / RqTable / LperTable / SumTable
+// dot product: 1, 4, 8, 16;  P: AddTable / SmTable / PerTable / RqTable / LperTable / SumTable / DotTable
 template <typename T, int DCAP, class P>
 __global__ __launch_bounds__(NTHREADS) void k_assemble_small_table(const P prm, const T *__restrict__ X, int n, int d,
                                                                     const T *__restrict__ noise, T *__restrict__ A,
@@ -729,6 +768,7 @@ template <typename T, int DC> RqTable<T, DC> rq_table(const CovTable &t) { retur
 template <typename T, int DC> LperTable<T, DC> lper_table(const CovTable &t) {
   return {(const T *)t.ell, (const T *)t.second, (const T *)t.third, (const T *)t.oscale};
 }
+template <typename T, int DC> DotTable<T, DC> dot_table(const CovTable &t) { return {t.power(), (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
 template <typename T, int DC> SumTable<T, DC> sum_table(const CovTable &t) { return {t.fams, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
 
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
@@ -747,7 +787,8 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
   }
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
-  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER || t.family == COV_SUM;   // d <= 8 (rational quadratic: 16) by the family's limit
+  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER || t.family == COV_SUM ||
+                          t.family == COV_DOT;   // d <= 8 (rational quadratic, dot product: 16) by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
   PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
@@ -806,6 +847,12 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
       if (d == 1) table(sum_table<T, 1>(t));
       else if (d <= 4) table(sum_table<T, 4>(t));
       else table(sum_table<T, 8>(t));
+      break;
+    case COV_DOT:
+      if (d == 1) table(dot_table<T, 1>(t));
+      else if (d <= 4) table(dot_table<T, 4>(t));
+      else if (d <= 8) table(dot_table<T, 8>(t));
+      else table(dot_table<T, 16>(t));
       break;
   }
   return launch_status(__func__);
@@ -891,6 +938,12 @@ int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int n
       if (d == 1) table(sum_table<T, 1>(t));
       else if (d <= 4) table(sum_table<T, 4>(t));
       else table(sum_table<T, 8>(t));
+      break;
+    case COV_DOT:
+      if (d == 1) table(dot_table<T, 1>(t));
+      else if (d <= 4) table(dot_table<T, 4>(t));
+      else if (d <= 8) table(dot_table<T, 8>(t));
+      else table(dot_table<T, 16>(t));
       break;
   }
   return launch_status(__func__);
@@ -988,6 +1041,21 @@ int plmc_rq_max_dim(void) { return plmc::RQ_MAX_DIM; }
 PLMC_RQ_ENTRY(f32, float)
 PLMC_RQ_ENTRY(f64, double)
 #undef PLMC_RQ_ENTRY
+int plmc_dot_max_dim(void) { return plmc::DOT_MAX_DIM; }
+int plmc_dot_max_power(void) { return plmc::DOT_MAX_POWER; }
+#define PLMC_DOT_ENTRY(SUF, T)                                                                                                                 \
+  int plmc_assemble_dot_##SUF(const T *X, int n, int d, const T *var, const T *offset, int power, const T *oscale, const T *noise, T *A,       \
+                              int64_t lda, int64_t strideA, int q, void *stream) {                                                             \
+    return plmc::assemble_impl<T>(CovTable::dot(d, power, var, offset, oscale), X, n, noise, A, lda, strideA, q, stream);                      \
+  }                                                                                                                                            \
+  int plmc_assemble_cross_dot_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *var, const T *offset, int power, const T *oscale,  \
+                                    T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                 \
+    return plmc::assemble_cross_impl<T>(CovTable::dot(d, power, var, offset, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q,        \
+                                        stream);                                                                                               \
+  }
+PLMC_DOT_ENTRY(f32, float)
+PLMC_DOT_ENTRY(f64, double)
+#undef PLMC_DOT_ENTRY
 int plmc_lper_max_dim(void) { return plmc::LPER_MAX_DIM; }
 #define PLMC_LPER_ENTRY(SUF, T)                                                                                                                \
   int plmc_assemble_lper_##SUF(const T *X, int n, int d, const T *ell, const T *period, const T *rbf_ell, const T *oscale, const T *noise,     \

@@ -276,6 +276,44 @@ __device__ __forceinline__ T lper_value(const T (&a)[DCAP], const T (&b)[DCAP], 
   }
   return lper_exp(e, r2);
 }
+
+// ---- dot product [gpytorch-knowledge: LinearKernel, PolynomialKernel, unverified offline]:
+//     k(x, x') = (c + sum_k v_k x_k x'_k)^P,   v_k > 0, c >= 0, P an integer >= 1
+// (LinearKernel: P = 1, c = 0; PolynomialKernel: v = 1).  NOT stationary: k(x, x) = (c + sum_k v_k x_k^2)^P is a value like any other, so
+// the diagonal goes through these functions too.  s is one FMA chain over the raw inputs that starts from c, with the row's coordinates
+// scaled once (t_k = v_k a_k, one rounding); s^P is P - 1 multiplications -- no pow, exp or log, so a negative s keeps its sign under an
+// odd P and s = 0 gives exactly 0 (P = 1: exactly s).  fp32: |error| <= P (d + 2) 2^-24 S^P to first order, S = c + sum_k |v_k a_k b_k|
+// ("Dot-product kernels: fp32 numerics").
+__device__ __forceinline__ float  dot_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double dot_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// s^P and, in `pm1`, s^(P - 1) from the same chain: 1 * s * s ... (the first product is exact)
+template <typename T> __device__ __forceinline__ T dot_pow(T s, int P, T &pm1) {
+  T p = T(1);
+#pragma unroll 1
+  for (int i = 1; i < P; ++i) p *= s;
+  pm1 = p;
+  return p * s;
+}
+// one covariance value (unit output scale): ta = v a [DCAP] (0 beyond d: that dimension adds exactly 0 to s), b raw
+template <typename T, int DCAP>
+__device__ __forceinline__ T dot_value(const T (&ta)[DCAP], const T (&b)[DCAP], T c, int P) {
+  T s = c;
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) s = dot_fma(ta[k], b[k], s);
+  T pm1;
+  return dot_pow(s, P, pm1);
+}
+// gradient epilogue: value s^P and P s^(P - 1) (d k / d c; d k / d v_k = P s^(P - 1) a_k b_k), unit output scale.  pr = a b [DCAP]
+// (the products the d / d v sums need anyway), v [DCAP] (0 beyond d)
+template <typename T, int DCAP>
+__device__ __forceinline__ void dot_value_deriv(const T (&pr)[DCAP], const T (&v)[DCAP], T c, int P, T &val, T &dval) {
+  T s = c;
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) s = dot_fma(v[k], pr[k], s);
+  T pm1;
+  val = dot_pow(s, P, pm1);
+  dval = T(P) * pm1;
+}
 #undef dexp
 #undef dsqrt
 

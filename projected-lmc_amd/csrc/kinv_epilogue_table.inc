@@ -8,6 +8,8 @@
 #include "kinv_epilogue_sum.inc"
   } else if constexpr (F == COV_RQ) {
 #include "kinv_epilogue_rq.inc"
+  } else if constexpr (F == COV_DOT) {
+#include "kinv_epilogue_dot.inc"
   } else if constexpr (F == COV_SM) {
 #include "kinv_epilogue_sm.inc"
   } else {

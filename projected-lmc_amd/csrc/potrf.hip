@@ -1525,6 +1525,24 @@ int plmc_factorize_rq_ex_f64(const double *X, int n, int d, const double *ell, c
   PLMC_REQUIRE_TABLE(job.table);
   return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
 }
+// The same for a dot-product kernel (plmc_assemble_dot_*): the job carries the variances, the offset and the power
+int plmc_factorize_dot_ex_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale,
+                              const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  const plmc::AssembleJob job{plmc::CovTable::dot(d, power, var, offset, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
+  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
+}
+int plmc_factorize_dot_ex_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
+                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
+                              int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
+  (void)eig_lo;
+  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
+  const plmc::AssembleJob job{plmc::CovTable::dot(d, power, var, offset, oscale), n, X, noise};
+  PLMC_REQUIRE_TABLE(job.table);
+  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
+}
 // The same for a locally periodic kernel (plmc_assemble_lper_*): the job carries the periodic lengthscales, the periods and the RBF
 // lengthscales
 int plmc_factorize_lper_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,

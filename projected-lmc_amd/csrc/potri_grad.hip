@@ -246,6 +246,8 @@ __global__ __launch_bounds__(B3_NT, 2) void k_kinv_grad_bf3(int kind, int64_t n_
 // or null; `kind` and ncomp (1) are not looked at.
 // COV_RQ: a rational-quadratic kernel of up to DC (1, 4, 8, 16) input dimensions (kinv_epilogue_rq.inc): ell = its lengthscales, `means` its alpha (q),
 // oscale (q) or null; `kind` and ncomp (1) are not looked at.
+// COV_DOT: a dot-product kernel of up to DC (1, 4, 8, 16) input dimensions (kinv_epilogue_dot.inc): ell = its variances, `means` its offset (q),
+// oscale (q) or null, ncomp = its power; `kind` is not looked at.
 // COV_LPER: a locally periodic kernel of up to DC (1, 4, 8) input dimensions (kinv_epilogue_lper.inc): ell = its periodic lengthscales,
 // `means` its periods, `third` its RBF lengthscales, oscale (q) or null; `kind` and ncomp (1) are not looked at.  No other family reads
 // `third`.
@@ -262,7 +264,7 @@ __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *sme
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_DOT || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
@@ -401,6 +403,21 @@ __global__ __launch_bounds__(RED_NT) void k_reduce_grad_rq(const double *__restr
   }
 }
 
+// The reduction for the dot-product kernel: one row of GP slots per tile (kinv_epilogue_dot.inc).  grid (q).
+// grad[lat]: [ d/d v (d) | d/d c | d/d noise | d/d oscale ]; the epilogue left no factor out.
+__global__ __launch_bounds__(RED_NT) void k_reduce_grad_dot(const double *__restrict__ partials, int m, int d, double *__restrict__ grad) {
+  PLMC_REDUCE_TILES(GP, 0);
+  if (threadIdx.x < GP) {
+    const double tot = reduce_slot_total(red);
+    const int k = threadIdx.x;
+    double *gl = grad + (int64_t)lat * (d + 3);
+    if (k < d) gl[k] = 0.5 * tot;
+    else if (k == DOT_MAX_DIM) gl[d] = 0.5 * tot;
+    else if (k == MAX_DIM) gl[d + 1] = 0.5 * tot;
+    else if (k == MAX_DIM + 1) gl[d + 2] = 0.5 * tot;
+  }
+}
+
 // The reduction for the locally periodic kernel: one row of GP slots per tile (kinv_epilogue_lper.inc).  grid (q).
 // grad[lat]: [ d/d ell (d) | d/d period (d) | d/d lam (d) | d/d noise | d/d oscale ], with the factors the epilogue left out.  A factor
 // that is switched off (ell = +inf or lam = +inf) gets finite sum / inf = exactly 0.
@@ -525,10 +542,11 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     const bool from_vd = Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat);
     if (!from_vd)
-      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER && family != COV_SUM && !table.of_sum,
+      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER && family != COV_SUM && family != COV_DOT && !table.of_sum,
                    family == COV_SUM || table.of_sum ? "the sum gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_LPER ? "the locally periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
+                   : family == COV_DOT ? "the dot-product gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                    : family == COV_RQ ? "the rational-quadratic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
                                       : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
     if (check_only) return 0;
@@ -564,6 +582,13 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
         else if (d <= 8) PLMC_LAUNCH_TB(COV_RQ, 8);
         else PLMC_LAUNCH_TB(COV_RQ, 16);
         break;
+      case COV_DOT:                                        // (three planes: d = 1 only, as COV_RQ)
+        if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_DOT, 1);
+        else if (d == 1) PLMC_LAUNCH_TB(COV_DOT, 1);
+        else if (d <= 4) PLMC_LAUNCH_TB(COV_DOT, 4);
+        else if (d <= 8) PLMC_LAUNCH_TB(COV_DOT, 8);
+        else PLMC_LAUNCH_TB(COV_DOT, 16);
+        break;
       case COV_SM: PLMC_LAUNCH_TB(COV_SM, 1); break;       // (d = 1 only: kinv_grad_f32_any)
       case COV_ADD: PLMC_LAUNCH_TB(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -589,6 +614,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
       case COV_LPER: if (d == 1) PLMC_LAUNCH_TG(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_LPER, 4); else PLMC_LAUNCH_TG(COV_LPER, 8); break;
       case COV_SUM: if (d == 1) PLMC_LAUNCH_TG(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SUM, 4); else PLMC_LAUNCH_TG(COV_SUM, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_TG(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_RQ, 8); else PLMC_LAUNCH_TG(COV_RQ, 16); break;
+      case COV_DOT: if (d == 1) PLMC_LAUNCH_TG(COV_DOT, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_DOT, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_DOT, 8); else PLMC_LAUNCH_TG(COV_DOT, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -607,6 +633,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
       case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
       case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
+      case COV_DOT: hipLaunchKernelGGL(k_reduce_grad_dot, dim3(q), dim3(RED_NT), 0, st, part, m, d, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
@@ -655,7 +682,7 @@ __global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_loo_grad_add(
+__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_DOT || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_loo_grad_add(
     int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
     const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
     const T *__restrict__ means, const T *__restrict__ third) {
@@ -749,6 +776,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
       case COV_LPER: if (d == 1) PLMC_LAUNCH_LT(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_LPER, 4); else PLMC_LAUNCH_LT(COV_LPER, 8); break;
       case COV_SUM: if (d == 1) PLMC_LAUNCH_LT(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SUM, 4); else PLMC_LAUNCH_LT(COV_SUM, 8); break;
       case COV_RQ: if (d == 1) PLMC_LAUNCH_LT(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_RQ, 8); else PLMC_LAUNCH_LT(COV_RQ, 16); break;
+      case COV_DOT: if (d == 1) PLMC_LAUNCH_LT(COV_DOT, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_DOT, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_DOT, 8); else PLMC_LAUNCH_LT(COV_DOT, 16); break;
       case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
       case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
       case COV_PLAIN:
@@ -767,6 +795,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
       case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
       case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
       case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
+      case COV_DOT: hipLaunchKernelGGL(k_reduce_grad_dot, dim3(q), dim3(RED_NT), 0, st, part, m, d, grad); break;
       case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
       case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
@@ -867,10 +896,11 @@ static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_
   // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel keeps d sines, cosine
   // complements and 2 d sums live and follows the same rule, and so does the locally periodic kernel (3 d sums).  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
   // every d; beside the three bf16 planes (PLMC_SPLIT=3, or no eig_lo) it fits at d = 1 only, so d > 1 takes the fp32 products there.
+  // The dot-product epilogue follows the rational-quadratic rule (DC = 4, 8, 16 spill beside the three planes, none beside the two).
   const bool three_planes = !(split == 2 && eig_lo);
   // A heterogeneous sum may hold a periodic or a locally periodic member and follows their rule whatever its members are.
   if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER || table.family == plmc::COV_LPER || table.family == plmc::COV_SUM) && table.d > 1) ||
-      (table.family == plmc::COV_RQ && table.d > 1 && three_planes))
+      ((table.family == plmc::COV_RQ || table.family == plmc::COV_DOT) && table.d > 1 && three_planes))
     return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream,
                                              nullptr, 0, check_only);
   // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
@@ -1038,6 +1068,22 @@ int plmc_kinv_grad_sum_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64
     });
   return kinv_grad_f64(t, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
 }
+// dot-product kernel: plmc_kinv_grad_vd_* with the table (variances, offset, power, output scale) (include/plmc.h); `partials` is sized
+// by plmc_grad_partials_bytes
+int plmc_kinv_grad_dot_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
+                              const float *var, const float *offset, int power, const float *oscale, double *grad, float *Kinv, int64_t ldk,
+                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
+  return kinv_grad_f32_any(CovTable::dot(d, power, var, offset, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
+                           partials, q, eig_lo, stream, Vd);
+}
+int plmc_kinv_grad_dot_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
+                              const double *var, const double *offset, int power, const double *oscale, double *grad, double *Kinv, int64_t ldk,
+                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
+  (void)eig_lo;
+  (void)Vd;
+  return kinv_grad_f64(CovTable::dot(d, power, var, offset, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
+                       q, stream);
+}
 int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
                        const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
                        double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
@@ -1090,6 +1136,12 @@ int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw,
   int plmc_loo_grad_rq_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,        \
                              int d, const T *ell, const T *alpha, const T *oscale, double *grad, void *partials, int q, void *stream) {         \
     return plmc::loo_grad_impl<T>(CovTable::rq(d, ell, alpha, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);  \
+  }                                                                                                                                             \
+  int plmc_loo_grad_dot_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
+                              int d, const T *var, const T *offset, int power, const T *oscale, double *grad, void *partials, int q,            \
+                              void *stream) {                                                                                                   \
+    return plmc::loo_grad_impl<T>(CovTable::dot(d, power, var, offset, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q,  \
+                                  stream);                                                                                                      \
   }                                                                                                                                             \
   int plmc_loo_operand_##SUF(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *rowscale, T *Xop, int64_t krows, int64_t ldx, \
                              int64_t strideX, int n, int q, void *stream) {                                                                    \

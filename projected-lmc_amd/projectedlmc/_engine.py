@@ -14,6 +14,7 @@ import torch
 
 from . import _hip
 from . import settings
+from .kernels import dot_power
 from ._pivot import PivotCheck, deferred_pivot_checks, walk      # noqa: F401 (deferred_pivot_checks: re-exported for callers)
 
 LOG2PI = math.log(2.0 * math.pi)
@@ -154,6 +155,11 @@ def _contig(t, dtype=None):
 # only, `oscale` (q, G); it goes to the `_sum` entry points, which take no kind and (G, fam, table) in the place of ell, `fam` a host array
 # of the members' codes (include/plmc.h, "Sums of kernel families").  The table has the rank of an additive one; its gradient table
 # [d table | d noise | d oscale] splits like the others.
+# Kind "linear" / "poly<P>" (kernels.LinearKernel, PolynomialKernel): the dot-product family.  `ell` is its table (q, d + 1) =
+# [variances | offset], `oscale` (q) | None; it goes to the `_dot` entry points, which take no kind and (variances, offset, P) in the place
+# of ell, P a host int read off the kind string (kernels.dot_power; include/plmc.h, "Dot-product kernels").  The table has the rank and
+# the width of the rational-quadratic one and is sized and split like it: [d variances | d offset | d noise | d oscale].  The kernel is
+# not stationary: what needs k(x, x) hands the table to kernels.prior_diagonal.
 PER = "periodic"
 LPER = "locally_periodic"
 RQ = "rq"
@@ -164,6 +170,9 @@ _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assem
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
          "plmc_loo_grad": "plmc_loo_grad_lper"}
+_DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
+        "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
+        "plmc_loo_grad": "plmc_loo_grad_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
        "plmc_loo_grad": "plmc_loo_grad_rq"}
@@ -191,6 +200,10 @@ def sum_members(kind):
     return kind[len(SUM) + 1:-1].split(",")
 
 
+def is_dot(kind):
+    return dot_power(kind) is not None
+
+
 def is_sm(ell):
     return ell.dim() == 4
 
@@ -209,8 +222,9 @@ def n_components(ell, kind=None):
 
 def kind_code(kind):
     """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic, the locally
-    periodic and the rational-quadratic kernel likewise: their name stands in the code's place and sends _kernel_call to them."""
-    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) or is_sum(kind) else _hip.KIND[kind])
+    periodic, the rational-quadratic and the dot-product kernels likewise: their name stands in the code's place and sends _kernel_call
+    to them."""
+    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) or is_sum(kind) or is_dot(kind) else _hip.KIND[kind])
 
 
 def grad_table_width(ell, kind=None):
@@ -218,7 +232,8 @@ def grad_table_width(ell, kind=None):
     spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights];
     periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale];
     locally periodic: ell[0] is the three rows (3, d), [d/d lengthscales | d/d periods | d/d RBF lengthscales | d/d noise | d/d oscale];
-    rational quadratic: ell[0] is (d + 1), [d/d lengthscales | d/d alpha | d/d noise | d/d oscale]."""
+    rational quadratic: ell[0] is (d + 1), [d/d lengthscales | d/d alpha | d/d noise | d/d oscale];
+    dot product: ell[0] is (d + 1), [d/d variances | d/d offset | d/d noise | d/d oscale]."""
     return ell[0].numel() + 1 + n_components(ell, kind)
 
 
@@ -233,6 +248,14 @@ def _check_kernel_shape(L, ell, kind=None):
         if d > L.cdll.plmc_sum_max_dim() or len(members) > L.cdll.plmc_sum_max_components():
             raise ValueError("sum of %d kernels on %d dimensions exceeds plmc_sum_max_components()=%d / plmc_sum_max_dim()=%d"
                              % (len(members), d, L.cdll.plmc_sum_max_components(), L.cdll.plmc_sum_max_dim()))
+        return
+    if is_dot(kind):
+        d, P = ell.shape[-1] - 1, dot_power(kind)
+        if ell.dim() != 2 or d < 1:
+            raise ValueError("a dot-product kernel's table is (q, d + 1) = [variances | offset]")
+        if d > L.cdll.plmc_dot_max_dim() or P < 1 or P > L.cdll.plmc_dot_max_power():
+            raise ValueError("dot-product kernel of power %d on %d dimensions exceeds plmc_dot_max_power()=%d / plmc_dot_max_dim()=%d"
+                             % (P, d, L.cdll.plmc_dot_max_power(), L.cdll.plmc_dot_max_dim()))
         return
     d = ell.shape[-1] - (1 if kind == RQ else 0)
     if kind == RQ:
@@ -265,7 +288,8 @@ def _kernel_call(L, base, dt, head, ell, tail, stream=None):
     """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
     form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER, or its
     locally periodic form (*head[1:], lengthscales, periods, RBF lengthscales, *tail) when head[0] is LPER, or its rational-quadratic form
-    (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ.
+    (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ, or its dot-product form (*head[1:], variances, offset, P, *tail) when head[0]
+    is "linear" or "poly<P>".
     A heterogeneous sum (head[0] a "sum(...)" kind) goes to its form (*head[1:], G, fam, table, *tail); it copies nothing.
     `stream`: the side stream the call is queued on, if not the current one."""
     if is_sum(head[0]):
@@ -274,6 +298,16 @@ def _kernel_call(L, base, dt, head, ell, tail, stream=None):
             codes = [_hip.FAM[m_] for m_ in sum_members(head[0])]
             fam = ell._sum_fam = (head[0], (ctypes.c_int * len(codes))(*codes))
         L.call(_SUM[base], dt, *head[1:], ell.shape[1], ctypes.addressof(fam[1]), _hip.ptr(ell), *tail)
+        return
+    if isinstance(head[0], str) and is_dot(head[0]):
+        rows = getattr(ell, "_dot_rows", None)               # split once per table, as the rational-quadratic kernel's rows below
+        if rows is None:
+            d = ell.shape[1] - 1
+            rows = ell._dot_rows = (ell[:, :d].contiguous(), ell[:, d].contiguous())
+        if stream is not None:
+            rows[0].record_stream(stream)
+            rows[1].record_stream(stream)
+        L.call(_DOT[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), dot_power(head[0]), *tail)
         return
     if isinstance(head[0], str) and head[0] == RQ:
         rows = getattr(ell, "_rq_rows", None)                # split once per table, as the periodic kernel's rows below
@@ -703,8 +737,8 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     yc = _contig(y).reshape(q, 1, n)
     st = _hip.stream_ptr(dev)
     mode = settings.prediction_cache.value() if cache is not None else "off"
-    if key is not None and is_sum(kind):
-        key = key + (kind,)                                # the members are part of the state a cached factorisation belongs to
+    if key is not None and (is_sum(kind) or is_dot(kind)):
+        key = key + (kind,)                                # the members / the power are part of the state a cached factorisation belongs to
     hit = False
     if cache is not None and mode != "off":
         ws = cache.ws
@@ -751,7 +785,7 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
         cov = Kss - gemm_tn(V, V)                                   # V^T V on the library's tile engine (plmc_gemm_tn)
         return mean, cov
     from .kernels import prior_diagonal
-    var = prior_diagonal(kind, Xsc, osc, q) - vsq                      # k(x*, x*) = 1 for the stationary kinds (additive: sum_g os_g)
+    var = prior_diagonal(kind, Xsc, osc, q, ellc) - vsq                # k(x*, x*) = 1 for the stationary kinds (additive: sum_g os_g)
     return mean, var
 
 

@@ -31,6 +31,7 @@ _TYPED = {
     "plmc_assemble_lper": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_sum": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_rq": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    "plmc_assemble_dot": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _I, _P],
     "plmc_assemble_sm": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
     "plmc_write_rhs": [_P, _I, _I, _P, _L, _L, _I, _I, _I, _P],
     "plmc_assemble_cross": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
@@ -39,6 +40,7 @@ _TYPED = {
     "plmc_assemble_cross_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
+    "plmc_assemble_cross_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_assemble_cross_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_potrf": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P],
     "plmc_potrf_ex": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
@@ -48,6 +50,7 @@ _TYPED = {
     "plmc_factorize_lper_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_sum_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_rq_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
+    "plmc_factorize_dot_ex": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_factorize_sm_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
     "plmc_potrs_aug_kept": [_P, _L, _L, _I, _L, _L, _P, _I, _P, _P],
@@ -65,6 +68,7 @@ _TYPED = {
     "plmc_kinv_grad_lper_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sum_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_rq_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
+    "plmc_kinv_grad_dot_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
     "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
@@ -72,6 +76,7 @@ _TYPED = {
     "plmc_loo_grad_lper": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sum": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_grad_rq": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_loo_grad_dot": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
@@ -105,6 +110,8 @@ _PLAIN = {
     "plmc_sum_max_dim": ([], _I),
     "plmc_sum_grad_partials_bytes": ([_L, _I, _I, _I], _L),
     "plmc_rq_max_dim": ([], _I),
+    "plmc_dot_max_dim": ([], _I),
+    "plmc_dot_max_power": ([], _I),
     "plmc_qr_max": ([], _I),
     "plmc_last_error": ([], _c.c_char_p),
     "plmc_grad_scratch_bytes": ([_L, _I], _L),

@@ -239,6 +239,88 @@ class RQKernel(Kernel):
         return self.kind, torch.cat([self._ell(d, like), self.alpha.reshape(-1, 1)], 1), None
 
 
+def dot_power(kind):
+    """The power P of a dot-product kind -- "linear" (1) or "poly<P>" -- or None for every other kind.  P travels in the kind string, so
+    it survives add_noise and tells prediction-cache keys apart."""
+    if kind == "linear":
+        return 1
+    if isinstance(kind, str) and kind.startswith("poly") and kind[4:].isdigit():
+        return int(kind[4:])
+    return None
+
+
+class _DotKernel(Kernel):
+    """What LinearKernel and PolynomialKernel share: the dot-product family of the batched exact engine (include/plmc.h, "Dot-product
+    kernels"),  k(x, x') = (c + sum_k v_k x_k x'_k)^P.  No lengthscale; NOT stationary (k(x, x) depends on x).  SGPR, the dense LMC / ICM,
+    the variational models, the additive kernel and the product kernel refuse them."""
+    has_lengthscale = False
+    is_stationary = False
+
+    def _register(self, name, shape, constraint):
+        self.register_parameter("raw_" + name, torch.nn.Parameter(torch.zeros(*shape)))
+        setattr(self, "raw_%s_constraint" % name, constraint or Positive())
+
+    def _get(self, name):
+        return getattr(self, "raw_%s_constraint" % name).transform(getattr(self, "raw_" + name))
+
+    def _set(self, name, value):
+        raw = getattr(self, "raw_" + name)
+        value = torch.as_tensor(value, dtype=raw.dtype, device=raw.device)
+        with torch.no_grad():
+            raw.copy_(getattr(self, "raw_%s_constraint" % name).inverse_transform(value).expand_as(raw))
+
+
+class LinearKernel(_DotKernel):
+    """Linear kernel [gpytorch-knowledge: LinearKernel, unverified offline]: k(x, x') = sum_k v_k x_k x'_k -- Bayesian linear regression
+    with prior variance v_k on the k-th weight.  gpytorch's parameter name and shape, so state dicts line up: raw_variance
+    (*batch, 1, 1 if ard_num_dims is None else ard_num_dims), zero-initialised, Positive constraint.  Kernel kind "linear".  The prior has
+    rank <= d: without noise the matrix is singular for n > d."""
+    kind = "linear"
+
+    def __init__(self, ard_num_dims=None, batch_shape=torch.Size(), active_dims=None, variance_prior=None, variance_constraint=None,
+                 **kwargs):
+        kwargs.pop("lengthscale_prior", None)                 # (handle_covar_ passes one to every kernel; this one has no lengthscale)
+        kwargs.pop("lengthscale_constraint", None)
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, active_dims=active_dims, **kwargs)
+        self.variance_prior = variance_prior
+        self._register("variance", (*self.batch_shape, 1, 1 if ard_num_dims is None else int(ard_num_dims)), variance_constraint)
+
+    variance = property(lambda self: self._get("variance"), lambda self, v: self._set("variance", v))
+
+    def _pieces(self, d, like=None):
+        """The table (q, d + 1) = [variances | 0] and no output scale; the offset column is a constant."""
+        v = self.variance.reshape(-1, self.variance.shape[-1])
+        if v.shape[-1] != d:
+            v = v.expand(v.shape[0], d)
+        return self.kind, torch.cat([v, torch.zeros_like(v[:, :1])], 1), None
+
+
+class PolynomialKernel(_DotKernel):
+    """Polynomial kernel [gpytorch-knowledge: PolynomialKernel, unverified offline]: k(x, x') = (x . x' + c)^P, P an integer >= 1.
+    gpytorch's parameter name and shape: raw_offset (*batch, 1), zero-initialised, Positive constraint.  Kernel kind "poly<P>": the power
+    is part of the kind."""
+
+    def __init__(self, power=None, offset_prior=None, offset_constraint=None, batch_shape=torch.Size(), active_dims=None, **kwargs):
+        if power is None:
+            raise RuntimeError("power is a required argument")
+        if isinstance(power, bool) or not isinstance(power, int) or power < 1:
+            raise RuntimeError("power expected to be an int >= 1, got %r" % (power,))
+        kwargs.pop("lengthscale_prior", None)                 # (see LinearKernel)
+        kwargs.pop("lengthscale_constraint", None)
+        super().__init__(ard_num_dims=kwargs.pop("ard_num_dims", None), batch_shape=batch_shape, active_dims=active_dims, **kwargs)
+        self.power = power
+        self.kind = "poly%d" % power
+        self.offset_prior = offset_prior
+        self._register("offset", (*self.batch_shape, 1), offset_constraint)
+
+    offset = property(lambda self: self._get("offset"), lambda self, v: self._set("offset", v))
+
+    def _pieces(self, d, like=None):
+        """The table (q, d + 1) = [1 | offset] and no output scale; the variance columns are constants."""
+        c = self.offset.reshape(-1, 1)
+        return self.kind, torch.cat([torch.ones(c.shape[0], d, dtype=c.dtype, device=c.device), c], 1), None
+
+
 class ProductKernel(Kernel):
     """Product of kernels [gpytorch-knowledge: ProductKernel, the elementwise product of its factors, unverified offline] -- what
     `k1 * k2` returns.  One product is served, the LOCALLY PERIODIC kernel PeriodicKernel * RBFKernel (either order):
@@ -297,6 +379,12 @@ def refuse_rq(kernel, model):
     _refuse(RQKernel, "RQKernel", kernel, model)
 
 
+def refuse_dot(kernel, model):
+    """The dot-product kernels run on the batched exact engine only: name the model that cannot take them, and the class."""
+    _refuse(LinearKernel, "LinearKernel", kernel, model)
+    _refuse(PolynomialKernel, "PolynomialKernel", kernel, model)
+
+
 def refuse_sum(kernel, model):
     """A sum of different kernel families (additive.AdditiveKernel with mixed members, kind "sum(...)") runs on the batched exact engine
     only: name the model that cannot take it, and the members.  A sum of one stationary kind goes wherever it went.  `kernel` is an
@@ -315,11 +403,18 @@ def refuse_sm(kernel, model):
     _refuse(SpectralMixtureKernel, "SpectralMixtureKernel", kernel, model)
 
 
-def prior_diagonal(kind, x, oscale, q):
-    """k(x, x) per latent, (q, n): 1 for the stationary kinds, prod_k (1 + x_k^2 + x_k^3 / 3) for the spline kernel."""
+def prior_diagonal(kind, x, oscale, q, table=None):
+    """k(x, x) per latent, (q, n): 1 for the stationary kinds, prod_k (1 + x_k^2 + x_k^3 / 3) for the spline kernel,
+    (c + sum_k v_k x_k^2)^P for a dot-product kind, which needs its `table` (q, d + 1) = [v | c]; no other kind looks at it."""
     if kind == "sm" and oscale is None:                        # unit weights: k(x, x) = M needs the table, not known here
         raise ValueError("prior_diagonal: a spectral mixture needs its weights")
-    if kind == "spline":
+    P = dot_power(kind)
+    if P is not None:
+        if table is None:
+            raise ValueError("prior_diagonal: a dot-product kernel needs its table")
+        table = table.to(x.dtype)
+        dg = (table[:, -1:] + table[:, :-1] @ (x * x).transpose(-1, -2)) ** P
+    elif kind == "spline":
         dg = (1 + x ** 2 + x ** 3 / 3).prod(dim=-1).reshape(1, -1).expand(q, -1)
     else:
         dg = torch.ones(q, x.shape[-2], dtype=x.dtype, device=x.device)
@@ -365,7 +460,8 @@ class LazyKernel:
     the lengthscales and, in its last column, alpha; oscale (q) | None.  kind "locally_periodic": ell (q, 3, d) holds the periodic
     lengthscales, the periods and the RBF lengthscales, oscale (q) | None.  kind "sum(<member>,...)": a sum of different families
     (additive.py); the member kinds travel in the kind string (so through add_noise and into the prediction cache's key), ell
-    (q, G, 3 d + 1) holds one record [lengthscales | periods | RBF lengthscales | alpha] per member, oscale (q, G)."""
+    (q, G, 3 d + 1) holds one record [lengthscales | periods | RBF lengthscales | alpha] per member, oscale (q, G).  kind "linear" /
+    "poly<P>": ell (q, d + 1) holds the variances and, in its last column, the offset of a dot-product kernel; oscale (q) | None."""
 
     def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
         self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise
@@ -402,7 +498,7 @@ class LazyKernel:
 
     def diagonal(self, *args, **kwargs):
         q = self.ell.shape[0]
-        dg = prior_diagonal(self.kind, self.x1.to(self.ell.dtype), self.oscale, q)
+        dg = prior_diagonal(self.kind, self.x1.to(self.ell.dtype), self.oscale, q, self.ell)
         if self.noise is not None:
             dg = dg + self.noise.reshape(-1, 1)
         return dg.reshape(*self.batch_shape, -1)

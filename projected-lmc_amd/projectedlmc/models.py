@@ -58,6 +58,7 @@ def handle_covar_(kernel, dim, decomp=None, n_funcs=1, prior_scales=None, prior_
         _k.refuse_sm(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         _k.refuse_periodic(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         _k.refuse_rq(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
+        _k.refuse_dot(kernel, "handle_covar_(decomp=...) with several groups (the additive kernel)")
         # k(x) = sum_g s_g k_g(x[idx_g]): every sub-kernel gets an output scale (:159-162)
         from .additive import AdditiveKernel
         subs = []
@@ -279,6 +280,7 @@ class ExactGPModel(ExactGP):
             _k.refuse_sm(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_periodic(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_rq(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
+            _k.refuse_dot(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_product(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             _k.refuse_sum(self.covar_module, "ExactGPModel(n_inducing_points=...) (SGPR)")
             from .sgpr import InducingPointKernel

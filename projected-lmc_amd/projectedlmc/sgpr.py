@@ -24,10 +24,11 @@ from .kernels import Kernel
 
 class InducingPointKernel(Kernel):
     def __init__(self, base_kernel, inducing_points, likelihood, active_dims=None, jitter=0.0):
-        from .kernels import refuse_periodic, refuse_product, refuse_rq, refuse_sm, refuse_sum
+        from .kernels import refuse_dot, refuse_periodic, refuse_product, refuse_rq, refuse_sm, refuse_sum
         refuse_sm(base_kernel, "InducingPointKernel (SGPR)")
         refuse_periodic(base_kernel, "InducingPointKernel (SGPR)")
         refuse_rq(base_kernel, "InducingPointKernel (SGPR)")
+        refuse_dot(base_kernel, "InducingPointKernel (SGPR)")
         refuse_product(base_kernel, "InducingPointKernel (SGPR)")
         refuse_sum(base_kernel, "InducingPointKernel (SGPR)")
         super().__init__(active_dims=active_dims)

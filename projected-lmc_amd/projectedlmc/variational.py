@@ -206,6 +206,7 @@ class VariationalMultitaskGPModel(torch.nn.Module):
         _k.refuse_sm(kernel_type, "VariationalMultitaskGPModel")
         _k.refuse_periodic(kernel_type, "VariationalMultitaskGPModel")
         _k.refuse_rq(kernel_type, "VariationalMultitaskGPModel")
+        _k.refuse_dot(kernel_type, "VariationalMultitaskGPModel")
         if ker_kwargs is None:
             ker_kwargs = {}
         if train_x.ndimension() == 1:
