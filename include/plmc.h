@@ -919,8 +919,9 @@ int plmc_qr_small_f64(const double *A, int m, int n, int64_t lda, double *Q, int
  * serialised by one library-wide lock while they enqueue (the kernels overlap on the device as their streams allow); each
  * thread keeps its own choice of sweep set.  The Python layer calls from one thread per process.
  * Dev knobs are environment variables read once per process (PLMC_HALF_TILES, PLMC_GRP,
- * PLMC_SERIAL, PLMC_BULK_LDS, PLMC_CHAIN, PLMC_CHAIN_NW, PLMC_CHAIN_EDGE); plmc_dev_reload_knobs() re-reads them (tests and bench.py change one and reload).  They change
- * schedules; PLMC_GRP also changes the depth of the updates and with it the rounding.  PLMC_SPLIT (0, 2, 3) selects the
+ * PLMC_SERIAL, PLMC_BULK_LDS, PLMC_CHAIN, PLMC_CHAIN_NW, PLMC_CHAIN_EDGE, PLMC_TAIL_PAIR); plmc_dev_reload_knobs() re-reads them (tests and bench.py change one and reload).  They change
+ * schedules; PLMC_GRP and PLMC_TAIL_PAIR (1 = default: the split engines apply the far part of two consecutive trailing updates as one
+ * product of twice the depth; 0 = one per group) also change the depth of the updates and with it the rounding.  PLMC_SPLIT (0, 2, 3) selects the
  * arithmetic of the bulk fp32 products (see plmc_potrf_ex_f32).  Buffer sizes do not depend on any knob.
  * plmc_prof_mfma_rate: dense MFMA rate (TFLOP/s) of the current device measured with a bare instruction stream
  * (v_mfma_f32_16x16x4_f32, _f64_16x16x4_f64 or v_mfma_f32_16x16x32_bf16, 4 waves per SIMD, no memory traffic); synchronous; `sink` = caller-owned

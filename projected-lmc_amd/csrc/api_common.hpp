@@ -58,8 +58,8 @@ struct ProfScope {
 };
 
 // Dev knobs (environment variables), read ONCE per process on first use; plmc_dev_reload_knobs() re-reads them (the
-// tests and bench.py change a knob and reload).  They change schedules; PLMC_GRP also changes the depth of the updates (and
-// with it the rounding), PLMC_SPLIT selects the arithmetic of the bulk fp32 products.
+// tests and bench.py change a knob and reload).  They change schedules; PLMC_GRP and PLMC_TAIL_PAIR also change the depth of the
+// updates (and with it the rounding), PLMC_SPLIT selects the arithmetic of the bulk fp32 products.
 struct Knobs {
   double half_tiles;   // PLMC_HALF_TILES: 0 never, 1 always, N > 1 = tile-count threshold (default 640)
   int grp;             // PLMC_GRP: fixed group size of the sweep (default 0 = 8)
@@ -71,6 +71,8 @@ struct Knobs {
   int bulk_streams;    // PLMC_BULK_STREAMS: 2 = group panel + head rows on their own helper stream beside the tail, 1 = in front of the tail on the caller's stream
   int chain;           // PLMC_CHAIN: 1 (default) = the chain of a group as one resident launch (k_chain), 0 = three launches per block row
   int chain_edge;      // PLMC_CHAIN_EDGE: pool size for the first and the last two groups of a sweep (<= 0: as the others)
+  int tail_pair;       // PLMC_TAIL_PAIR: 1 (default) = the split engines apply the far part of every second tail together with the next one, as one
+                       // product of twice the depth (potrf.hip, Sweep::pair); 0 = one tail per group
   int chain_nw;        // PLMC_CHAIN_NW: pool workgroups of the resident chain beside the q critical ones (0 = by the number of latents)
 };
 const Knobs &knobs();

@@ -411,9 +411,11 @@ __global__ __launch_bounds__(64) void k_split_scales(int64_t n_pad, const float 
 // products on the 16-bit matrix cores (bf3_engine.hpp).  A workgroup of 512 threads takes the macro tile (block rows ib, ib + 1) x (column tile
 // bx).  The operands are the panel rows of the current group, which k_gpanel_bf3 / k_wtri_planes also write as k8-ordered
 // bf16 planes into a rolling two-group buffer `Pl` (per buffer b3_elems(128 GMAX, lda) elements, same column coordinates as
-// the factor buffer); tile decoding, skip and depth rules and the write-back are those of k_update, per half.
+// the factor buffer; four slots of 128 grp rows, back to back, when the sweep pairs its tails: Sweep::planes); tile decoding, skip and depth rules and the write-back are those of k_update, per half.
 // Block rows ib < raw_end are the NEXT group's rows and this is their last update: their final values also go, as planes,
 // into `Praw` (row 128 (ib - ib0) .., same columns) -- the right-hand side of the next group panel (k_gpanel_bf3).
+// ROLE: as k_update's, except 1 = the "near" rows of a sweep that pairs its tails (Sweep::lookahead: rows R2; bulk, no priority).  A
+// paired launch hands in the rows of TWO groups (r_lo .. r_hi) and `Pl` = the slot of the first, the second group's slot right behind it.
 // grid (nU + Taug + nW, (nrows + 1) / 2, q).
 template <class S, int ROLE>
 __global__ __launch_bounds__(B3_NT, 2) void k_update_bf3(float *A, int64_t lda, int64_t strideA, int ib0, int nrows, int r_lo, int r_hi,
@@ -873,8 +875,11 @@ struct Sweep {
   // null unless it runs, the full-height planes of W also without the inverse factor, the kept buffers unless `keep`.
   T *Vd, *Wg, *Vg2[2], *Ph, *Pbulk;
   unsigned short *Pl[2], *Praw, *VgP2[2], *Wk, *Uk;
+  unsigned short *Pl4 = nullptr;                  // paired tails: the first of four plane slots, slot_step 16-bit elements each
   float *scl;
   int64_t strideV, pl_lat, sc_lat, uk_step;       // uk_step: 16-bit elements per kept buffer
+  int64_t slot_step = 0;
+  bool pair = false;                              // the far part of every second tail goes with the next one (lookahead)
   T *WA;                                          // inverse-factor columns of the factor buffer (nullptr without them)
   const Knobs &kn;                                // dev knobs: read once per process (api.hip)
   double hthr;
@@ -910,6 +915,15 @@ struct Sweep {
     // Group boundaries.  Large groups divide the read-modify-write traffic of the trailing matrix by G and put
     // G (G + 1) / 2 tile products into every group-panel strip; the chain of a group costs ~3 G small launches.
     ng = (m + grp - 1) / grp;
+    // Paired tails (PLMC_TAIL_PAIR, split engines): a pair of groups must be ONE run of k8 rows for the depth-(2 x 128 grp) product, so
+    // the solved rows roll over four slots of exactly 128 grp rows each, slot = group & 3, from the start of pbulk (VdLayout).  Where
+    // the four do not fit in front of Praw (three planes at grp > 5) and for a sweep that keeps its planes (one buffer per group:
+    // plmc_potrs_aug_kept walks those) the sweep stays on one tail per group.
+    if constexpr (bf3) {
+      slot_step = b3_elems<S>((int64_t)grp * NB, lda);
+      pair = kn.tail_pair != 0 && !keep && 4 * slot_step <= L.slot_room();
+      if (pair) Pl4 = L.at<unsigned short>(Vd, L.pbulk);
+    }
     chain_pool = kn.chain_nw > 0 ? (kn.chain_nw < 200 ? kn.chain_nw : 200) : (q >= 8 ? 80 : (q >= 4 ? 44 : (q >= 2 ? 36 : 31)));   // (PLMC_CHAIN_NW > 80: dev only)
   }
 
@@ -921,7 +935,13 @@ struct Sweep {
   // ... or the factor buffer's own columns (aug + inverse factor)
   ColMap<T> cm_buf(int u0, int nU, int taug, int w0, int nW) const { return ColMap<T>{u0, nU, taug, w0, WA ? nW : 0, n_pad, WA, lda, strideA}; }
   // split engine: plane buffer of the solved rows of the group that starts at block row g0
-  unsigned short *planes(int g0) const { return keep ? Uk + (int64_t)(g0 / grp) * uk_step : Pl[(g0 / grp) & 1]; }
+  // (paired tails: slots k and k + 1 are adjacent, so the slot of a pair's first group is the buffer of both)
+  unsigned short *planes(int g0) const {
+    const int gi = g0 / grp;
+    return keep ? Uk + (int64_t)gi * uk_step : (pair ? Pl4 + (int64_t)(gi & 3) * slot_step : Pl[gi & 1]);
+  }
+  // paired tails: first block row of the depth near(gi) / far(gi) apply -- an odd group brings the group before it along
+  int pair_lo(int gi) const { return G0((gi & 1) ? gi - 1 : gi); }
 
   // tiles of the diagonal-block outputs that k_diag leaves alone (they are read as parts of full 128 x 128 operands), and the chain
   // kernel's control words in the pad column of Wg
@@ -951,8 +971,9 @@ struct Sweep {
   // PK_TRAIL_ROW (rank-128 update inside a group's triangle)
   // raw_end (split engine): block rows below it are the next group's -- this launch is their last update and also writes
   // their planes (Praw) for the next group panel
+  // near (split engine, paired tails): the tail's rows R2, under a kernel symbol of their own (k_update_bf3 ROLE 1)
   void update(int ib0, int nrows, int r_lo, int r_hi, const ColMap<T> &cm, hipStream_t s, int cls, int skip_ib = 0, int skip_jb = 0,
-              bool crit = false, int raw_end = 0) {
+              bool crit = false, int raw_end = 0, bool near = false) {
     const int Cn = cm.nU + cm.Taug + cm.nW;
     if (nrows <= 0 || Cn == 0) return;
     const double depth = (r_hi - r_lo + 1) * nb, nr = (double)nrows;
@@ -985,7 +1006,8 @@ struct Sweep {
 #define PLMC_UPD3(ROLE)                                                                                                                    \
   hipLaunchKernelGGL((k_update_bf3<S, ROLE>), grid, dim3(B3_NT), 0, s, A, lda, strideA, ib0, nrows, r_lo, r_hi, cm, skip_ib, skip_jb, pl, \
                      pl_lat, wcol0, Praw, pl_lat, raw_end, (const float *)scl, sc_lat, Wk, pl_lat)
-        if (cls == PK_TRAIL) PLMC_UPD3(0);
+        if (cls == PK_TRAIL && near) PLMC_UPD3(1);
+        else if (cls == PK_TRAIL) PLMC_UPD3(0);
         else if (crit) PLMC_UPD3(2);
         else PLMC_UPD3(3);
 #undef PLMC_UPD3
@@ -1122,6 +1144,18 @@ struct Sweep {
     }
   }
 
+  // paired tails (split engine; the schedule: lookahead).  near(gi): rows R2 = group gi + 2, the tail's columns, the depth of group gi
+  // (even gi) or of groups gi - 1 and gi (odd gi).  far(gi), odd gi only: every row below R2, groups gi - 1 and gi.
+  void near(int gi, hipStream_t s) {
+    const int g1 = G0(gi + 1), g2 = G0(gi + 2), g3 = G0(gi + 3);
+    update(g2, g3 - g2, pair_lo(gi), g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), s, PK_TRAIL, 0, 0, false, 0, true);
+  }
+  void far(int gi, hipStream_t s) {
+    if (!(gi & 1)) return;
+    const int g1 = G0(gi + 1), g3 = G0(gi + 3);
+    update(g3, m - g3, pair_lo(gi), g1 - 1, cm_buf(g3, m - g3, Taug, 0, g1), s, PK_TRAIL);
+  }
+
   // The helper streams and ordering events of THIS caller stream (api.hip: sweeps from different streams may overlap).  True when
   // the look-ahead can run: both helper streams and its nine events exist, and the sweep has more than two groups.
   bool bind_streams() {
@@ -1165,7 +1199,13 @@ struct Sweep {
       if (bf3) {
         gpanel(g0, g1 - g0, cm_buf(g1, g2 - g1, 0, 0, 0), gi & 1, st, 1);
         gpanel(g0, g1 - g0, cm_buf(g2, m - g2, Taug, 0, g0), gi & 1, st, 0);
-        update(g1, m - g1, g0, g1 - 1, cm_buf(g1, m - g1, Taug, 0, g1), st, PK_TRAIL, g2, g2, false, g2);
+        if (pair) {                                          // head, near, far as under the look-ahead
+          update(g1, g2 - g1, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL_HEAD, 0, 0, false, g2);
+          near(gi, st);
+          far(gi, st);
+        } else {
+          update(g1, m - g1, g0, g1 - 1, cm_buf(g1, m - g1, Taug, 0, g1), st, PK_TRAIL, g2, g2, false, g2);
+        }
         update(g1, g2 - g1, g0, g1 - 1, cm_buf(g1, g2 - g1, 0, 0, 0), st, PK_TRAIL_HEAD, 0, 0, true);
       } else {
         gpanel(g0, g1 - g0, cm_buf(g1, m - g1, Taug, 0, g0), gi & 1, st, 0);
@@ -1187,6 +1227,25 @@ struct Sweep {
   // gpanel_rest(gi) read: by then C has waited for e_hd(gi), recorded behind it.  U1 / head / tail touch disjoint
   // tiles; every tile receives its updates in the same order as on one stream, so the result is bit-identical to the
   // serial schedule (tests/test_gpu_edges.py).
+  // Paired tails (`pair`: split engines, PLMC_TAIL_PAIR=1).  The update C -= P^T P need not be applied group by group: rows that
+  // nobody reads for two more groups take two groups' updates as ONE product of twice the depth -- one prologue, one C load and
+  // one C store instead of two of each.  The tail splits into
+  //   near(gi): rows R2, the tail's columns; depth = group gi (even gi) or groups gi - 1 and gi (odd gi) -> [e_tail]
+  //   far(gi):  rows below R2, odd gi only; depth = groups gi - 1 and gi.  Even gi: no launch.
+  // both on T, near first.  U1 and head are unchanged (rows R1, depth of group gi; the head still writes the raw planes).  Row group r
+  // receives every group k < r exactly once, in the order of k:
+  //   from        | r even                     | r odd
+  //   far(1, 3..) | 0 .. r - 3, in pairs       | 0 .. r - 4, in pairs          (far(gi): rows of the groups >= gi + 3)
+  //   near(r - 2) | r - 2                      | r - 3 and r - 2
+  //   head(r - 1) | r - 1                      | r - 1
+  // (so the last tail of a sweep with an odd number of tails is a near of one group's depth and has no far: nothing lies below its
+  // rows).  Ordering: head(gi + 1) / U1(gi + 1) wait for near(gi) [e_tail] -- far(gi - 1), which wrote the same rows, is in front of
+  // it on T; far(gi) runs beside the chains and panels of the groups gi + 1 and gi + 2 and is complete before near(gi + 1) (T).  The
+  // planes of the solved rows roll over FOUR slots, slot = group & 3 (Sweep::planes): gpanel(gi) overwrites the rows of group
+  // gi - 4, last read by far(gi - 3) or far(gi - 4); both panel launches of gi are behind head(gi - 1) resp. its e_hd, and head(gi - 1)
+  // waited for e_tail of near(gi - 2), which T ran behind those fars.  The one-stream form issues the same launches one after the
+  // other.  A paired tile rounds its level-0 sum once over the double depth instead of subtracting twice, so the results differ
+  // from PLMC_TAIL_PAIR=0 in the last bits -- and are the same bits under every schedule.
   // A sweep that also assembles (plmc_factorize_ex_*, `job`): only the first group's own block triangle is written in front of the
   // chain, everything else rides on the helper stream H beside the first group's chain (the first consumer, the transpose + head
   // panel of group 0, waits for it: e_sc).  So does the scan for the scales -- but only of the rows below the first group: chain(0)
@@ -1240,8 +1299,14 @@ struct Sweep {
 
       (void)hipStreamWaitEvent(st, e_p, 0);
       (void)hipStreamWaitEvent(st, e_gh, 0);
-      update(g2, m - g2, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL);         // tail: rows below R1
-      (void)hipEventRecord(e_tail, st);
+      if (pair) {
+        near(gi, st);                                                                          // rows R2: all that head(gi + 1) / U1(gi + 1) wait for
+        (void)hipEventRecord(e_tail, st);
+        far(gi, st);                                                                           // odd gi: rows below R2, groups gi - 1 and gi
+      } else {
+        update(g2, m - g2, g0, g1 - 1, cm_buf(g2, m - g2, Taug, 0, g1), st, PK_TRAIL);         // tail: rows below R1
+        (void)hipEventRecord(e_tail, st);
+      }
     }
     // log det and the pivot / abort check read the diagonal of U and the chain kernels' control words: final behind the last chain,
     // so they ride on the chain stream beside the last group's panel instead of behind the whole sweep (25 us + a launch gap)

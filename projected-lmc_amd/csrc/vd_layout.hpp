@@ -42,6 +42,10 @@ inline int64_t vd_wk_blocks(int64_t n_pad, int64_t lda, int elem_bytes) {
 //   pbulk    panel buffer of the other columns (GMAX block rows, ld lda)
 //   4-byte elements only, 16-bit planes in k8 order (bf3_engine.hpp):
 //   pl[2]    rolling two-group buffer of the solved panel rows (128 GMAX rows x lda columns each: `plane_blocks`)
+//            A sweep that pairs its tails (potrf.hip, Sweep::pair) rolls over FOUR slots instead, slot = group & 3, laid back to
+//            back from the start of pbulk -- the split engine's group panel works in place and never uses pbulk -- so that the
+//            rows of a pair of groups are one contiguous run of k8 rows: `slot_room` 16-bit elements in front of praw.  The
+//            sizes and offsets of the layout (pinned as part of the ABI) do not change for it.
 //   praw     the raw rows of the group whose panel comes next (one such buffer)
 //   vgp[2]   planes of Vgg (128 GMAX x 128 GMAX), ping-pong like vg
 //   scl      the scale block (SC_*)
@@ -87,6 +91,8 @@ struct VdLayout {
     }
     blocks = b;
   }
+  // 16-bit elements between the start of pbulk and praw: room for the four slots of a sweep that pairs its tails
+  int64_t slot_room() const { return praw < 0 ? 0 : (praw - pbulk) * (int64_t)NB * NB * 2; }
   int64_t stride() const { return blocks * NB * NB; }                         // per latent, in elements
   int64_t stride_u16() const { return stride() * (elem_bytes / 2); }           // ... in 16-bit plane elements
   int64_t stride_f32() const { return stride() * elem_bytes / 4; }             // ... in floats
