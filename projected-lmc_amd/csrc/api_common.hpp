@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "gemm_core.hpp"
 #include "covariance.hpp"
@@ -78,7 +79,8 @@ struct Knobs {
 const Knobs &knobs();
 
 // One covariance table: what a kernel family hands to the host layer, and the ONE place a family is declared to it.  Only the extern "C"
-// wrappers build one (from their flat arguments); assemble_impl, assemble_cross_impl, the sweep's AssembleJob and kinv_grad_impl take it.
+// wrappers build one (from their flat arguments, PLMC_FAMILY_ENTRIES below); assemble_impl, assemble_cross_impl, the sweep's AssembleJob,
+// kinv_grad_impl and loo_grad_impl take it.
 //   PLAIN  one ARD kernel of `kind` (covariance.hpp): ell (q, d), oscale (q) | null
 //   ADD    ncomp <= MAX_COMP stationary kernels of `kind` summed: ell (q, ncomp, d), oscale (q, ncomp) | null
 //   SM     spectral mixture of ncomp components: ell = its scales, second = its means (q, ncomp, d), oscale = its weights (q, ncomp) | null
@@ -93,6 +95,81 @@ const Knobs &knobs();
 //          power P (power()), 1 <= P <= DOT_MAX_POWER -- one component, so the slot is free
 // `kind` is not looked at for SM, PER, RQ, LPER, SUM and DOT; the pointers are of the call's element type.  `third` is null for every other family.
 enum CovFamily { COV_PLAIN, COV_ADD, COV_SM, COV_PER, COV_RQ, COV_LPER, COV_SUM, COV_DOT };
+
+// What the host layer knows about a family beside its table, one row per CovFamily in the order of the enumerators: CovTable::check(), the
+// capacity ladder (with_capacity), the routing of the fp32 gradient call (potri_grad.hip, kinv_grad_any) and the occupancy floor of the
+// gradient kernels (table_min_waves) read it; nothing else lists the families.
+constexpr int EVERY_D = 1 << 30, NEVER = 1 << 30;
+struct FamilyTraits {
+  int max_dim;                       // the family's own limit on d (0: none, MAX_DIM by the entry points' checks) ...
+  const char *dim_text;              // ... and the refusal
+  int max_count;                     // largest ncomp -- components, mixtures or power (0: not looked at) ...
+  const char *count_text;            // ... and the refusal
+  bool count_first;                  // which of the two is checked first
+  bool needs_second, needs_third;    // `second` / `third` must not be null
+  bool rows_per_comp;                // the gradient kernels write one row of partial sums per component (else one)
+  int max_dc;                        // largest capacity DC of its table kernels: the ladder is 1, 4, 8 [, 16]
+  // largest d whose gradient epilogue runs beside the split engine's two fp16 / three bf16 planes without spilling (above it the fp32
+  // products take the call whatever PLMC_SPLIT says): index NPL - 2.  The mixture keeps d sines, cosines and partial products per element
+  // live beside the accumulators, the periodic kernel d sines, cosine complements and 2 d sums, the locally periodic one 3 d sums: that fits
+  // the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel, so d = 1 only (the reference's use).  A
+  // heterogeneous sum may hold a periodic or a locally periodic member and follows their rule whatever its members are.  The
+  // rational-quadratic and the dot-product epilogue fit beside the two planes at every d; beside the three (PLMC_SPLIT=3, or no eig_lo)
+  // DC = 4, 8, 16 would spill.
+  int split_max_d[2];
+  const char *vd_noun;               // its split-engine gradient call takes the planes of W from the sweep's Vd only, and is refused by this
+                                     // name otherwise (null: it may split W itself)
+  int one_wave_dc[2];                // smallest DC at which k_kinv_grad_add / k_loo_grad_add ask for one wave per SIMD, not two: fp32, fp64
+};
+constexpr FamilyTraits FAMILY[] = {
+    /* PLAIN */ {0, nullptr, 0, nullptr, false, false, false, false, 0, {EVERY_D, EVERY_D}, nullptr, {NEVER, NEVER}},
+    /* ADD   */ {0, nullptr, MAX_COMP, "need 1 <= components <= plmc_max_components()", true, false, false, true, 0, {EVERY_D, EVERY_D}, nullptr,
+                 {NEVER, NEVER}},
+    /* SM    */ {SM_MAX_DIM, "need 0 < d <= plmc_sm_max_dim()", SM_MAX_MIX, "need 1 <= mixtures <= plmc_sm_max_mixtures()", true, true, false, true, 8,
+                 {1, 1}, "spectral-mixture", {NEVER, 1}},
+    /* PER   */ {PER_MAX_DIM, "need 0 < d <= plmc_per_max_dim()", 0, nullptr, false, true, false, false, 8, {1, 1}, "periodic", {NEVER, 2}},
+    /* RQ    */ {RQ_MAX_DIM, "need 0 < d <= plmc_rq_max_dim()", 0, nullptr, false, true, false, false, 16, {EVERY_D, 1}, "rational-quadratic", {NEVER, 1}},
+    /* LPER  */ {LPER_MAX_DIM, "need 0 < d <= plmc_lper_max_dim()", 0, nullptr, false, true, true, false, 8, {1, 1}, "locally periodic", {NEVER, 2}},
+    /* SUM   */ {SUM_MAX_DIM, "need 0 < d <= plmc_sum_max_dim()", MAX_COMP, "need 1 <= components <= plmc_sum_max_components()", true, false, false, true,
+                 8, {1, 1}, "sum", {5, 1}},
+    /* DOT   */ {DOT_MAX_DIM, "need 0 < d <= plmc_dot_max_dim()", DOT_MAX_POWER, "need 1 <= power <= plmc_dot_max_power()", false, true, false, false, 16,
+                 {EVERY_D, 1}, "dot-product", {NEVER, 1}},
+};
+static_assert(sizeof(FAMILY) / sizeof(FAMILY[0]) == COV_DOT + 1, "one row per CovFamily");
+
+// occupancy floor (the second __launch_bounds__ argument) of the table families' gradient kernels
+template <typename T, CovFamily F, int DC> constexpr int table_min_waves() { return DC >= FAMILY[F].one_wave_dc[sizeof(T) == 8] ? 1 : 2; }
+
+// The ONE capacity ladder of the table families (COV_SM .. COV_DOT): call(F, DC) with the family and the smallest capacity DC in {1, 4, 8
+// [, 16]} that holds d, both as std::integral_constant -- the callable is the launch of its site.  PLANES = 0: every d up to the family's
+// limit; PLANES = 2 / 3: the kernels that run beside that many planes of the split engine, i.e. DC = 1 alone where
+// FamilyTraits::split_max_d says so (no other instance exists there: it would spill, and the routing keeps d > 1 away).  COV_PLAIN and
+// COV_ADD have their own kernels and rules at every site and do not come here.
+template <int PLANES, CovFamily F, class Call>
+void with_capacity_of(int d, Call &&call) {
+  constexpr std::integral_constant<CovFamily, F> f{};
+  constexpr int top = PLANES != 0 && FAMILY[F].split_max_d[PLANES == 3] == 1 ? 1 : FAMILY[F].max_dc;   // 1, 8 or 16
+  if constexpr (top == 1) call(f, std::integral_constant<int, 1>());
+  else {
+    if (d == 1) call(f, std::integral_constant<int, 1>());
+    else if (d <= 4) call(f, std::integral_constant<int, 4>());
+    else if (top == 8 || d <= 8) call(f, std::integral_constant<int, 8>());
+    else call(f, std::integral_constant<int, top>());
+  }
+}
+template <int PLANES, class Call>
+void with_capacity(CovFamily family, int d, Call &&call) {
+  switch (family) {                  // (in the order the gradient kernels have in the code object: potri_grad.hip, kinv_grad_any)
+    case COV_PER: with_capacity_of<PLANES, COV_PER>(d, call); break;
+    case COV_LPER: with_capacity_of<PLANES, COV_LPER>(d, call); break;
+    case COV_SUM: with_capacity_of<PLANES, COV_SUM>(d, call); break;
+    case COV_RQ: with_capacity_of<PLANES, COV_RQ>(d, call); break;
+    case COV_DOT: with_capacity_of<PLANES, COV_DOT>(d, call); break;
+    case COV_SM: with_capacity_of<PLANES, COV_SM>(d, call); break;
+    case COV_PLAIN: case COV_ADD: break;
+  }
+}
+
 struct CovTable {
   CovFamily family;
   int kind, d, ncomp;
@@ -143,41 +220,51 @@ struct CovTable {
   bool single_member() const { return family == COV_SUM && ncomp == 1; }
   // the family's limits: the message of the first one missed, or null
   const char *check() const {
+    const FamilyTraits &f = FAMILY[family];
+    if (family == COV_ADD && (kind < 0 || kind > K_MATERN52)) return "additive kernels take the stationary kinds only (no spline kernel)";
+    const char *count = f.max_count && (ncomp < 1 || ncomp > f.max_count) ? f.count_text : nullptr;
+    const char *dim = f.max_dim && (d <= 0 || d > f.max_dim) ? f.dim_text : nullptr;
+    if (count || dim) return f.count_first ? (count ? count : dim) : (dim ? dim : count);
     if (family == COV_SUM) {
-      if (ncomp < 1 || ncomp > MAX_COMP) return "need 1 <= components <= plmc_sum_max_components()";
-      if (d <= 0 || d > SUM_MAX_DIM) return "need 0 < d <= plmc_sum_max_dim()";
       if (fams == -3 || !ell) return "null pointer";
       if (fams == -2) return "the spline kernel is not a member of a sum (members: the stationary kinds 0..3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER)";
       if (fams < 0) return "unknown member family code (members: the stationary kinds 0..3, PLMC_FAM_PERIODIC, PLMC_FAM_RQ, PLMC_FAM_LPER; no spectral mixture)";
-      return nullptr;
     }
-    if (family == COV_ADD) {
-      if (kind < 0 || kind > K_MATERN52) return "additive kernels take the stationary kinds only (no spline kernel)";
-      if (ncomp < 1 || ncomp > MAX_COMP) return "need 1 <= components <= plmc_max_components()";
-    } else if (family == COV_SM) {
-      if (ncomp < 1 || ncomp > SM_MAX_MIX) return "need 1 <= mixtures <= plmc_sm_max_mixtures()";
-      if (d <= 0 || d > SM_MAX_DIM) return "need 0 < d <= plmc_sm_max_dim()";
-    } else if (family == COV_PER) {
-      if (d <= 0 || d > PER_MAX_DIM) return "need 0 < d <= plmc_per_max_dim()";
-    } else if (family == COV_RQ) {
-      if (d <= 0 || d > RQ_MAX_DIM) return "need 0 < d <= plmc_rq_max_dim()";
-    } else if (family == COV_LPER) {
-      if (d <= 0 || d > LPER_MAX_DIM) return "need 0 < d <= plmc_lper_max_dim()";
-      if (!third) return "null pointer";
-    } else if (family == COV_DOT) {
-      if (d <= 0 || d > DOT_MAX_DIM) return "need 0 < d <= plmc_dot_max_dim()";
-      if (ncomp < 1 || ncomp > DOT_MAX_POWER) return "need 1 <= power <= plmc_dot_max_power()";
-    }
-    return (family == COV_SM || family == COV_PER || family == COV_RQ || family == COV_LPER || family == COV_DOT) && !second ? "null pointer" : nullptr;
+    return (f.needs_third && !third) || (f.needs_second && !second) ? "null pointer" : nullptr;
   }
   // the family whose kernels run: an additive table of one component IS the plain kernel (ell (q, 1, d) is ell (q, d)) and takes the
   // plain instantiations, bit for bit
   CovFamily route() const { return family == COV_ADD && ncomp == 1 ? COV_PLAIN : family; }
   // rows of GP partial-sum slots per tile that the K^-1 + gradient kernels write (potri_grad.hip)
-  int partials_rows() const { return family == COV_ADD || family == COV_SM || family == COV_SUM ? ncomp : 1; }
+  int partials_rows() const { return FAMILY[family].rows_per_comp ? ncomp : 1; }
+  // what the gradient kernels get as `kind`: a sum's carries its members
+  int kernel_kind() const { return family == COV_SUM ? fams : kind; }
+  // FamilyTraits::vd_noun of the call: the one member of a sum keeps scratch behind the partial sums (of_sum), so it follows the sum
+  const char *vd_noun() const { return FAMILY[of_sum ? COV_SUM : route()].vd_noun; }
 };
 #define PLMC_REQUIRE_TABLE(t) \
   do { if (const char *why_ = (t).check()) return plmc::fail(__func__, why_); } while (0)
+
+// The ONE list of the families' extern "C" entry points (include/plmc.h declares them by hand; every .hip file includes it, so the compiler
+// holds each generated wrapper against its declaration).  X(SUF, T, infix, LEAD, (flat table arguments), table): the entry points of a
+// family are plmc_<operation><infix>..._<SUF>, their first argument is `int kind` where LEAD is KIND, and where the plain entry point has
+// `int d, const T *ell, const T *oscale` they have `int d` and the flat table arguments, from which `table` builds the CovTable.  Each
+// operation defines its wrappers for both element types with one body:
+//   PLMC_FAMILY_ENTRIES(MY_ENTRY, f32, float) PLMC_FAMILY_ENTRIES(MY_ENTRY, f64, double)
+// (`shape` is the rational-quadratic alpha: `alpha` is K^-1 y in the gradient entry points.)
+#define PLMC_LEAD_KIND int kind,
+#define PLMC_LEAD_NO_KIND
+#define PLMC_UNPACK(...) __VA_ARGS__
+#define PLMC_FAMILY_ENTRIES(X, SUF, T)                                                                                                        \
+  X(SUF, T, , KIND, (const T *ell, const T *oscale), plmc::CovTable::plain(kind, d, ell, oscale))                                             \
+  X(SUF, T, _add, KIND, (int ncomp, const T *ell, const T *oscale), plmc::CovTable::add(kind, d, ncomp, ell, oscale))                         \
+  X(SUF, T, _sm, NO_KIND, (int nmix, const T *scales, const T *means, const T *weights), plmc::CovTable::sm(d, nmix, scales, means, weights)) \
+  X(SUF, T, _per, NO_KIND, (const T *ell, const T *period, const T *oscale), plmc::CovTable::per(d, ell, period, oscale))                     \
+  X(SUF, T, _rq, NO_KIND, (const T *ell, const T *shape, const T *oscale), plmc::CovTable::rq(d, ell, shape, oscale))                         \
+  X(SUF, T, _lper, NO_KIND, (const T *ell, const T *period, const T *rbf_ell, const T *oscale),                                               \
+    plmc::CovTable::lper(d, ell, period, rbf_ell, oscale))                                                                                    \
+  X(SUF, T, _sum, NO_KIND, (int ncomp, const int *fam, const T *table, const T *oscale), plmc::CovTable::sum(d, ncomp, fam, table, oscale))   \
+  X(SUF, T, _dot, NO_KIND, (const T *var, const T *offset, int power, const T *oscale), plmc::CovTable::dot(d, power, var, offset, oscale))
 
 // Covariance assembly handed to the sweep (plmc_factorize*_ex_*): the sweep queues the rows of its first group on the caller's stream and
 // the rest on a helper stream beside the first group's chain, instead of the caller assembling the whole matrix in front of the sweep.

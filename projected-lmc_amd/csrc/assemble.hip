@@ -760,16 +760,18 @@ template <typename T, int DC, template <typename, int> class P, class... Args>
 void launch_cross_table(dim3 grid, hipStream_t st, const P<T, DC> &prm, Args... args) {
   hipLaunchKernelGGL((k_assemble_cross_table<T, DC, P<T, DC>>), grid, dim3(NTHREADS), 0, st, prm, args...);
 }
-// the device-side tables of a descriptor
-template <typename T, int DC> AddTable<T, DC> add_table(const CovTable &t) { return {t.kind, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
-template <typename T, int DC> SmTable<T, DC> sm_table(const CovTable &t) { return {t.ncomp, (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
-template <typename T, int DC> PerTable<T, DC> per_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
-template <typename T, int DC> RqTable<T, DC> rq_table(const CovTable &t) { return {(const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
-template <typename T, int DC> LperTable<T, DC> lper_table(const CovTable &t) {
-  return {(const T *)t.ell, (const T *)t.second, (const T *)t.third, (const T *)t.oscale};
+// the device-side table of family F from a descriptor
+template <typename T, CovFamily F, int DC>
+auto device_table(const CovTable &t) {
+  const T *ell = (const T *)t.ell, *second = (const T *)t.second, *oscale = (const T *)t.oscale;
+  if constexpr (F == COV_ADD) return AddTable<T, DC>{t.kind, t.ncomp, ell, oscale};
+  else if constexpr (F == COV_SM) return SmTable<T, DC>{t.ncomp, ell, second, oscale};
+  else if constexpr (F == COV_PER) return PerTable<T, DC>{ell, second, oscale};
+  else if constexpr (F == COV_RQ) return RqTable<T, DC>{ell, second, oscale};
+  else if constexpr (F == COV_LPER) return LperTable<T, DC>{ell, second, (const T *)t.third, oscale};
+  else if constexpr (F == COV_SUM) return SumTable<T, DC>{t.fams, t.ncomp, ell, oscale};
+  else if constexpr (F == COV_DOT) return DotTable<T, DC>{t.power(), ell, second, oscale};
 }
-template <typename T, int DC> DotTable<T, DC> dot_table(const CovTable &t) { return {t.power(), (const T *)t.ell, (const T *)t.second, (const T *)t.oscale}; }
-template <typename T, int DC> SumTable<T, DC> sum_table(const CovTable &t) { return {t.fams, t.ncomp, (const T *)t.ell, (const T *)t.oscale}; }
 
 // block rows ib0 .. ib0 + nrows - 1 (nrows < 0: all of them); the tiles right of the diagonal of those rows, the first `ncols` block
 // columns only (ncols < 0: all), without the leading skip x skip block triangle
@@ -787,8 +789,7 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
   }
   const int kind = t.kind, d = t.d;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale;
-  const bool small_only = t.family == COV_SM || t.family == COV_PER || t.family == COV_RQ || t.family == COV_LPER || t.family == COV_SUM ||
-                          t.family == COV_DOT;   // d <= 8 (rational quadratic, dot product: 16) by the family's limit
+  const bool small_only = FAMILY[t.family].max_dim != 0;   // d <= 8 (rational quadratic, dot product: 16) by the family's limit
   PLMC_REQUIRE(kind >= 0 && kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(X && ell && noise && A, "null pointer");
   PLMC_REQUIRE(n > 0 && q > 0 && d > 0 && d <= MAX_DIM, small_only ? "need n>0, q>0" : "need n>0, q>0, 0<d<=plmc_max_dim()");
@@ -816,44 +817,14 @@ int assemble_impl(const CovTable &t, const T *X, int n, const T *noise, T *A, in
                            strideA, ib0, skip);
       break;
     case COV_ADD:
-      if (d <= 4) table(add_table<T, 4>(t));
-      else if (d <= 8) table(add_table<T, 8>(t));
+      if (d <= 4) table(device_table<T, COV_ADD, 4>(t));
+      else if (d <= 8) table(device_table<T, COV_ADD, 8>(t));
       else
         hipLaunchKernelGGL(k_assemble_add<T>, grid, dim3(NTHREADS), (2 * NB * (d + 1) + t.ncomp * d + t.ncomp) * sizeof(T), st, kind, X, n, d,
                            t.ncomp, ell, oscale, noise, A, lda, strideA, ib0, skip);
       break;
-    case COV_SM:
-      if (d == 1) table(sm_table<T, 1>(t));
-      else if (d <= 4) table(sm_table<T, 4>(t));
-      else table(sm_table<T, 8>(t));
-      break;
-    case COV_PER:
-      if (d == 1) table(per_table<T, 1>(t));
-      else if (d <= 4) table(per_table<T, 4>(t));
-      else table(per_table<T, 8>(t));
-      break;
-    case COV_RQ:
-      if (d == 1) table(rq_table<T, 1>(t));
-      else if (d <= 4) table(rq_table<T, 4>(t));
-      else if (d <= 8) table(rq_table<T, 8>(t));
-      else table(rq_table<T, 16>(t));
-      break;
-    case COV_LPER:
-      if (d == 1) table(lper_table<T, 1>(t));
-      else if (d <= 4) table(lper_table<T, 4>(t));
-      else table(lper_table<T, 8>(t));
-      break;
-    case COV_SUM:
-      if (d == 1) table(sum_table<T, 1>(t));
-      else if (d <= 4) table(sum_table<T, 4>(t));
-      else table(sum_table<T, 8>(t));
-      break;
-    case COV_DOT:
-      if (d == 1) table(dot_table<T, 1>(t));
-      else if (d <= 4) table(dot_table<T, 4>(t));
-      else if (d <= 8) table(dot_table<T, 8>(t));
-      else table(dot_table<T, 16>(t));
-      break;
+    default:
+      with_capacity<0>(t.family, d, [&](auto f, auto dc) { table(device_table<T, decltype(f)::value, decltype(dc)::value>(t)); });
   }
   return launch_status(__func__);
 }
@@ -908,43 +879,13 @@ int assemble_cross_impl(const CovTable &t, const T *X, int n, const T *Xs, int n
       else plain(std::integral_constant<int, 32>());
       break;
     case COV_ADD:
-      if (d <= 4) table(add_table<T, 4>(t));
-      else if (d <= 8) table(add_table<T, 8>(t));
-      else if (d <= 16) table(add_table<T, 16>(t));
-      else table(add_table<T, 32>(t));
+      if (d <= 4) table(device_table<T, COV_ADD, 4>(t));
+      else if (d <= 8) table(device_table<T, COV_ADD, 8>(t));
+      else if (d <= 16) table(device_table<T, COV_ADD, 16>(t));
+      else table(device_table<T, COV_ADD, 32>(t));
       break;
-    case COV_SM:
-      if (d == 1) table(sm_table<T, 1>(t));
-      else if (d <= 4) table(sm_table<T, 4>(t));
-      else table(sm_table<T, 8>(t));
-      break;
-    case COV_PER:
-      if (d == 1) table(per_table<T, 1>(t));
-      else if (d <= 4) table(per_table<T, 4>(t));
-      else table(per_table<T, 8>(t));
-      break;
-    case COV_RQ:
-      if (d == 1) table(rq_table<T, 1>(t));
-      else if (d <= 4) table(rq_table<T, 4>(t));
-      else if (d <= 8) table(rq_table<T, 8>(t));
-      else table(rq_table<T, 16>(t));
-      break;
-    case COV_LPER:
-      if (d == 1) table(lper_table<T, 1>(t));
-      else if (d <= 4) table(lper_table<T, 4>(t));
-      else table(lper_table<T, 8>(t));
-      break;
-    case COV_SUM:
-      if (d == 1) table(sum_table<T, 1>(t));
-      else if (d <= 4) table(sum_table<T, 4>(t));
-      else table(sum_table<T, 8>(t));
-      break;
-    case COV_DOT:
-      if (d == 1) table(dot_table<T, 1>(t));
-      else if (d <= 4) table(dot_table<T, 4>(t));
-      else if (d <= 8) table(dot_table<T, 8>(t));
-      else table(dot_table<T, 16>(t));
-      break;
+    default:
+      with_capacity<0>(t.family, d, [&](auto f, auto dc) { table(device_table<T, decltype(f)::value, decltype(dc)::value>(t)); });
   }
   return launch_status(__func__);
 }
@@ -959,17 +900,8 @@ int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, 
 }
 }  // namespace plmc
 
-// the only place the covariance tables of this file are built from flat arguments
+// the entry points of the families (api_common.hpp, PLMC_FAMILY_ENTRIES): the only place the covariance tables of this file are built
 extern "C" {
-using plmc::CovTable;
-int plmc_assemble_f32(int kind, const float *X, int n, int d, const float *ell, const float *oscale,
-                      const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<float>(CovTable::plain(kind, d, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale,
-                      const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<double>(CovTable::plain(kind, d, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
 int plmc_write_rhs_f32(const float *rhs, int nrhs, int n, float *A, int64_t lda, int64_t strideA, int c0,
                        int clear_cols, int q, void *stream) {
   return plmc::write_rhs_impl<float>(rhs, nrhs, n, A, lda, strideA, c0, clear_cols, q, stream);
@@ -978,129 +910,26 @@ int plmc_write_rhs_f64(const double *rhs, int nrhs, int n, double *A, int64_t ld
                        int clear_cols, int q, void *stream) {
   return plmc::write_rhs_impl<double>(rhs, nrhs, n, A, lda, strideA, c0, clear_cols, q, stream);
 }
-int plmc_assemble_cross_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, const float *ell,
-                            const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
-                            int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<float>(CovTable::plain(kind, d, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
-int plmc_assemble_cross_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, const double *ell,
-                            const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
-                            int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<double>(CovTable::plain(kind, d, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
+#define PLMC_ASSEMBLE_ENTRY(SUF, T, INFIX, LEAD, PARAMS, TABLE)                                                                               \
+  int plmc_assemble##INFIX##_##SUF(PLMC_LEAD_##LEAD const T *X, int n, int d, PLMC_UNPACK PARAMS, const T *noise, T *A, int64_t lda,          \
+                                   int64_t strideA, int q, void *stream) {                                                                    \
+    return plmc::assemble_impl<T>(TABLE, X, n, noise, A, lda, strideA, q, stream);                                                            \
+  }                                                                                                                                           \
+  int plmc_assemble_cross##INFIX##_##SUF(PLMC_LEAD_##LEAD const T *X, int n, const T *Xs, int ns, int d, PLMC_UNPACK PARAMS, T *Out,          \
+                                         int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                   \
+    return plmc::assemble_cross_impl<T>(TABLE, X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);                                     \
+  }
+PLMC_FAMILY_ENTRIES(PLMC_ASSEMBLE_ENTRY, f32, float)
+PLMC_FAMILY_ENTRIES(PLMC_ASSEMBLE_ENTRY, f64, double)
+#undef PLMC_ASSEMBLE_ENTRY
 int plmc_max_components(void) { return plmc::MAX_COMP; }
 int plmc_sm_max_mixtures(void) { return plmc::SM_MAX_MIX; }
 int plmc_sm_max_dim(void) { return plmc::SM_MAX_DIM; }
-int plmc_assemble_sm_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
-                         const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<float>(CovTable::sm(d, nmix, scales, means, weights), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_sm_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
-                         const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<double>(CovTable::sm(d, nmix, scales, means, weights), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_cross_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means,
-                               const float *weights, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
-                               void *stream) {
-  return plmc::assemble_cross_impl<float>(CovTable::sm(d, nmix, scales, means, weights), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
-int plmc_assemble_cross_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means,
-                               const double *weights, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
-                               void *stream) {
-  return plmc::assemble_cross_impl<double>(CovTable::sm(d, nmix, scales, means, weights), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
 int plmc_per_max_dim(void) { return plmc::PER_MAX_DIM; }
-int plmc_assemble_per_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
-                          float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<float>(CovTable::per(d, ell, period, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_per_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
-                          double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<double>(CovTable::per(d, ell, period, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_cross_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period,
-                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
-                                void *stream) {
-  return plmc::assemble_cross_impl<float>(CovTable::per(d, ell, period, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
-int plmc_assemble_cross_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
-                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,
-                                void *stream) {
-  return plmc::assemble_cross_impl<double>(CovTable::per(d, ell, period, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
 int plmc_rq_max_dim(void) { return plmc::RQ_MAX_DIM; }
-#define PLMC_RQ_ENTRY(SUF, T)                                                                                                                  \
-  int plmc_assemble_rq_##SUF(const T *X, int n, int d, const T *ell, const T *alpha, const T *oscale, const T *noise, T *A, int64_t lda,       \
-                             int64_t strideA, int q, void *stream) {                                                                           \
-    return plmc::assemble_impl<T>(CovTable::rq(d, ell, alpha, oscale), X, n, noise, A, lda, strideA, q, stream);                               \
-  }                                                                                                                                            \
-  int plmc_assemble_cross_rq_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *alpha, const T *oscale, T *Out,       \
-                                   int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                          \
-    return plmc::assemble_cross_impl<T>(CovTable::rq(d, ell, alpha, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);        \
-  }
-PLMC_RQ_ENTRY(f32, float)
-PLMC_RQ_ENTRY(f64, double)
-#undef PLMC_RQ_ENTRY
 int plmc_dot_max_dim(void) { return plmc::DOT_MAX_DIM; }
 int plmc_dot_max_power(void) { return plmc::DOT_MAX_POWER; }
-#define PLMC_DOT_ENTRY(SUF, T)                                                                                                                 \
-  int plmc_assemble_dot_##SUF(const T *X, int n, int d, const T *var, const T *offset, int power, const T *oscale, const T *noise, T *A,       \
-                              int64_t lda, int64_t strideA, int q, void *stream) {                                                             \
-    return plmc::assemble_impl<T>(CovTable::dot(d, power, var, offset, oscale), X, n, noise, A, lda, strideA, q, stream);                      \
-  }                                                                                                                                            \
-  int plmc_assemble_cross_dot_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *var, const T *offset, int power, const T *oscale,  \
-                                    T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                 \
-    return plmc::assemble_cross_impl<T>(CovTable::dot(d, power, var, offset, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q,        \
-                                        stream);                                                                                               \
-  }
-PLMC_DOT_ENTRY(f32, float)
-PLMC_DOT_ENTRY(f64, double)
-#undef PLMC_DOT_ENTRY
 int plmc_lper_max_dim(void) { return plmc::LPER_MAX_DIM; }
-#define PLMC_LPER_ENTRY(SUF, T)                                                                                                                \
-  int plmc_assemble_lper_##SUF(const T *X, int n, int d, const T *ell, const T *period, const T *rbf_ell, const T *oscale, const T *noise,     \
-                               T *A, int64_t lda, int64_t strideA, int q, void *stream) {                                                      \
-    return plmc::assemble_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), X, n, noise, A, lda, strideA, q, stream);                   \
-  }                                                                                                                                            \
-  int plmc_assemble_cross_lper_##SUF(const T *X, int n, const T *Xs, int ns, int d, const T *ell, const T *period, const T *rbf_ell,           \
-                                     const T *oscale, T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q,               \
-                                     void *stream) {                                                                                           \
-    return plmc::assemble_cross_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q,     \
-                                        stream);                                                                                               \
-  }
-PLMC_LPER_ENTRY(f32, float)
-PLMC_LPER_ENTRY(f64, double)
-#undef PLMC_LPER_ENTRY
 int plmc_sum_max_components(void) { return plmc::MAX_COMP; }
 int plmc_sum_max_dim(void) { return plmc::SUM_MAX_DIM; }
-#define PLMC_SUM_ENTRY(SUF, T)                                                                                                                 \
-  int plmc_assemble_sum_##SUF(const T *X, int n, int d, int ncomp, const int *fam, const T *table, const T *oscale, const T *noise, T *A,      \
-                              int64_t lda, int64_t strideA, int q, void *stream) {                                                             \
-    return plmc::assemble_impl<T>(CovTable::sum(d, ncomp, fam, table, oscale), X, n, noise, A, lda, strideA, q, stream);                       \
-  }                                                                                                                                            \
-  int plmc_assemble_cross_sum_##SUF(const T *X, int n, const T *Xs, int ns, int d, int ncomp, const int *fam, const T *table, const T *oscale, \
-                                    T *Out, int64_t ldo, int64_t strideO, int64_t col0, int64_t n_rows, int q, void *stream) {                 \
-    return plmc::assemble_cross_impl<T>(CovTable::sum(d, ncomp, fam, table, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream); \
-  }
-PLMC_SUM_ENTRY(f32, float)
-PLMC_SUM_ENTRY(f64, double)
-#undef PLMC_SUM_ENTRY
-int plmc_assemble_add_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale,
-                          const float *noise, float *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_add_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale,
-                          const double *noise, double *A, int64_t lda, int64_t strideA, int q, void *stream) {
-  return plmc::assemble_impl<double>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, noise, A, lda, strideA, q, stream);
-}
-int plmc_assemble_cross_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell,
-                                const float *oscale, float *Out, int64_t ldo, int64_t strideO, int64_t col0,
-                                int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<float>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
-int plmc_assemble_cross_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell,
-                                const double *oscale, double *Out, int64_t ldo, int64_t strideO, int64_t col0,
-                                int64_t n_rows, int q, void *stream) {
-  return plmc::assemble_cross_impl<double>(CovTable::add(kind, d, ncomp, ell, oscale), X, n, Xs, ns, Out, ldo, strideO, col0, n_rows, q, stream);
-}
 }

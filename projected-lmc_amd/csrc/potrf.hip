@@ -1480,16 +1480,6 @@ int w_diag_impl(const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, T *kinv
 
 }  // namespace plmc
 
-extern "C" {
-// Vd blocks per latent (vd_layout.hpp): for 4-byte elements the plane buffers of the split engine are counted whether or not
-// PLMC_SPLIT is on, so that a workspace never depends on a knob (ADVICE r2).
-int64_t plmc_vd_blocks_for(int64_t n_pad, int64_t lda, int elem_bytes) { return plmc::VdLayout(n_pad, lda, elem_bytes, false).blocks; }
-int64_t plmc_vd_blocks(int64_t n_pad, int64_t lda) { return plmc_vd_blocks_for(n_pad, lda, 4); }
-// ... when the sweep keeps the planes of every group's solved rows (with_inverse | 4, fp32): one 128 GMAX-row plane buffer per
-// group instead of the two rolling ones
-int64_t plmc_vd_blocks_keep(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, true).blocks; }
-// where potrf_impl / potrs_aug_kept put the scale block (4-byte elements), in floats
-int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, false).scl * plmc::NB * plmc::NB; }
 // PLMC_SPLIT picks the arithmetic of the bulk fp32 products: 0 = fp32 MFMA everywhere, 3 = SplitB3, 2 (default) = SplitH2
 // where the caller supplies eigenvalue bounds (plmc_potrf_ex_f32), SplitB3 otherwise.
 static int potrf_f32_any(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
@@ -1500,151 +1490,40 @@ static int potrf_f32_any(float *A, int64_t n_pad, int64_t lda, int naug, int64_t
     return plmc::potrf_impl<float, plmc::SplitH2>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, job);
   return plmc::potrf_impl<float, plmc::SplitB3>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, job);
 }
+// ... of either element type: fp64 has one arithmetic and does not look at eig_lo
+template <typename T>
+static int potrf_any(T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *Vd, double *logdet, int *info, int with_inverse, int q,
+                     const T *eig_lo, void *stream, const plmc::AssembleJob *job = nullptr) {
+  if constexpr (sizeof(T) == 4) return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, job);
+  else return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, job);
+}
+
+extern "C" {
+// Vd blocks per latent (vd_layout.hpp): for 4-byte elements the plane buffers of the split engine are counted whether or not
+// PLMC_SPLIT is on, so that a workspace never depends on a knob (ADVICE r2).
+int64_t plmc_vd_blocks_for(int64_t n_pad, int64_t lda, int elem_bytes) { return plmc::VdLayout(n_pad, lda, elem_bytes, false).blocks; }
+int64_t plmc_vd_blocks(int64_t n_pad, int64_t lda) { return plmc_vd_blocks_for(n_pad, lda, 4); }
+// ... when the sweep keeps the planes of every group's solved rows (with_inverse | 4, fp32): one 128 GMAX-row plane buffer per
+// group instead of the two rolling ones
+int64_t plmc_vd_blocks_keep(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, true).blocks; }
+// where potrf_impl / potrs_aug_kept put the scale block (4-byte elements), in floats
+int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) { return plmc::VdLayout(n_pad, lda, 4, false).scl * plmc::NB * plmc::NB; }
 // plmc_assemble_* + plmc_potrf_ex_* in one call (the augmented columns are written by the caller BEFORE it: plmc_write_rhs_*,
 // plmc_assemble_cross_*): the sweep writes the rows of its first group of block rows itself and queues the others beside that
-// group's chain.  Same kernels on the same data as the two calls: bit-identical results.
-int plmc_factorize_ex_f32(int kind, const float *X, int n, int d, const float *ell, const float *oscale, const float *noise, float *A,
-                          int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q,
-                          const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::plain(kind, d, ell, oscale), n, X, noise};
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_ex_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale, const double *noise, double *A,
-                          int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info, int with_inverse, int q,
-                          const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::plain(kind, d, ell, oscale), n, X, noise};
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for an additive kernel (plmc_assemble_add_*): the job carries the table, the sweep does not look at it
-int plmc_factorize_add_ex_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, const float *noise,
-                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
-                              int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::add(kind, d, ncomp, ell, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_add_ex_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, const double *noise,
-                              double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
-                              int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::add(kind, d, ncomp, ell, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a spectral-mixture kernel (plmc_assemble_sm_*): the job carries the table
-int plmc_factorize_sm_ex_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
-                             const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
-                             int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::sm(d, nmix, scales, means, weights), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_sm_ex_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
-                             const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
-                             int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::sm(d, nmix, scales, means, weights), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a periodic kernel (plmc_assemble_per_*): the job carries the lengthscales and the periods
-int plmc_factorize_per_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
-                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
-                              int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::per(d, ell, period, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_per_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
-                              double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
-                              int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::per(d, ell, period, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a rational-quadratic kernel (plmc_assemble_rq_*): the job carries the lengthscales and alpha
-int plmc_factorize_rq_ex_f32(const float *X, int n, int d, const float *ell, const float *alpha, const float *oscale, const float *noise,
-                             float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
-                             int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::rq(d, ell, alpha, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_rq_ex_f64(const double *X, int n, int d, const double *ell, const double *alpha, const double *oscale, const double *noise,
-                             double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info,
-                             int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::rq(d, ell, alpha, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a dot-product kernel (plmc_assemble_dot_*): the job carries the variances, the offset and the power
-int plmc_factorize_dot_ex_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale,
-                              const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
-                              int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::dot(d, power, var, offset, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_dot_ex_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
-                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
-                              int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::dot(d, power, var, offset, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a locally periodic kernel (plmc_assemble_lper_*): the job carries the periodic lengthscales, the periods and the RBF
-// lengthscales
-int plmc_factorize_lper_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
-                               const float *noise, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
-                               int *info, int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::lper(d, ell, period, rbf_ell, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_lper_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *rbf_ell, const double *oscale,
-                               const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
-                               int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::lper(d, ell, period, rbf_ell, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
-// The same for a heterogeneous sum (plmc_assemble_sum_*): the job carries the table and the members read from the host array `fam`
-int plmc_factorize_sum_ex_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, const float *noise,
-                              float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet, int *info,
-                              int with_inverse, int q, const float *eig_lo, void *stream) {
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::sum(d, ncomp, fam, table, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);
-}
-int plmc_factorize_sum_ex_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
-                              const double *noise, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet,
-                              int *info, int with_inverse, int q, const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");
-  const plmc::AssembleJob job{plmc::CovTable::sum(d, ncomp, fam, table, oscale), n, X, noise};
-  PLMC_REQUIRE_TABLE(job.table);
-  return plmc::potrf_impl<double, void>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream, &job);
-}
+// group's chain.  Same kernels on the same data as the two calls: bit-identical results.  One entry point per family (api_common.hpp,
+// PLMC_FAMILY_ENTRIES): the job carries the table, the sweep does not look at it.
+#define PLMC_FACTORIZE_ENTRY(SUF, T, INFIX, LEAD, PARAMS, TABLE)                                                                              \
+  int plmc_factorize##INFIX##_ex_##SUF(PLMC_LEAD_##LEAD const T *X, int n, int d, PLMC_UNPACK PARAMS, const T *noise, T *A, int64_t n_pad,    \
+                                       int64_t lda, int naug, int64_t strideA, T *Vd, double *logdet, int *info, int with_inverse, int q,    \
+                                       const T *eig_lo, void *stream) {                                                                       \
+    PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");                                                                          \
+    const plmc::AssembleJob job{TABLE, n, X, noise};                                                                                          \
+    PLMC_REQUIRE_TABLE(job.table);                                                                                                            \
+    return potrf_any<T>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);                               \
+  }
+PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_ENTRY, f32, float)
+PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_ENTRY, f64, double)
+#undef PLMC_FACTORIZE_ENTRY
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

@@ -264,7 +264,7 @@ __device__ __forceinline__ void kinv_tile_epilogue_add(const Acc<T> &acc, T *sme
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_DOT || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
+__global__ __launch_bounds__(NTHREADS, (table_min_waves<T, F, DC>())) void k_kinv_grad_add(int kind, int ncomp, const T *__restrict__ W, int64_t n_pad, int64_t ldw,
                                                                 int64_t strideW, const T *__restrict__ alpha, const T *__restrict__ X, int n, int d,
                                                                 const T *__restrict__ ell, const T *__restrict__ oscale, T *Kinv, int64_t ldk,
                                                                 int64_t strideK, T *kinv_diag, double *__restrict__ partials, int nlat,
@@ -510,6 +510,28 @@ __global__ void k_w_scale(const float *__restrict__ eig_lo, float *__restrict__ 
   }
 }
 
+// The family's reduction of the per-tile partial sums (`part`: table.partials_rows() rows of GP slots per tile) into its gradient table
+template <typename T>
+void launch_reduce_grad(const CovTable &table, const double *part, int m, int q, double *grad, hipStream_t st) {
+  const int d = table.d, ncomp = table.ncomp;
+  const T *ell = (const T *)table.ell, *second = (const T *)table.second, *third = (const T *)table.third;
+  ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * table.partials_rows() * GP * sizeof(double) / 2);
+  switch (table.route()) {
+    case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
+    case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
+    case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
+    case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
+    case COV_DOT: hipLaunchKernelGGL(k_reduce_grad_dot, dim3(q), dim3(RED_NT), 0, st, part, m, d, grad); break;
+    case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+    case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
+    case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
+  }
+}
+
+// `call(member table, its gradient table, check_only)` runs the member family's gradient path, or its argument checks alone (below)
+template <typename T, class Call>
+int sum_single_member(const CovTable &t, int64_t n_pad, int q, double *grad, void *partials, void *stream, Call call);
+
 // S: split scheme of the W^T W products (void: MFMA of the element type); eig_lo: see potrf_impl.
 // `partials` is table.partials_rows() rows of GP slots per tile and `grad` as wide as the family's reduction kernel writes it.
 // check_only: return after the argument checks, before the first launch (sum_single_member).
@@ -519,7 +541,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
                    const float *Vd = nullptr, int64_t lda_vd = 0, bool check_only = false) {
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
-  const int kind = table.family == COV_SUM ? table.fams : table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();   // (SUM: the kernels' `kind` carries the members)
+  const int kind = table.kernel_kind(), d = table.d, ncomp = table.ncomp, rows = table.partials_rows();
   const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
   PLMC_REQUIRE(table.kind >= 0 && table.kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(W && alpha && X && ell && grad && partials, "null pointer");
@@ -541,14 +563,13 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
     const float *wsc = nullptr;
     int64_t wp_lat = b3_elems<S>(n_pad, n_pad), ws_lat = 1;
     const bool from_vd = Vd && vd_w_planes(Vd, n_pad, lda_vd, &wp, &wp_lat, &wsc, &ws_lat);
-    if (!from_vd)
-      PLMC_REQUIRE(family != COV_PER && family != COV_SM && family != COV_RQ && family != COV_LPER && family != COV_SUM && family != COV_DOT && !table.of_sum,
-                   family == COV_SUM || table.of_sum ? "the sum gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                   : family == COV_PER  ? "the periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                   : family == COV_LPER ? "the locally periodic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                   : family == COV_DOT ? "the dot-product gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                   : family == COV_RQ ? "the rational-quadratic gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)"
-                                      : "the spectral-mixture gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)");
+    if (!from_vd) {
+      if (const char *noun = table.vd_noun()) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "the %s gradient call takes the planes of W from the sweep's Vd (factorise with the inverse factor)", noun);
+        return fail(__func__, msg);
+      }
+    }
     if (check_only) return 0;
     if (!from_vd) {
       char *pb = reinterpret_cast<char *>(partials) + (int64_t)m * m * q * rows * GP * (int64_t)sizeof(double);
@@ -571,25 +592,10 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
   hipLaunchKernelGGL((k_kinv_grad_add_bf3<S, F, DC>), gridb, dim3(B3_NT), 0, st, kind, ncomp, n_pad, alpha, X, n, d, ell, oscale, Kinv, ldk, strideK, \
                      kinv_diag, part, q, wp, wsc, wp_lat, ws_lat, (const float *)second, (const float *)third)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
-    switch (family) {
-      case COV_PER: PLMC_LAUNCH_TB(COV_PER, 1); break;     // (d = 1 only: kinv_grad_f32_any)
-      case COV_LPER: PLMC_LAUNCH_TB(COV_LPER, 1); break;   // (d = 1 only: kinv_grad_f32_any)
-      case COV_SUM: PLMC_LAUNCH_TB(COV_SUM, 1); break;     // (d = 1 only: kinv_grad_f32_any)
-      case COV_RQ:                                         // (three planes: d = 1 only, kinv_grad_f32_any -- DC = 4 / 8 would spill there)
-        if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_RQ, 1);
-        else if (d == 1) PLMC_LAUNCH_TB(COV_RQ, 1);
-        else if (d <= 4) PLMC_LAUNCH_TB(COV_RQ, 4);
-        else if (d <= 8) PLMC_LAUNCH_TB(COV_RQ, 8);
-        else PLMC_LAUNCH_TB(COV_RQ, 16);
+    switch (family) {                                      // (table families first, here and below: the order of the kernels in the code object)
+      default:                                             // beside the planes: DC = 1 only, except RQ / DOT beside two (FamilyTraits::split_max_d)
+        with_capacity<S::NPL>(family, d, [&](auto f, auto dc) { PLMC_LAUNCH_TB(decltype(f)::value, decltype(dc)::value); });
         break;
-      case COV_DOT:                                        // (three planes: d = 1 only, as COV_RQ)
-        if constexpr (S::NPL == 3) PLMC_LAUNCH_TB(COV_DOT, 1);
-        else if (d == 1) PLMC_LAUNCH_TB(COV_DOT, 1);
-        else if (d <= 4) PLMC_LAUNCH_TB(COV_DOT, 4);
-        else if (d <= 8) PLMC_LAUNCH_TB(COV_DOT, 8);
-        else PLMC_LAUNCH_TB(COV_DOT, 16);
-        break;
-      case COV_SM: PLMC_LAUNCH_TB(COV_SM, 1); break;       // (d = 1 only: kinv_grad_f32_any)
       case COV_ADD: PLMC_LAUNCH_TB(COV_ADD, 0); break;
       case COV_PLAIN:
         if (d <= 4) PLMC_LAUNCH_KB(4, false);
@@ -610,12 +616,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
                      strideK, kinv_diag, part, q, second, third)
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * np / 3.0, q * (np * np / 2) * sizeof(T));
     switch (family) {
-      case COV_PER: if (d == 1) PLMC_LAUNCH_TG(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_PER, 4); else PLMC_LAUNCH_TG(COV_PER, 8); break;
-      case COV_LPER: if (d == 1) PLMC_LAUNCH_TG(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_LPER, 4); else PLMC_LAUNCH_TG(COV_LPER, 8); break;
-      case COV_SUM: if (d == 1) PLMC_LAUNCH_TG(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SUM, 4); else PLMC_LAUNCH_TG(COV_SUM, 8); break;
-      case COV_RQ: if (d == 1) PLMC_LAUNCH_TG(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_RQ, 8); else PLMC_LAUNCH_TG(COV_RQ, 16); break;
-      case COV_DOT: if (d == 1) PLMC_LAUNCH_TG(COV_DOT, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_DOT, 4); else if (d <= 8) PLMC_LAUNCH_TG(COV_DOT, 8); else PLMC_LAUNCH_TG(COV_DOT, 16); break;
-      case COV_SM: if (d == 1) PLMC_LAUNCH_TG(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_TG(COV_SM, 4); else PLMC_LAUNCH_TG(COV_SM, 8); break;
+      default: with_capacity<0>(family, d, [&](auto f, auto dc) { PLMC_LAUNCH_TG(decltype(f)::value, decltype(dc)::value); }); break;
       case COV_ADD: PLMC_LAUNCH_TG(COV_ADD, 0); break;
       case COV_PLAIN:
         if (d <= 4) PLMC_LAUNCH_KG(4, false);
@@ -626,19 +627,7 @@ int kinv_grad_impl(const CovTable &table, const T *W, int64_t n_pad, int64_t ldw
 #undef PLMC_LAUNCH_TG
 #undef PLMC_LAUNCH_KG
   }
-  {
-    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
-    switch (family) {
-      case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
-      case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
-      case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
-      case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
-      case COV_DOT: hipLaunchKernelGGL(k_reduce_grad_dot, dim3(q), dim3(RED_NT), 0, st, part, m, d, grad); break;
-      case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
-      case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
-      case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
-    }
-  }
+  launch_reduce_grad<T>(table, part, m, q, grad, st);
   return launch_status(__func__);
 }
 
@@ -682,7 +671,7 @@ __global__ __launch_bounds__(NTHREADS, (LOO_MIN_WAVES<T, DCAP>)) void k_loo_grad
 }
 
 template <typename T, CovFamily F, int DC = 0>
-__global__ __launch_bounds__(NTHREADS, ((sizeof(T) == 8 && (F == COV_SM || F == COV_RQ || F == COV_DOT || F == COV_SUM || ((F == COV_PER || F == COV_LPER) && DC > 1))) || (F == COV_SUM && DC > 4) ? 1 : 2)) void k_loo_grad_add(
+__global__ __launch_bounds__(NTHREADS, (table_min_waves<T, F, DC>())) void k_loo_grad_add(
     int kind, int ncomp, const T *__restrict__ Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *__restrict__ beta,
     const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
     const T *__restrict__ means, const T *__restrict__ third) {
@@ -746,9 +735,13 @@ __global__ __launch_bounds__(NTHREADS) void k_loo_operand(const T *__restrict__ 
 template <typename T>
 int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,
                   double *grad, void *partials, int q, void *stream, bool check_only = false) {
+  if (table.single_member())          // a sum of one member IS that member: its family's own path
+    return sum_single_member<T>(table, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check) {
+      return loo_grad_impl<T>(mt, Xop, n_pad, krows, ldx, strideX, beta, X, n, fg, partials, q, stream, check);
+    });
   PLMC_REQUIRE_TABLE(table);
   const CovFamily family = table.route();
-  const int kind = table.family == COV_SUM ? table.fams : table.kind, d = table.d, ncomp = table.ncomp, rows = table.partials_rows();   // (SUM: the kernels' `kind` carries the members)
+  const int kind = table.kernel_kind(), d = table.d, ncomp = table.ncomp;
   const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
   PLMC_REQUIRE(table.kind >= 0 && table.kind <= 4, "unknown kernel kind");
   PLMC_REQUIRE(Xop && beta && X && ell && grad && partials, "null pointer");
@@ -772,12 +765,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
   {
     ProfScope ps(PK_KINV_GRAD, st, q * np * np * (double)krows, q * np * (double)krows * sizeof(T));
     switch (family) {
-      case COV_PER: if (d == 1) PLMC_LAUNCH_LT(COV_PER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_PER, 4); else PLMC_LAUNCH_LT(COV_PER, 8); break;
-      case COV_LPER: if (d == 1) PLMC_LAUNCH_LT(COV_LPER, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_LPER, 4); else PLMC_LAUNCH_LT(COV_LPER, 8); break;
-      case COV_SUM: if (d == 1) PLMC_LAUNCH_LT(COV_SUM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SUM, 4); else PLMC_LAUNCH_LT(COV_SUM, 8); break;
-      case COV_RQ: if (d == 1) PLMC_LAUNCH_LT(COV_RQ, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_RQ, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_RQ, 8); else PLMC_LAUNCH_LT(COV_RQ, 16); break;
-      case COV_DOT: if (d == 1) PLMC_LAUNCH_LT(COV_DOT, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_DOT, 4); else if (d <= 8) PLMC_LAUNCH_LT(COV_DOT, 8); else PLMC_LAUNCH_LT(COV_DOT, 16); break;
-      case COV_SM: if (d == 1) PLMC_LAUNCH_LT(COV_SM, 1); else if (d <= 4) PLMC_LAUNCH_LT(COV_SM, 4); else PLMC_LAUNCH_LT(COV_SM, 8); break;
+      default: with_capacity<0>(family, d, [&](auto f, auto dc) { PLMC_LAUNCH_LT(decltype(f)::value, decltype(dc)::value); }); break;
       case COV_ADD: PLMC_LAUNCH_LT(COV_ADD, 0); break;
       case COV_PLAIN:
         if (d <= 4) PLMC_LAUNCH_LG(4, false);
@@ -788,19 +776,7 @@ int loo_grad_impl(const CovTable &table, const T *Xop, int64_t n_pad, int64_t kr
   }
 #undef PLMC_LAUNCH_LT
 #undef PLMC_LAUNCH_LG
-  {
-    ProfScope ps(PK_REDUCE, st, 0.0, (double)m * m * q * rows * GP * sizeof(double) / 2);
-    switch (family) {
-      case COV_PER: hipLaunchKernelGGL(k_reduce_grad_per<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, grad); break;
-      case COV_LPER: hipLaunchKernelGGL(k_reduce_grad_lper<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, second, third, grad); break;
-      case COV_SUM: hipLaunchKernelGGL(k_reduce_grad_sum<T>, dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, table.fams, ell, grad); break;
-      case COV_RQ: hipLaunchKernelGGL(k_reduce_grad_rq<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad); break;
-      case COV_DOT: hipLaunchKernelGGL(k_reduce_grad_dot, dim3(q), dim3(RED_NT), 0, st, part, m, d, grad); break;
-      case COV_SM: hipLaunchKernelGGL((k_reduce_grad_add<T, true>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
-      case COV_ADD: hipLaunchKernelGGL((k_reduce_grad_add<T, false>), dim3(q, ncomp), dim3(RED_NT), 0, st, part, m, d, ncomp, ell, grad); break;
-      case COV_PLAIN: hipLaunchKernelGGL(k_reduce_grad<T>, dim3(q), dim3(RED_NT), 0, st, part, m, d, ell, grad);
-    }
-  }
+  launch_reduce_grad<T>(table, part, m, q, grad, st);
   return launch_status(__func__);
 }
 
@@ -873,6 +849,38 @@ int sum_single_member(const CovTable &t, int64_t n_pad, int q, double *grad, voi
 
 }  // namespace plmc
 
+// The K^-1 + gradient call of either element type.  fp32 goes by the arithmetic of its products (PLMC_SPLIT) and by what fits beside the
+// split engine (api_common.hpp, FamilyTraits::split_max_d); fp64 has one path and looks at neither eig_lo nor Vd.  Vd: the scratch of
+// the sweep that produced W, or null.
+template <typename T>
+static int kinv_grad_any(const plmc::CovTable &table, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n,
+                         double *grad, T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag, void *partials, int q, const T *eig_lo, void *stream,
+                         const T *Vd = nullptr, bool check_only = false) {
+  if (!table.single_member()) {
+    if constexpr (sizeof(T) == 8) {
+      return plmc::kinv_grad_impl<double, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr,
+                                                stream, nullptr, 0, check_only);
+    } else {
+      const int split = plmc::knobs().split;
+      const bool three_planes = !(split == 2 && eig_lo);
+      if (split == 0 || table.d > plmc::FAMILY[table.family].split_max_d[three_planes])
+        return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr,
+                                                 stream, nullptr, 0, check_only);
+      // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
+      if (!three_planes)
+        return plmc::kinv_grad_impl<float, plmc::SplitH2>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                                                          eig_lo, stream, Vd, ldw, check_only);
+      return plmc::kinv_grad_impl<float, plmc::SplitB3>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
+                                                        nullptr, stream, Vd, ldw, check_only);
+    }
+  }
+  // a sum of one member IS that member: its family's own path.  (Behind the others in the text, so that the gradient kernels come first
+  // in the code object, as they always did: profiles/family_dispatch_kernel_identity.md.)
+  return plmc::sum_single_member<T>(table, n_pad, q, grad, partials, stream, [&](const plmc::CovTable &mt, double *fg, bool check) {
+    return kinv_grad_any<T>(mt, W, n_pad, ldw, strideW, alpha, X, n, fg, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd, check);
+  });
+}
+
 extern "C" {
 // per-tile partial sums + (4-byte elements) the planes of W for the split engine (the entry points without Vd); independent of the knobs
 int64_t plmc_grad_scratch_bytes_for(int64_t n_pad, int q, int elem_bytes) {
@@ -886,268 +894,64 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
   const int64_t m = n_pad / plmc::NB;
   return m * m * (int64_t)q * plmc::GP * (int64_t)sizeof(double);
 }
-// the fp32 call by the arithmetic of its products (PLMC_SPLIT); Vd: the scratch of the sweep that produced W, or null
-static int kinv_grad_f32_any(const plmc::CovTable &table, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                             const float *X, int n, double *grad, float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                             const float *eig_lo, void *stream, const float *Vd = nullptr, bool check_only = false) {
-  const int split = plmc::knobs().split;
-  // A spectral mixture on d > 1 dimensions keeps d sines, cosines and partial products per element live beside the accumulators: that
-  // fits the registers of the 256-thread fp32 kernel, not those of the 512-thread split-engine kernel (it would spill) -- so d > 1 takes
-  // the fp32 products whatever the knob; d = 1, the reference's use, runs on the split engine.  The periodic kernel keeps d sines, cosine
-  // complements and 2 d sums live and follows the same rule, and so does the locally periodic kernel (3 d sums).  The rational-quadratic epilogue fits beside the two-plane fp16 scheme at
-  // every d; beside the three bf16 planes (PLMC_SPLIT=3, or no eig_lo) it fits at d = 1 only, so d > 1 takes the fp32 products there.
-  // The dot-product epilogue follows the rational-quadratic rule (DC = 4, 8, 16 spill beside the three planes, none beside the two).
-  const bool three_planes = !(split == 2 && eig_lo);
-  // A heterogeneous sum may hold a periodic or a locally periodic member and follows their rule whatever its members are.
-  if (split == 0 || ((table.family == plmc::COV_SM || table.family == plmc::COV_PER || table.family == plmc::COV_LPER || table.family == plmc::COV_SUM) && table.d > 1) ||
-      ((table.family == plmc::COV_RQ || table.family == plmc::COV_DOT) && table.d > 1 && three_planes))
-    return plmc::kinv_grad_impl<float, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream,
-                                             nullptr, 0, check_only);
-  // Vd: the scratch of the sweep that produced W, whose leading dimension is ldw (W lives in the factor buffer's columns)
-  if (split == 2 && eig_lo)
-    return plmc::kinv_grad_impl<float, plmc::SplitH2>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo,
-                                                      stream, Vd, ldw, check_only);
-  return plmc::kinv_grad_impl<float, plmc::SplitB3>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr,
-                                                    stream, Vd, ldw, check_only);
-}
-static int kinv_grad_f64(const plmc::CovTable &table, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
-                         const double *X, int n, double *grad, double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                         void *stream, bool check_only = false) {
-  return plmc::kinv_grad_impl<double, void>(table, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, nullptr, stream,
-                                            nullptr, 0, check_only);
-}
-// the entry points: the only place the covariance tables of this file are built from flat arguments
-using plmc::CovTable;
-int plmc_kinv_grad_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                       const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
-                       float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                       void *stream) {
-  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                           nullptr, stream);
-}
-int plmc_kinv_grad_ex_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                          const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
-                          float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                          const float *eig_lo, void *stream) {
-  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                           eig_lo, stream);
-}
-int plmc_kinv_grad_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                          const float *X, int n, int d, const float *ell, const float *oscale, double *grad,
-                          float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                          const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                           eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
-                          const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
-                          double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                          const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
-}
-// additive kernels: plmc_kinv_grad_vd_* with a component table (include/plmc.h)
-int plmc_kinv_grad_add_vd_f32(int kind, const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha,
-                              const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, double *grad,
-                              float *Kinv, int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q,
-                              const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::add(kind, d, ncomp, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
-                           q, eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_add_vd_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
-                              const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, double *grad,
-                              double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                              const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::add(kind, d, ncomp, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                       stream);
-}
-// spectral-mixture kernel: plmc_kinv_grad_vd_* with the table (scales, means, weights) (include/plmc.h)
+// The entry points of the families (api_common.hpp, PLMC_FAMILY_ENTRIES): the only place the covariance tables of this file are built from
+// flat arguments.  plmc_kinv_grad*_vd_*: `partials` is sized by plmc_grad_partials_bytes, for a spectral mixture, a locally periodic
+// kernel and a sum by their own plmc_*_grad_partials_bytes.  plmc_loo_grad*: the leave-one-out pseudo-likelihood (include/plmc.h,
+// "Leave-one-out objective"), the family's gradient table of 1/2 (beta beta^T - Xop^T Xop).
+#define PLMC_GRAD_ENTRY(SUF, T, INFIX, LEAD, PARAMS, TABLE)                                                                                     \
+  int plmc_kinv_grad##INFIX##_vd_##SUF(PLMC_LEAD_##LEAD const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X,    \
+                                       int n, int d, PLMC_UNPACK PARAMS, double *grad, T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag,     \
+                                       void *partials, int q, const T *eig_lo, const T *Vd, void *stream) {                                     \
+    return kinv_grad_any<T>(TABLE, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd);  \
+  }                                                                                                                                             \
+  int plmc_loo_grad##INFIX##_##SUF(PLMC_LEAD_##LEAD const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta,    \
+                                   const T *X, int n, int d, PLMC_UNPACK PARAMS, double *grad, void *partials, int q, void *stream) {           \
+    return plmc::loo_grad_impl<T>(TABLE, Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);                               \
+  }
+PLMC_FAMILY_ENTRIES(PLMC_GRAD_ENTRY, f32, float)
+PLMC_FAMILY_ENTRIES(PLMC_GRAD_ENTRY, f64, double)
+#undef PLMC_GRAD_ENTRY
+// the plain kernel without the sweep's scratch, with and without eigenvalue bounds
+#define PLMC_KINV_GRAD_PLAIN(SUF, T)                                                                                                            \
+  int plmc_kinv_grad_##SUF(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n, int d,         \
+                           const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag, void *partials,    \
+                           int q, void *stream) {                                                                                               \
+    return kinv_grad_any<T>(plmc::CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK,         \
+                            kinv_diag, partials, q, nullptr, stream);                                                                           \
+  }                                                                                                                                             \
+  int plmc_kinv_grad_ex_##SUF(int kind, const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X, int n, int d,      \
+                              const T *ell, const T *oscale, double *grad, T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag, void *partials, \
+                              int q, const T *eig_lo, void *stream) {                                                                           \
+    return kinv_grad_any<T>(plmc::CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK,         \
+                            kinv_diag, partials, q, eig_lo, stream);                                                                            \
+  }
+PLMC_KINV_GRAD_PLAIN(f32, float)
+PLMC_KINV_GRAD_PLAIN(f64, double)
+#undef PLMC_KINV_GRAD_PLAIN
+// one row of fp64 partial sums per tile (and component), whatever the element type
 int64_t plmc_sm_grad_partials_bytes(int64_t n_pad, int q, int nmix, int elem_bytes) {
-  (void)elem_bytes;                                   // one row of fp64 partial sums per tile and component, whatever the element type
+  (void)elem_bytes;
   return plmc_grad_partials_bytes(n_pad, q * nmix);
 }
-int plmc_kinv_grad_sm_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                             int nmix, const float *scales, const float *means, const float *weights, double *grad, float *Kinv, int64_t ldk,
-                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::sm(d, nmix, scales, means, weights), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
-                           partials, q, eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_sm_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                             int nmix, const double *scales, const double *means, const double *weights, double *grad, double *Kinv, int64_t ldk,
-                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::sm(d, nmix, scales, means, weights), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
-                       q, stream);
-}
-// periodic kernel: plmc_kinv_grad_vd_* with the table (lengthscales, periods, output scale) (include/plmc.h)
 int64_t plmc_per_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
-  (void)elem_bytes;                                   // one row of fp64 partial sums per tile, whatever the element type
+  (void)elem_bytes;
   return plmc_grad_partials_bytes(n_pad, q);
 }
-int plmc_kinv_grad_per_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                              const float *ell, const float *period, const float *oscale, double *grad, float *Kinv, int64_t ldk,
-                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::per(d, ell, period, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                           eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_per_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                              const double *ell, const double *period, const double *oscale, double *grad, double *Kinv, int64_t ldk,
-                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::per(d, ell, period, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                       stream);
-}
-// rational-quadratic kernel: plmc_kinv_grad_vd_* with the table (lengthscales, alpha, output scale) (include/plmc.h); `partials` is sized
-// by plmc_grad_partials_bytes.  (`shape` is the kernel's alpha; `alpha` is K^-1 y as everywhere in this file)
-int plmc_kinv_grad_rq_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                             const float *ell, const float *shape, const float *oscale, double *grad, float *Kinv, int64_t ldk,
-                             int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::rq(d, ell, shape, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                           eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_rq_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                             const double *ell, const double *shape, const double *oscale, double *grad, double *Kinv, int64_t ldk,
-                             int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::rq(d, ell, shape, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q,
-                       stream);
-}
-// locally periodic kernel: plmc_kinv_grad_vd_* with the table (periodic lengthscales, periods, RBF lengthscales, output scale)
-// (include/plmc.h); `partials` is sized by plmc_lper_grad_partials_bytes
 int64_t plmc_lper_grad_partials_bytes(int64_t n_pad, int q, int elem_bytes) {
-  (void)elem_bytes;                                   // one row of fp64 partial sums per tile, whatever the element type
+  (void)elem_bytes;
   return plmc_grad_partials_bytes(n_pad, q);
 }
-int plmc_kinv_grad_lper_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                               const float *ell, const float *period, const float *rbf_ell, const float *oscale, double *grad, float *Kinv,
-                               int64_t ldk, int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd,
-                               void *stream) {
-  return kinv_grad_f32_any(CovTable::lper(d, ell, period, rbf_ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
-                           partials, q, eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_lper_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                               const double *ell, const double *period, const double *rbf_ell, const double *oscale, double *grad, double *Kinv,
-                               int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd,
-                               void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::lper(d, ell, period, rbf_ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
-                       partials, q, stream);
-}
-// heterogeneous sum: plmc_kinv_grad_add_vd_* with the members (host array `fam`) and their table (include/plmc.h); `partials` is sized by
-// plmc_sum_grad_partials_bytes.  One member: that family's own path (sum_single_member)
+// ... and the scratch of a one-member sum behind them (sum_single_member)
 int64_t plmc_sum_grad_partials_bytes(int64_t n_pad, int q, int ncomp, int elem_bytes) {
-  (void)elem_bytes;                                   // one row of fp64 partial sums per tile and component, whatever the element type
+  (void)elem_bytes;
   return plmc_grad_partials_bytes(n_pad, q * ncomp) + plmc::SUM_TAIL_BYTES * q;
 }
-int plmc_kinv_grad_sum_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                              int ncomp, const int *fam, const float *table, const float *oscale, double *grad, float *Kinv, int64_t ldk,
-                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);
-  if (t.single_member())
-    return plmc::sum_single_member<float>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {
-      return kinv_grad_f32_any(mt, W, n_pad, ldw, strideW, alpha, X, n, fg, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd, check_only);
-    });
-  return kinv_grad_f32_any(t, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_sum_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                              int ncomp, const int *fam, const double *table, const double *oscale, double *grad, double *Kinv, int64_t ldk,
-                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);
-  if (t.single_member())
-    return plmc::sum_single_member<double>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {
-      return kinv_grad_f64(mt, W, n_pad, ldw, strideW, alpha, X, n, fg, Kinv, ldk, strideK, kinv_diag, partials, q, stream, check_only);
-    });
-  return kinv_grad_f64(t, W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
-}
-// dot-product kernel: plmc_kinv_grad_vd_* with the table (variances, offset, power, output scale) (include/plmc.h); `partials` is sized
-// by plmc_grad_partials_bytes
-int plmc_kinv_grad_dot_vd_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *alpha, const float *X, int n, int d,
-                              const float *var, const float *offset, int power, const float *oscale, double *grad, float *Kinv, int64_t ldk,
-                              int64_t strideK, float *kinv_diag, void *partials, int q, const float *eig_lo, const float *Vd, void *stream) {
-  return kinv_grad_f32_any(CovTable::dot(d, power, var, offset, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag,
-                           partials, q, eig_lo, stream, Vd);
-}
-int plmc_kinv_grad_dot_vd_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha, const double *X, int n, int d,
-                              const double *var, const double *offset, int power, const double *oscale, double *grad, double *Kinv, int64_t ldk,
-                              int64_t strideK, double *kinv_diag, void *partials, int q, const double *eig_lo, const double *Vd, void *stream) {
-  (void)eig_lo;
-  (void)Vd;
-  return kinv_grad_f64(CovTable::dot(d, power, var, offset, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials,
-                       q, stream);
-}
-int plmc_kinv_grad_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
-                       const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
-                       double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                       void *stream) {
-  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
-}
-int plmc_kinv_grad_ex_f64(int kind, const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *alpha,
-                          const double *X, int n, int d, const double *ell, const double *oscale, double *grad,
-                          double *Kinv, int64_t ldk, int64_t strideK, double *kinv_diag, void *partials, int q,
-                          const double *eig_lo, void *stream) {
-  (void)eig_lo;
-  return kinv_grad_f64(CovTable::plain(kind, d, ell, oscale), W, n_pad, ldw, strideW, alpha, X, n, grad, Kinv, ldk, strideK, kinv_diag, partials, q, stream);
-}
-// leave-one-out pseudo-likelihood (include/plmc.h, "Leave-one-out objective"): the family's gradient table of 1/2 (beta beta^T - Xop^T Xop)
-#define PLMC_LOO_ENTRY(SUF, T)                                                                                                                  \
-  int plmc_loo_grad_##SUF(int kind, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n, \
-                          int d, const T *ell, const T *oscale, double *grad, void *partials, int q, void *stream) {                           \
-    return plmc::loo_grad_impl<T>(CovTable::plain(kind, d, ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
-  }                                                                                                                                             \
-  int plmc_loo_grad_add_##SUF(int kind, const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X,    \
-                              int n, int d, int ncomp, const T *ell, const T *oscale, double *grad, void *partials, int q, void *stream) {     \
-    return plmc::loo_grad_impl<T>(CovTable::add(kind, d, ncomp, ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q,   \
-                                  stream);                                                                                                      \
-  }                                                                                                                                             \
-  int plmc_loo_grad_sm_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n, int d, \
-                             int nmix, const T *scales, const T *means, const T *weights, double *grad, void *partials, int q, void *stream) { \
-    return plmc::loo_grad_impl<T>(CovTable::sm(d, nmix, scales, means, weights), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, \
-                                  stream);                                                                                                      \
-  }                                                                                                                                             \
-  int plmc_loo_grad_per_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
-                              int d, const T *ell, const T *period, const T *oscale, double *grad, void *partials, int q, void *stream) {      \
-    return plmc::loo_grad_impl<T>(CovTable::per(d, ell, period, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream); \
-  }                                                                                                                                             \
-  int plmc_loo_grad_lper_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,      \
-                               int d, const T *ell, const T *period, const T *rbf_ell, const T *oscale, double *grad, void *partials, int q,   \
-                               void *stream) {                                                                                                  \
-    return plmc::loo_grad_impl<T>(CovTable::lper(d, ell, period, rbf_ell, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, \
-                                  q, stream);                                                                                                   \
-  }                                                                                                                                             \
-  int plmc_loo_grad_sum_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
-                              int d, int ncomp, const int *fam, const T *table, const T *oscale, double *grad, void *partials, int q,          \
-                              void *stream) {                                                                                                   \
-    const CovTable t = CovTable::sum(d, ncomp, fam, table, oscale);                                                                             \
-    if (t.single_member())                                                                                                                      \
-      return plmc::sum_single_member<T>(t, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check_only) {              \
-        return plmc::loo_grad_impl<T>(mt, Xop, n_pad, krows, ldx, strideX, beta, X, n, fg, partials, q, stream, check_only);                    \
-      });                                                                                                                                       \
-    return plmc::loo_grad_impl<T>(t, Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);                                   \
-  }                                                                                                                                             \
-  int plmc_loo_grad_rq_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,        \
-                             int d, const T *ell, const T *alpha, const T *oscale, double *grad, void *partials, int q, void *stream) {         \
-    return plmc::loo_grad_impl<T>(CovTable::rq(d, ell, alpha, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);  \
-  }                                                                                                                                             \
-  int plmc_loo_grad_dot_##SUF(const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta, const T *X, int n,       \
-                              int d, const T *var, const T *offset, int power, const T *oscale, double *grad, void *partials, int q,            \
-                              void *stream) {                                                                                                   \
-    return plmc::loo_grad_impl<T>(CovTable::dot(d, power, var, offset, oscale), Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q,  \
-                                  stream);                                                                                                      \
-  }                                                                                                                                             \
+#define PLMC_LOO_OPERAND(SUF, T)                                                                                                                \
   int plmc_loo_operand_##SUF(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *rowscale, T *Xop, int64_t krows, int64_t ldx, \
                              int64_t strideX, int n, int q, void *stream) {                                                                    \
     return plmc::loo_operand_impl<T>(Kinv, n_pad, ldk, strideK, rowscale, Xop, krows, ldx, strideX, n, q, stream);                              \
   }
-PLMC_LOO_ENTRY(f32, float)
-PLMC_LOO_ENTRY(f64, double)
-#undef PLMC_LOO_ENTRY
+PLMC_LOO_OPERAND(f32, float)
+PLMC_LOO_OPERAND(f64, double)
+#undef PLMC_LOO_OPERAND
 }
