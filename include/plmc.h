@@ -816,6 +816,59 @@ int plmc_loo_operand_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t
                          int64_t ldx, int64_t strideX, int n, int q, void *stream);
 
 /*
+ * Input gradients of the exact log density: d log N(y; 0, Khat) / dX for q latents that share the inputs X (n x d), the row-wise
+ * pull-back of Omega = alpha alpha^T - Khat^-1 through the kernel's input derivative:
+ *     gX[lat][i][k] = sum_{j < n, j != i} (alpha_i alpha_j - P_ij) d k_lat(x_i, x_j) / d x_i[k]          (gX: q x n x d doubles, contiguous)
+ * -- no factor 1/2: x_i enters row i and column i of Khat.  The diagonal of these families does not depend on x.
+ *   Kinv: P = Khat^-1 as plmc_kinv_grad*_vd_* writes it through its `Kinv` argument (n_pad x ldk per latent, batch stride strideK): P_ij is
+ *   read at Kinv[min(i, j)][max(i, j)].  Nothing below the diagonal, no row or column at or beyond n (the identity padding) and nothing
+ *   of alpha (q x n_pad) at or beyond n is read; those may hold anything.
+ *   The table arguments are the family's, as in its plmc_kinv_grad*_vd_*; every family but the two named below is served: the stationary
+ *   kinds 0..3 and their component table (a slot with ell = +inf gets exactly 0), the spectral mixture (a dimension with scale = mean = 0
+ *   gets exactly 0), the periodic, the rational-quadratic and the locally periodic kernel, each up to its own limit on d.  Two
+ *   coincident rows of X contribute nothing to each other (Matern-1/2: the convention of plmc_kernel_vjp_*).
+ *   Every element of gX is written exactly once (no zero-initialised buffer), sums are fp64 in a fixed order without atomics (two calls
+ *   give the same bits), no scratch.  Every stored element is read twice: q n^2 kernel-derivative evaluations.
+ * Refused as argument errors: the spline kind, plmc_input_grad_sum_* and plmc_input_grad_dot_* (the diagonal of the spline and the
+ * dot-product kernels depends on x); they exist because the families' entry points come from one list.
+ * Bad arguments fail through plmc_last_error() before anything is launched.
+ */
+int plmc_input_grad_f32(int kind, const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n,
+                        int d, const float *ell, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_f64(int kind, const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n,
+                        int d, const double *ell, const double *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_add_f32(int kind, const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X,
+                            int n, int d, int ncomp, const float *ell, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_add_f64(int kind, const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X,
+                            int n, int d, int ncomp, const double *ell, const double *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_sm_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                           int nmix, const float *scales, const float *means, const float *weights, double *gX, int q, void *stream);
+int plmc_input_grad_sm_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                           int nmix, const double *scales, const double *means, const double *weights, double *gX, int q, void *stream);
+int plmc_input_grad_per_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                            const float *ell, const float *period, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_per_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                            const double *ell, const double *period, const double *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_rq_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                           const float *ell, const float *shape, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_rq_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                           const double *ell, const double *shape, const double *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_lper_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                             const float *ell, const float *period, const float *rbf_ell, const float *oscale, double *gX, int q,
+                             void *stream);
+int plmc_input_grad_lper_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                             const double *ell, const double *period, const double *rbf_ell, const double *oscale, double *gX, int q,
+                             void *stream);
+int plmc_input_grad_sum_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                            int ncomp, const int *fam, const float *table, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_sum_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                            int ncomp, const int *fam, const double *table, const double *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_dot_f32(const float *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const float *alpha, const float *X, int n, int d,
+                            const float *var, const float *offset, int power, const float *oscale, double *gX, int q, void *stream);
+int plmc_input_grad_dot_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const double *alpha, const double *X, int n, int d,
+                            const double *var, const double *offset, int power, const double *oscale, double *gX, int q, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

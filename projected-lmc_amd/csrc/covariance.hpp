@@ -49,6 +49,27 @@ template <typename T> __device__ __forceinline__ void kern_value_base(int kind, 
   base = T(5.0 / 3.0) * (T(1) + s) * e;
 }
 
+// ---- d k / d x (input_grad.hip).  Every family's *_dx adds  g os d k(a, b) / d a_k  to gx[k], k < DCAP, for one pair of raw input
+// rows a (registers) and b, with its table rows padded so that a slot beyond d adds exactly 0.  Coincident rows give exactly 0 for
+// every family.
+// stationary kinds, one component: il = 1 / ell [DCAP] (0 beyond d and on a slot the component ignores, ell = +inf).  The arithmetic
+// of k_kernel_vjp_add: the raw difference scaled, kern_value_base (Matern-1/2: base = 0 at r = 0), -g os base df_k / ell_k.
+template <typename T, int DCAP>
+__device__ __forceinline__ void kern_dx(int kind, const T (&a)[DCAP], const T *b, const T *il, T g, T os, T (&gx)[DCAP]) {
+  T df[DCAP];
+  T r2 = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    df[k] = (a[k] - b[k]) * il[k];
+    r2 += df[k] * df[k];
+  }
+  T val, base;
+  kern_value_base<T>(kind, r2, val, base);
+  const T c = g * os * base;
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) gx[k] -= (c * df[k]) * il[k];
+}
+
 // Gradient-epilogue variant: for fp32 the transcendental pair is taken from the hardware units
 // (v_sqrt_f32 / v_exp_f32, ~1-2 ulp) instead of the ~35-instruction IEEE expansions; the values only
 // weight a reduction whose fp32 tolerance is 1e-3, the covariance ASSEMBLY keeps the accurate forms.
@@ -168,6 +189,38 @@ __device__ __forceinline__ T sm_value(const T (&a)[DCAP], const T (&b)[DCAP], co
   }
   return sum;
 }
+__device__ __forceinline__ void sm_sincos(float f, float &s, float &c) { s = sinpif(2.0f * f); c = cospif(2.0f * f); }
+__device__ __forceinline__ void sm_sincos(double f, double &s, double &c) { sincospi(2.0 * f, &s, &c); }
+// d k / d a_k, summed over the M components (sm_value's tables):
+//     w env [-4 pi^2 s_k^2 tau_k prod_l cos_l - 2 pi mu_k sin_k prod_{l != k} cos_l],
+// the product of the other cosines from prefix and suffix products (kinv_epilogue_sm.inc): no division, finite where a cosine is 0.
+// A dimension with s = mu = 0 gives exactly 0.
+template <typename T, int DCAP>
+__device__ __forceinline__ void sm_dx(const T (&a)[DCAP], const T *b, const T *sc, const T *mu, const T *wt, int M, T g, T (&gx)[DCAP]) {
+#pragma unroll 1
+  for (int m = 0; m < M; ++m) {
+    T tau[DCAP], sn[DCAP], cs[DCAP], ex[DCAP];
+    T e = T(0), pre = T(1);
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      tau[k] = a[k] - b[k];
+      const T st = sc[m * DCAP + k] * tau[k];
+      e += st * st;
+      sm_sincos(sm_phase(a[k], b[k], mu[m * DCAP + k]), sn[k], cs[k]);
+      ex[k] = pre;
+      pre *= cs[k];
+    }
+    T suf = T(1);
+#pragma unroll
+    for (int k = DCAP - 1; k >= 0; --k) { ex[k] *= suf; suf *= cs[k]; }
+    const T cw = g * wt[m] * dexp(T(-SM_2PI2) * e);
+#pragma unroll
+    for (int k = 0; k < DCAP; ++k) {
+      const T s = sc[m * DCAP + k];
+      gx[k] -= cw * (T(2 * SM_2PI2) * (s * s * tau[k]) * pre + T(SM_2PI) * (mu[m * DCAP + k] * sn[k]) * ex[k]);
+    }
+  }
+}
 
 // ---- periodic [gpytorch-knowledge: PeriodicKernel.forward, v1.11, unverified offline]:
 //     k(x, x') = exp(-2 sum_k sin^2(pi (x_k - x'_k) / p_k) / ell_k)            (the lengthscale is not squared).
@@ -209,6 +262,26 @@ __device__ __forceinline__ T per_value(const T (&a)[DCAP], const T (&b)[DCAP], c
     e += (s * s) * w[k];
   }
   return dexp(T(-2) * e);
+}
+// sin(pi f), cos(pi f): sin(2 pi f) = 2 s c
+__device__ __forceinline__ void per_sincospi(float f, float &s, float &c) { s = sinpif(f); c = cospif(f); }
+__device__ __forceinline__ void per_sincospi(double f, double &s, double &c) { sincospi(f, &s, &c); }
+constexpr double PER_2PI = 6.283185307179586;
+// d k / d a_k = -k (2 / ell_k) (pi / p_k) sin(2 pi f_k)                                    (per_value's tables)
+template <typename T, int DCAP>
+__device__ __forceinline__ void per_dx(const T (&a)[DCAP], const T *b, const T *ip, const T *ipr, const T *w, T g, T os, T (&gx)[DCAP]) {
+  T s2[DCAP];
+  T e = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    T s, c;
+    per_sincospi(per_phase(a[k], b[k], ip[k], ipr[k]), s, c);
+    e += (s * s) * w[k];
+    s2[k] = T(2) * s * c;
+  }
+  const T cw = g * os * dexp(T(-2) * e);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) gx[k] -= cw * (T(PER_2PI) * (w[k] * ip[k]) * s2[k]);
 }
 
 // ---- rational quadratic [gpytorch-knowledge: RQKernel, unverified offline]:
@@ -254,6 +327,22 @@ __device__ __forceinline__ T rq_value(const T (&a)[DCAP], const T (&b)[DCAP], co
   }
   return rq_profile(r2, alpha, i2a);
 }
+// d k / d a_k = -base df_k / ell_k with rq_value_base_h's base = k / (1 + u)                 (rq_value's tables)
+template <typename T, int DCAP>
+__device__ __forceinline__ void rq_dx(const T (&a)[DCAP], const T *b, const T *w, T alpha, T i2a, T g, T os, T (&gx)[DCAP]) {
+  T df[DCAP];
+  T r2 = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    df[k] = (a[k] - b[k]) * w[k];
+    r2 += df[k] * df[k];
+  }
+  T val, base, vh;
+  rq_value_base_h(r2, alpha, i2a, val, base, vh);
+  const T c = g * os * base;
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) gx[k] -= (c * df[k]) * w[k];
+}
 
 // ---- locally periodic [gpytorch-knowledge: ProductKernel of PeriodicKernel and RBFKernel, unverified offline]:
 //     k(x, x') = exp(-2 sum_k sin^2(pi tau_k / p_k) / ell_k - 1/2 sum_k (tau_k / lam_k)^2),   tau = x - x'
@@ -275,6 +364,26 @@ __device__ __forceinline__ T lper_value(const T (&a)[DCAP], const T (&b)[DCAP], 
     r2 += sd * sd;
   }
   return lper_exp(e, r2);
+}
+// d k / d a_k = -k [(2 / ell_k) (pi / p_k) sin(2 pi f_k) + tau_k / lam_k^2]: the periodic term (per_dx) plus the RBF one, sharing
+// the one exponential                                                                        (lper_value's tables)
+template <typename T, int DCAP>
+__device__ __forceinline__ void lper_dx(const T (&a)[DCAP], const T *b, const T *ip, const T *ipr, const T *w, const T *v, T g, T os,
+                                        T (&gx)[DCAP]) {
+  T s2[DCAP], sd[DCAP];
+  T e = T(0), r2 = T(0);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) {
+    T s, c;
+    per_sincospi(per_phase(a[k], b[k], ip[k], ipr[k]), s, c);
+    e += (s * s) * w[k];
+    s2[k] = T(2) * s * c;
+    sd[k] = (a[k] - b[k]) * v[k];
+    r2 += sd[k] * sd[k];
+  }
+  const T cw = g * os * lper_exp(e, r2);
+#pragma unroll
+  for (int k = 0; k < DCAP; ++k) gx[k] -= cw * (T(PER_2PI) * (w[k] * ip[k]) * s2[k] + sd[k] * v[k]);
 }
 
 // ---- dot product [gpytorch-knowledge: LinearKernel, PolynomialKernel, unverified offline]:

@@ -37,7 +37,19 @@
       smem[L::AJ + tid] = live ? alpha[(int64_t)lat * n_pad + jb * NB + tid] : T(0);
     }
     __syncthreads();
-    const bool interior = ib < jb && (jb + 1) * NB <= n && !Kinv && !kinv_diag;
+    // `Kinv` alone (the input gradient of the MLL, input_grad.hip) does not change which instantiation sums a tile: the gradient
+    // table is the same bits with and without it.  The interior instantiation does not look at Kinv, and every element of such a
+    // tile lies above the diagonal: the tile is written here.
+    const bool interior = ib < jb && (jb + 1) * NB <= n && !kinv_diag;
+    if (interior && Kinv) {
+      T *Kt = Kinv + (int64_t)lat * strideK + (int64_t)ib * NB * ldk + (int64_t)jb * NB;
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) Kt[(int64_t)tile_row<T>(wm, mt, lane, r) * ldk + tile_col(wn, nt, lane)] = acc.v[mt][nt][r];
+    }
 #define PLMC_GRAD_TILE(KIND, INT) \
   grad_tile_small<T, DCAP, KIND, INT>(acc, smem, tid, os, ib, jb, n, lat, n_pad, Kinv, ldk, strideK, kinv_diag, g, g_noise, g_os)
     if (interior) {

@@ -166,25 +166,26 @@ RQ = "rq"
 SUM = "sum"
 _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
         "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
-        "plmc_loo_grad": "plmc_loo_grad_sum"}
+        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
-         "plmc_loo_grad": "plmc_loo_grad_lper"}
+         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper"}
 _DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
         "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
-        "plmc_loo_grad": "plmc_loo_grad_dot"}
+        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
-       "plmc_loo_grad": "plmc_loo_grad_rq"}
+       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
-        "plmc_loo_grad": "plmc_loo_grad_per"}
+        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
-       "plmc_loo_grad": "plmc_loo_grad_sm"}
+       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
-        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add"}
+        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add",
+        "plmc_input_grad": "plmc_input_grad_add"}
 
 
 def sum_kind(members):
@@ -423,6 +424,9 @@ class ExactLatentLogProb(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, ell, oscale, noise, y, kind, table=None):
+        x_grad = ctx.needs_input_grad[0]
+        if x_grad:
+            require_input_grad_kind(kind)
         _hip.require_device(X, ell, noise, y)
         L = _hip.lib()
         dt, dev = y.dtype, y.device
@@ -432,12 +436,15 @@ class ExactLatentLogProb(torch.autograd.Function):
         d = X.shape[1]
         _check_kernel_shape(L, ell, kind)
         G = n_components(ell, kind)
-        need_grad = any(ctx.needs_input_grad[1:5]) or table is not None
+        need_grad = any(ctx.needs_input_grad[1:5]) or table is not None or x_grad
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
         ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), _per_kind(kind))
         st = _hip.stream_ptr(dev)
         grad = table if table is not None else (torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
+        # d logp / dX, one (n, d) table per latent: the K^-1 + gradient kernel also writes K^-1, plmc_input_grad pulls alpha alpha^T - K^-1
+        # back through the kernel's input derivative.  Nothing of this exists when X requires no gradient.
+        gX = torch.empty(q, n, d, dtype=torch.float64, device=dev) if x_grad else None
 
         def enqueue(noise_eff):
             """factorisation + everything that consumes it; returns (deferred pivot check, logp)."""
@@ -455,12 +462,18 @@ class ExactLatentLogProb(torch.autograd.Function):
                 if gs is not None:
                     gs.wait_stream(torch.cuda.current_stream(dev))
                     gst = _hip.stream_handle(gs, dev)
-                    for t in (grad, Xc, ellc, osc, noise_eff):
+                    for t in (grad, Xc, ellc, osc, noise_eff, gX):
                         if t is not None:
                             t.record_stream(gs)
+                Kinv = _kinv_buffer(ws) if x_grad else None
+                ldk = Kinv.shape[2] if x_grad else 0
                 _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
                              _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad),
-                             None, 0, 0, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst), stream=gs)
+                             _hip.ptr(Kinv), ldk, ws.n_pad * ldk, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst),
+                             stream=gs)
+                if x_grad:
+                    _kernel_call(L, "plmc_input_grad", dt, (kind_code(kind), _hip.ptr(Kinv), ws.n_pad, ldk, ws.n_pad * ldk,
+                                 _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(gX), q, gst), stream=gs)
                 if gs is not None:
                     ws.pending = torch.cuda.Event()
                     ws.pending.record(gs)
@@ -483,7 +496,8 @@ class ExactLatentLogProb(torch.autograd.Function):
 
                 logp = walk(dt, info, attempt)[1]
         if need_grad:
-            ctx.save_for_backward(grad, ws.alpha[:, :n].clone())
+            ctx.save_for_backward(grad, ws.alpha[:, :n].clone(), gX)
+        ctx.x_dtype = X.dtype
         ctx.grad_ready = getattr(ws, "pending", None) if need_grad else None
         ctx.ell_shape = ell.shape
         ctx.os_shape = None if oscale is None else oscale.shape
@@ -492,15 +506,20 @@ class ExactLatentLogProb(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        grad, alpha = ctx.saved_tensors
+        grad, alpha, gX = ctx.saved_tensors
         dt = alpha.dtype
+        g_X = None
+        if gX is not None:                 # X is shared by the latents: their tables, weighted, summed in fp64
+            if ctx.grad_ready is not None:
+                torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
+            g_X = (gout.to(torch.float64)[:, None, None] * gX).sum(0).to(ctx.x_dtype)
         if ctx.table_out:                  # the hyper-parameter gradients flow through _HyperGrad
-            return None, None, None, None, -(gout[:, None].to(dt) * alpha), None, None
+            return g_X, None, None, None, -(gout[:, None].to(dt) * alpha), None, None
         if ctx.grad_ready is not None:
             torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
         g_ell, g_noise, g_os = _split_grad_table(gout.to(torch.float64)[:, None] * grad, ctx.ell_shape, ctx.os_shape)
         g_y = -(gout[:, None].to(dt) * alpha)
-        return None, g_ell, g_os, g_noise, g_y, None, None
+        return g_X, g_ell, g_os, g_noise, g_y, None, None
 
 
 class _HyperGrad(torch.autograd.Function):
@@ -622,9 +641,41 @@ def _loo_buffers(ws):
     leave-one-out objective, q (n_pad + NB) n_pad elements each, kept with the workspace."""
     buf = getattr(ws, "loo", None)
     if buf is None:
-        buf = ws.loo = (torch.empty(ws.q, ws.n_pad, ws.n_pad + ws.NB, dtype=ws.dtype, device=ws.device),
-                        torch.empty(ws.q, ws.n_pad + ws.NB, ws.n_pad, dtype=ws.dtype, device=ws.device))
+        buf = ws.loo = (_kinv_buffer(ws), torch.empty(ws.q, ws.n_pad + ws.NB, ws.n_pad, dtype=ws.dtype, device=ws.device))
     return buf
+
+
+def _kinv_buffer(ws):
+    """K^-1 as plmc_kinv_grad*_vd writes it through `Kinv` (n_pad rows of n_pad + NB per latent, the upper triangle), kept with the
+    workspace and created on first use: the leave-one-out objective and the input gradient of the MLL read it."""
+    buf = getattr(ws, "kinv", None)
+    if buf is None:
+        buf = ws.kinv = torch.empty(ws.q, ws.n_pad, ws.n_pad + ws.NB, dtype=ws.dtype, device=ws.device)
+    return buf
+
+
+def require_input_grad_kind(kind):
+    """d logp / dX exists for the kinds whose diagonal k(x, x) does not depend on x (plmc_input_grad*); the others say so."""
+    if kind == "spline" or is_dot(kind) or is_sum(kind):
+        raise NotImplementedError("kernel kind %r has no gradient with respect to the inputs yet (plmc_input_grad serves the stationary "
+                                  "kinds, additive tables, sm, periodic, rq and locally_periodic): detach the inputs, or use "
+                                  "one of those kernels behind an input_transform" % (kind,))
+
+
+def input_grad(kind, X, ell, oscale, Kinv, alpha):
+    """plmc_input_grad on caller-owned buffers: Kinv (q, n_pad, ldk) holding K^-1 in its upper triangle, alpha (q, n_pad), X (n, d) and
+    the kind's table (ell, oscale) as everywhere in this module -> gX (q, n, d) float64,
+        gX[l, i, k] = sum_{j != i} (alpha_li alpha_lj - Kinv_l[min(i, j), max(i, j)]) d k_l(x_i, x_j) / d x_i[k]."""
+    _hip.require_device(X, ell, Kinv, alpha)
+    L = _hip.lib()
+    dt, dev = Kinv.dtype, Kinv.device
+    q, n_pad, ldk = Kinv.shape
+    n, d = X.shape
+    Xc, ellc, osc, ac = (_contig(t, dt) for t in (X, ell, oscale, alpha))
+    gX = torch.empty(q, n, d, dtype=torch.float64, device=dev)
+    _kernel_call(L, "plmc_input_grad", dt, (kind_code(kind), _hip.ptr(Kinv), n_pad, ldk, Kinv.stride(0), _hip.ptr(ac), _hip.ptr(Xc), n, d),
+                 ellc, (_hip.ptr(osc), _hip.ptr(gX), q, _hip.stream_ptr(dev)))
+    return gX
 
 
 class ExactLooLogProb(torch.autograd.Function):

@@ -69,6 +69,9 @@ class LeaveOneOutPseudoLikelihood(ExactMarginalLogLikelihood):
         if isinstance(self.model, ProjectedGPModel):
             raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for ProjectedGPModel (its latent processes see "
                                       "projected data: train it with ProjectedLMCmll)")
+        if getattr(self.model, "input_transform", None) is not None:
+            raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for a model with an input_transform (the leave-one-out "
+                                      "objective has no gradient with respect to the inputs): train it with ExactMarginalLogLikelihood")
         if hasattr(c, "log_prob_batch"):
             raise NotImplementedError("LeaveOneOutPseudoLikelihood is not implemented for the inducing-point (SGPR) covariance of "
                                       "ExactGPModel(n_inducing_points=...)")

@@ -265,11 +265,18 @@ class ExactGPModel(ExactGP):
 
     def __init__(self, train_x, train_y, likelihood, n_tasks=1, prior_scales=None, prior_width=None,
                  mean_type=_m.ConstantMean, decomp=None, outputscales=False, kernel_type=_k.RBFKernel,
-                 ker_kwargs=None, n_inducing_points=None, **kwargs):
+                 ker_kwargs=None, n_inducing_points=None, input_transform=None, **kwargs):
         super().__init__(train_x, train_y, likelihood)
         if ker_kwargs is None:
             ker_kwargs = {}
-        self.dim = self.train_inputs[0].shape[1]
+        # input_transform (a torch.nn.Module | None): a learned feature map in front of the mean and the kernel, gpytorch's deep-kernel
+        # convention -- a warping, a linear embedding, a network.  Its parameters are the model's; the MLL reaches them through
+        # d logp / dX of the engine (_engine.ExactLatentLogProb).  `dim` is the width of the features.
+        if input_transform is not None and n_inducing_points is not None:
+            raise NotImplementedError("ExactGPModel(input_transform=..., n_inducing_points=...): the inducing-point (SGPR) path has no "
+                                      "gradient with respect to the inputs")
+        self.input_transform = input_transform
+        self.dim = self._features(self.train_inputs[0][:2].detach(), grad=False).shape[-1]
         self.n_tasks = n_tasks
         self.batch_lik = isinstance(likelihood, GaussianLikelihood)
         self.mean_module = mean_type(input_size=self.dim, batch_shape=torch.Size([n_tasks]))
@@ -286,8 +293,20 @@ class ExactGPModel(ExactGP):
             from .sgpr import InducingPointKernel
             self.covar_module = InducingPointKernel(self.covar_module, torch.randn(n_inducing_points, self.dim),
                                                     likelihood)
+        if input_transform is not None:
+            _engine.require_input_grad_kind(self.covar_module(torch.zeros(2, self.dim)).kind)
+
+    def _features(self, x, grad=True):
+        """What the mean and the kernel see: x, or input_transform(x)."""
+        if self.input_transform is None:
+            return x
+        if grad:
+            return self.input_transform(x)
+        with torch.no_grad():
+            return self.input_transform(x)
 
     def forward(self, x):
+        x = self._features(x)
         mean_x = self.mean_module(x)
         covar_x = self.covar_module(x)
         if not self.batch_lik and self.n_tasks > 1:
@@ -303,7 +322,8 @@ class ExactGPModel(ExactGP):
         return y if y.shape[-1] == n and y.shape[0] == self.n_tasks else y.T
 
     def _posterior(self, x, full_cov=False):
-        tx = self.train_inputs[0]
+        raw_tx = self.train_inputs[0]
+        tx, x = self._features(raw_tx, grad=False), self._features(x, grad=False)
         lazy = self.covar_module(tx)
         lik = self.likelihood
         if self.batch_lik:
@@ -320,7 +340,7 @@ class ExactGPModel(ExactGP):
         mean, v = _engine.exact_posterior(lazy.kind, lazy.x1, lazy.ell.detach(),
                                           None if lazy.oscale is None else lazy.oscale.detach(),
                                           noise.detach().to(lazy.ell.dtype), resid.detach(), xs, full_cov=full_cov,
-                                          cache=self._prediction_cache(), key=_engine.model_state_key(self, tx, self.train_targets))
+                                          cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_targets))
         mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
         return self._wrap_posterior(mean, v if full_cov else torch.diag_embed(v))
 
@@ -338,7 +358,7 @@ class ExactGPModel(ExactGP):
         means) is not supported."""
         if complex_mean:
             raise ValueError("A complex mean treatment was required, but the model mean function doesn't allow it !")
-        tx = self.train_inputs[0]
+        tx = self._features(self.train_inputs[0], grad=False)
         lazy = self.covar_module(tx)
         lik = self.likelihood
         if self.batch_lik:

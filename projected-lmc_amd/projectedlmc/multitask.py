@@ -27,6 +27,8 @@ class MultitaskGPModel(ExactGPModel):
         _k.refuse_periodic(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_rq(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_dot(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
+        if kwargs.get("input_transform") is not None:
+            raise NotImplementedError("MultitaskGPModel (dense LMC / ICM) has no gradient with respect to the inputs: no input_transform")
         super().__init__(train_x, train_y, likelihood, n_tasks=1, outputscales=False, **kwargs)
         _k.refuse_product(self.covar_module, "MultitaskGPModel (dense LMC / ICM)")      # (kernel_type may be a factory: look at what it built)
         _k.refuse_sum(self.covar_module, "MultitaskGPModel (dense LMC / ICM)")

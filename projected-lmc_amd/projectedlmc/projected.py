@@ -282,6 +282,7 @@ class ProjectedGPModel(ExactGPModel):
     # ------------------------------------------------------------------------------------ forward
     def forward(self, x):
         """Prior of the latent processes only (projected_lmc.py:1088-1091)."""
+        x = self._features(x)
         return MultivariateNormal(self.mean_module(x), self.covar_module(x))
 
     def _latent_posterior(self, x, full_cov=False):
@@ -289,7 +290,8 @@ class ProjectedGPModel(ExactGPModel):
             return self._latent_posterior_body(x, full_cov)
 
     def _latent_posterior_body(self, x, full_cov=False):
-        tx = self.train_inputs[0]
+        raw_tx = self.train_inputs[0]
+        tx, x = self._features(raw_tx, grad=False), self._features(x, grad=False)
         lazy = self.covar_module(tx)
         ytil = self.project_data(self.train_y).detach()
         if hasattr(lazy, "log_prob_batch"):                    # SGPR latents (n_inducing_points)
@@ -304,12 +306,12 @@ class ProjectedGPModel(ExactGPModel):
             osc = None if osc is None else osc[ids]
         return _engine.exact_posterior(lazy.kind, lazy.x1, ell, osc, noise, ytil, self.covar_module.select(x),
                                        full_cov=full_cov, cache=self._prediction_cache(),
-                                       key=_engine.model_state_key(self, tx, self.train_y) + (tuple(ids) if ids is not None else ()))
+                                       key=_engine.model_state_key(self, raw_tx, self.train_y) + (tuple(ids) if ids is not None else ()))
 
     def compute_loo(self, output=None):
         """LOO moments of the q latent GPs on the projected data, (n x q) each
         (projected_lmc.py:1108-1119)."""
-        tx = self.train_inputs[0]
+        tx = self._features(self.train_inputs[0], grad=False)
         lazy = self.covar_module(tx)
         with torch.no_grad():
             ytil = self.project_data(self.train_y)
