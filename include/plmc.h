@@ -869,6 +869,81 @@ int plmc_input_grad_dot_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int6
                             const double *var, const double *offset, int power, const double *oscale, double *gX, int q, void *stream);
 
 /*
+ * Derivative of the eval-mode posterior moments with respect to the test inputs, for q latents on the training inputs X (n x d) and the
+ * test inputs Xs (ns x d):
+ *     Jm[lat][s][k] = d mean(s) / d x*_s[k] =      sum_{i < n} alpha_i d k_lat(x*_s, x_i) / d x*_s[k]
+ *     Jv[lat][s][k] = d var(s)  / d x*_s[k] = -2 * sum_{i < n} B_is    d k_lat(x*_s, x_i) / d x*_s[k]         (Jm, Jv: q x ns x d doubles, contiguous)
+ * with alpha = Khat^-1 y and B = Khat^-1 K*^T.  The diagonal of these families does not depend on x, and test points do not interact in
+ * the marginal moments: Jm and Jv are the whole Jacobian.
+ *   alpha: q x n_pad (n_pad >= n; any padding).  B: row i a training point, column s a test point, contiguous in s, ldb >= ns elements
+ *   between rows, strideB between latents -- what a plmc_gemm_tn* call leaves.  B = NULL: only Jm is written, Jv is not touched (and may be
+ *   NULL).  Nothing of alpha at or beyond n, no row of B at or beyond n and no column at or beyond ns is read; those may hold anything.
+ *   The table arguments are the family's, as in its plmc_input_grad*, and so are the families served and their limits on d, the exact
+ *   zeros (a slot with ell = +inf; a mixture dimension with scale = mean = 0) and the coincident points: a test point that coincides with a
+ *   training point gets nothing from that pair (Matern-1/2: the convention of plmc_kernel_vjp_*).
+ *   The unit derivative of a pair is evaluated once, with the accurate transcendental forms, and weighted by alpha_i and by -2 B_is in
+ *   fp64.  Sums are fp64 in a fixed order without atomics (two calls give the same bits); every element of Jm (and Jv) is written exactly
+ *   once; no private scratch.
+ *   With few test points the training rows are split into plmc_posterior_dx_splits(n, ns, q) ranges, one workgroup each per block of 64
+ *   test points and latent, a function of (n, ns, q) alone; their partial sums go through `partials`,
+ *   plmc_posterior_dx_partials_bytes(n, ns, d, q) bytes (0 with one range: `partials` may then be NULL), and are added in the order of
+ *   the ranges.  q n ns kernel-derivative evaluations; B is read once.
+ * Refused as argument errors: the spline kind, plmc_posterior_dx_sum_* and plmc_posterior_dx_dot_* (the diagonal of the spline and the
+ * dot-product kernels depends on x); they exist because the families' entry points come from one list.
+ * Bad arguments (those, d beyond the family's limit, n < 1, ns < 1, a null pointer, ldb < ns) fail through plmc_last_error() before
+ * anything is launched.
+ */
+int     plmc_posterior_dx_splits(int n, int ns, int q);
+int64_t plmc_posterior_dx_partials_bytes(int n, int ns, int d, int q);
+int plmc_posterior_dx_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *oscale, const float *alpha,
+                          int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void *partials, int q, void *stream);
+int plmc_posterior_dx_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *oscale, const double
+                          *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void *partials, int q, void
+                          *stream);
+int plmc_posterior_dx_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell, const float *oscale, const
+                              float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void *partials, int
+                              q, void *stream);
+int plmc_posterior_dx_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell, const double *oscale,
+                              const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                              *partials, int q, void *stream);
+int plmc_posterior_dx_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means, const float
+                             *weights, const float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                             *partials, int q, void *stream);
+int plmc_posterior_dx_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means, const
+                             double *weights, const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double
+                             *Jv, void *partials, int q, void *stream);
+int plmc_posterior_dx_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *oscale, const
+                              float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void *partials, int
+                              q, void *stream);
+int plmc_posterior_dx_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period, const double *oscale,
+                              const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                              *partials, int q, void *stream);
+int plmc_posterior_dx_rq_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *shape, const float *oscale, const
+                             float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void *partials, int q,
+                             void *stream);
+int plmc_posterior_dx_rq_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *shape, const double *oscale,
+                             const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                             *partials, int q, void *stream);
+int plmc_posterior_dx_lper_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *rbf_ell,
+                               const float *oscale, const float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm,
+                               double *Jv, void *partials, int q, void *stream);
+int plmc_posterior_dx_lper_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period, const double
+                               *rbf_ell, const double *oscale, const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB,
+                               double *Jm, double *Jv, void *partials, int q, void *stream);
+int plmc_posterior_dx_sum_f32(const float *X, int n, const float *Xs, int ns, int d, int ncomp, const int *fam, const float *table, const float
+                              *oscale, const float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                              *partials, int q, void *stream);
+int plmc_posterior_dx_sum_f64(const double *X, int n, const double *Xs, int ns, int d, int ncomp, const int *fam, const double *table, const double
+                              *oscale, const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                              *partials, int q, void *stream);
+int plmc_posterior_dx_dot_f32(const float *X, int n, const float *Xs, int ns, int d, const float *var, const float *offset, int power, const float
+                              *oscale, const float *alpha, int64_t n_pad, const float *B, int64_t ldb, int64_t strideB, double *Jm, double *Jv, void
+                              *partials, int q, void *stream);
+int plmc_posterior_dx_dot_f64(const double *X, int n, const double *Xs, int ns, int d, const double *var, const double *offset, int power, const
+                              double *oscale, const double *alpha, int64_t n_pad, const double *B, int64_t ldb, int64_t strideB, double *Jm, double
+                              *Jv, void *partials, int q, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

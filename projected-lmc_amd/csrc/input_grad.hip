@@ -12,14 +12,13 @@
 // identity padding (rows or columns >= n) or in alpha past n is read, and every load is unconditional.
 #include "api_common.hpp"
 #include "covariance.hpp"
+#include "input_dx.hpp"
 #include "../../include/plmc.h"
 
 namespace plmc {
 
 constexpr int IG_JC = 32;                            // columns per staged chunk (NB is a multiple: a chunk lies in one block column)
-constexpr int IG_TAB = 2 * SM_MAX_MIX * SM_MAX_DIM + SM_MAX_MIX;   // the largest table of one latent: the mixture's
 static_assert(NB % IG_JC == 0 && NTHREADS == 2 * NB && IG_JC % (NTHREADS / NB) == 0 && NTHREADS % IG_JC == 0, "input-gradient thread map");
-static_assert(IG_TAB >= MAX_COMP * MAX_DIM + MAX_COMP && IG_TAB >= 4 * LPER_MAX_DIM && IG_TAB >= RQ_MAX_DIM + 2, "input-gradient table");
 
 template <typename T, int DC> constexpr int ig_stage_bytes() { return (IG_JC * (NB + 1) + IG_JC * DC + IG_JC + IG_TAB) * (int)sizeof(T); }
 template <typename T, int DC> constexpr int ig_lds_bytes() {
@@ -27,7 +26,7 @@ template <typename T, int DC> constexpr int ig_lds_bytes() {
   return ((ig_stage_bytes<T, DC>() > red ? ig_stage_bytes<T, DC>() : red) + 15) / 16 * 16;
 }
 
-// F: COV_ADD serves the plain kernel too (one component; ell (q, d) is ell (q, 1, d)).  `second`, `third`: the family's rows (CovTable).
+// F, the table arguments: input_dx.hpp
 template <typename T, CovFamily F, int DC>
 __global__ __launch_bounds__(NTHREADS) void k_input_grad(int kind, int ncomp, const T *__restrict__ Kinv, int64_t ldk, int64_t strideK,
                                                           const T *__restrict__ alpha, int64_t n_pad, const T *__restrict__ X, int n, int d,
@@ -47,57 +46,8 @@ __global__ __launch_bounds__(NTHREADS) void k_input_grad(int kind, int ncomp, co
   const T *al = alpha + (int64_t)lat * n_pad;
 
   // ---- the latent's table, padded with what makes a slot beyond d add exactly 0
-  if constexpr (F == COV_ADD) {                      // [MAX_COMP][DC] 1 / ell | [MAX_COMP] os
-    for (int e = tid; e < MAX_COMP * DC; e += NTHREADS) {
-      const int g = e / DC, k = e % DC;
-      const bool used = g < ncomp && k < d;
-      const T v = ell[((int64_t)lat * ncomp + (g < ncomp ? g : 0)) * d + (k < d ? k : 0)];
-      tab[e] = used ? T(1) / v : T(0);
-    }
-    if (tid < MAX_COMP) {
-      const T v = oscale ? oscale[(int64_t)lat * ncomp + (tid < ncomp ? tid : 0)] : T(1);
-      tab[MAX_COMP * DC + tid] = tid < ncomp ? v : T(0);
-    }
-  } else if constexpr (F == COV_SM) {                // [M][DC] scales | [M][DC] means | [M] weights
-    for (int e = tid; e < SM_MAX_MIX * DC; e += NTHREADS) {
-      const int g = e / DC, k = e % DC;
-      const bool used = g < ncomp && k < d;
-      const int64_t o = ((int64_t)lat * ncomp + (g < ncomp ? g : 0)) * d + (k < d ? k : 0);
-      const T s = ell[o], m = second[o];
-      tab[e] = used ? s : T(0);
-      tab[SM_MAX_MIX * DC + e] = used ? m : T(0);
-    }
-    if (tid < SM_MAX_MIX) {
-      const T v = oscale ? oscale[(int64_t)lat * ncomp + (tid < ncomp ? tid : 0)] : T(1);
-      tab[2 * SM_MAX_MIX * DC + tid] = tid < ncomp ? v : T(0);
-    }
-  } else if constexpr (F == COV_PER || F == COV_LPER) {   // [DC] 1 / p | its residual | 1 / ell | 1 / lam
-    if (tid < DC) {
-      const int64_t o = (int64_t)lat * d + (tid < d ? tid : 0);
-      T ip, ipr;
-      per_inv_period(second[o], ip, ipr);
-      const T w = T(1) / ell[o];
-      tab[tid] = tid < d ? ip : T(0);
-      tab[DC + tid] = tid < d ? ipr : T(0);
-      tab[2 * DC + tid] = tid < d ? w : T(0);
-      if constexpr (F == COV_LPER) {
-        const T v = T(1) / third[o];
-        tab[3 * DC + tid] = tid < d ? v : T(0);
-      }
-    }
-  } else if constexpr (F == COV_RQ) {                // [DC] 1 / ell | alpha | 1 / (2 alpha)
-    if (tid < DC) {
-      const T w = T(1) / ell[(int64_t)lat * d + (tid < d ? tid : 0)];
-      tab[tid] = tid < d ? w : T(0);
-    }
-    if (tid == 0) {
-      const T a = second[lat];
-      tab[DC] = a;
-      tab[DC + 1] = T(1) / (T(2) * a);
-    }
-  }
-  T os = T(1);
-  if constexpr (F == COV_PER || F == COV_LPER || F == COV_RQ) os = oscale ? oscale[lat] : T(1);
+  dx_stage_table<T, F, DC>(tab, tid, lat, d, ncomp, ell, second, third, oscale);
+  const T os = dx_oscale<T, F>(oscale, lat);
 
   // ---- this thread's row
   T xi[DC];
@@ -153,18 +103,7 @@ __global__ __launch_bounds__(NTHREADS) void k_input_grad(int kind, int ncomp, co
       T gx[DC];
 #pragma unroll
       for (int k = 0; k < DC; ++k) gx[k] = T(0);
-      if constexpr (F == COV_ADD) {
-#pragma unroll 1
-        for (int c = 0; c < ncomp; ++c) kern_dx<T, DC>(kind, xi, xj, tab + c * DC, g, tab[MAX_COMP * DC + c], gx);
-      } else if constexpr (F == COV_SM) {
-        sm_dx<T, DC>(xi, xj, tab, tab + SM_MAX_MIX * DC, tab + 2 * SM_MAX_MIX * DC, ncomp, g, gx);
-      } else if constexpr (F == COV_PER) {
-        per_dx<T, DC>(xi, xj, tab, tab + DC, tab + 2 * DC, g, os, gx);
-      } else if constexpr (F == COV_LPER) {
-        lper_dx<T, DC>(xi, xj, tab, tab + DC, tab + 2 * DC, tab + 3 * DC, g, os, gx);
-      } else if constexpr (F == COV_RQ) {
-        rq_dx<T, DC>(xi, xj, tab, tab[DC], tab[DC + 1], g, os, gx);
-      }
+      dx_pair<T, F, DC>(kind, ncomp, xi, xj, tab, g, os, gx);
 #pragma unroll
       for (int k = 0; k < DC; ++k) sum[k] += take ? (double)gx[k] : 0.0;
     }
@@ -189,10 +128,7 @@ template <typename T>
 int input_grad_impl(const CovTable &t, const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK, const T *alpha, const T *X, int n, double *gX,
                     int q, void *stream) {
   // the diagonal of these depends on x, which the row sum over j != i does not cover
-  PLMC_REQUIRE(t.family != COV_SUM, "a heterogeneous sum (_sum) has no input gradient yet");
-  PLMC_REQUIRE(t.family != COV_DOT, "the dot-product family (_dot: linear, polynomial) has no input gradient yet: its diagonal depends on x");
-  PLMC_REQUIRE(!((t.family == COV_PLAIN || t.family == COV_ADD) && t.kind == K_SPLINE),
-               "the spline kernel has no input gradient yet: its diagonal depends on x");
+  if (const char *why = dx_refusal(t)) return fail(__func__, why);
   PLMC_REQUIRE_TABLE(t);
   const int kind = t.kind, d = t.d, ncomp = t.ncomp;
   const T *ell = (const T *)t.ell, *oscale = (const T *)t.oscale, *second = (const T *)t.second, *third = (const T *)t.third;

@@ -166,26 +166,33 @@ RQ = "rq"
 SUM = "sum"
 _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
         "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
-        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum"}
+        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
+        "plmc_posterior_dx": "plmc_posterior_dx_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
-         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper"}
+         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
+         "plmc_posterior_dx": "plmc_posterior_dx_lper"}
 _DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
         "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
-        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot"}
+        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
+        "plmc_posterior_dx": "plmc_posterior_dx_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
-       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq"}
+       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
+       "plmc_posterior_dx": "plmc_posterior_dx_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
-        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per"}
+        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per",
+        "plmc_posterior_dx": "plmc_posterior_dx_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
-       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm"}
+       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
+       "plmc_posterior_dx": "plmc_posterior_dx_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
         "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add",
-        "plmc_input_grad": "plmc_input_grad_add"}
+        "plmc_input_grad": "plmc_input_grad_add",
+        "plmc_posterior_dx": "plmc_posterior_dx_add"}
 
 
 def sum_kind(members):
@@ -777,7 +784,23 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     (n^3 / 3 flops, a workspace from the shared pool) and only remembers the key; the second call with the same key pays for the
     sweep with the inverse factor and the kept planes (2 n^3 / 3, 13 GB at n = 8192, q = 8; ~50 GB per latent at n = 44 484) that
     every later call then reuses -- a one-shot prediction neither slows down nor holds that memory.  "eager" builds it
-    on the first call, "off" never."""
+    on the first call, "off" never.
+    Xs.requires_grad (with gradients enabled): the moments come from the autograd node PosteriorMoments, which carries d mean / dXs and
+    d var / dXs; hyper-parameters, noise and training data stay constants.  Without it nothing below changes."""
+    if torch.is_grad_enabled() and Xs.requires_grad:
+        if full_cov:
+            raise NotImplementedError("full_cov=True together with test inputs that require a gradient: only the marginal moments "
+                                      "(mean, variance) are differentiable with respect to the test inputs -- detach them, or "
+                                      "predict with full_cov=False")
+        require_input_grad_kind(kind)
+        return PosteriorMoments.apply(Xs, kind, X, ell, oscale, noise, y, cache, key)
+    return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov, cache, key)
+
+
+def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, dx=None):
+    """exact_posterior's work.  dx = "mean" | "both": also the Jacobians of the marginal moments with respect to Xs, -> (mean, var, Jm,
+    Jv | None) (_posterior_jacobians); they need the inverse factor, so a miss builds the cache at once where there is one (a caller
+    who differentiates predictions will call again) and takes a pooled workspace WITH the inverse factor where there is none."""
     _hip.require_device(X, ell, noise, y, Xs)
     L = _hip.lib()
     dt, dev = y.dtype, y.device
@@ -797,13 +820,14 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
                and ws.naug >= 1 + ns)
     # build: eager mode; lazy mode on the second call with one key; or the cached state is the same and only its capacity is short
     same_state = cache is not None and cache.ws is not None and key is not None and cache.key == key
-    build = cache is not None and mode != "off" and not hit and (mode == "eager" or same_state or (key is not None and cache.seen == key))
+    build = cache is not None and mode != "off" and not hit and (mode == "eager" or same_state or (key is not None and cache.seen == key)
+                                                                 or dx is not None)
     if not hit and not build:
         if cache is not None and mode != "off":
             cache.drop()                                   # (a stale factorisation of another state goes now, not at the next build)
             cache.seen = key
             cache.misses += 1
-        ws = get_workspace(n, q, 1 + ns, dt, dev, False)
+        ws = get_workspace(n, q, 1 + ns, dt, dev, dx is not None)
         factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)
     else:
         if hit:
@@ -837,7 +861,110 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
         return mean, cov
     from .kernels import prior_diagonal
     var = prior_diagonal(kind, Xsc, osc, q, ellc) - vsq                # k(x*, x*) = 1 for the stationary kinds (additive: sum_g os_g)
+    if dx is not None:
+        return (mean, var) + _posterior_jacobians(kind, Xc, Xsc, ellc, osc, ws, dx == "both")
     return mean, var
+
+
+def _wtv_buffer(ws):
+    """[alpha | B] = W^T [z | V] of the eval-mode posterior (n_pad rows of naug_pad per latent), kept with the workspace and created on
+    first use: the variance part of the prediction's input derivative reads B = Khat^-1 K*^T from its columns 1 ..."""
+    buf = getattr(ws, "wtv", None)
+    if buf is None:
+        buf = ws.wtv = torch.empty(ws.q, ws.n_pad, ws.naug_pad, dtype=ws.dtype, device=ws.device)
+    return buf
+
+
+def _posterior_jacobians(kind, Xc, Xsc, ellc, osc, ws, variance):
+    """(Jm, Jv | None), (q, ns, d) float64 each: d mean / dXs and d var / dXs from a factorised workspace with the inverse factor whose
+    augmented columns hold [z | V] = U^-T [y | K*^T] (plmc_posterior_dx).  alpha = W^T z as the leave-one-out path takes
+    it.  variance: B = W^T V on the tile engine, in place on the strided views -- W is the lower triangle of its block of the factor
+    buffer (explicit zeros above the diagonal inside the diagonal blocks; PLMC_TRI_A_LOWER skips the blocks above, which are never
+    written), rows >= n of the augmented columns are zero and the padded part of W is the identity.  The product starts at the aligned
+    column n_pad, so its column 0 is W^T z and test point s stands in column 1 + s; the columns it covers beyond 1 + ns are zeros
+    (plmc_write_rhs clears the block)."""
+    L = _hip.lib()
+    dt, dev, q, n = ws.dtype, ws.device, ws.q, ws.n
+    ns, d = Xsc.shape
+    st = _hip.stream_ptr(dev)
+    L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
+    L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z), _hip.ptr(ws.alpha), q, st)
+    B = None
+    if variance:
+        buf = _wtv_buffer(ws)
+        ncols = int(L.cdll.plmc_pad(1 + ns))
+        L.call("plmc_gemm_tn_tri", dt, 0, 1, ws.n_pad, ncols, ws.n_pad, _hip.ptr(ws.W), ws.ldw, ws.strideW,
+               _hip.ptr(ws.A[:, :, ws.n_pad:]), ws.lda, ws.strideA, _hip.ptr(buf), buf.shape[2], buf.stride(0), q, st)     # 1: PLMC_TRI_A_LOWER
+        B = buf[:, :, 1:]
+    return posterior_dx(kind, Xc, Xsc, ellc, osc, ws.alpha, B, n=n)
+
+
+def posterior_dx_splits(n, ns, q):
+    """Ranges plmc_posterior_dx splits n training rows into for ns test points and q latents (one workgroup each per block of test points)."""
+    return int(_hip.lib().cdll.plmc_posterior_dx_splits(n, ns, q))
+
+
+def posterior_dx(kind, X, Xs, ell, oscale, alpha, B, n=None, Jv=None):
+    """plmc_posterior_dx on caller-owned buffers: X (n, d), Xs (ns, d), the kind's table (ell, oscale) as everywhere in this module,
+    alpha (q, n_pad) and B (q, rows >= n, ldb >= ns) | None, a view with unit stride along the test points -> (Jm, Jv), (q, ns, d) float64,
+        Jm[l, s, k] = sum_i alpha_li d k_l(xs_s, x_i) / d xs_s[k],   Jv[l, s, k] = -2 sum_i B_l[i, s] d k_l(xs_s, x_i) / d xs_s[k].
+    B None: Jv is handed back as given (None, or the caller's buffer untouched)."""
+    _hip.require_device(X, Xs, ell, alpha, B)
+    L = _hip.lib()
+    dt, dev = alpha.dtype, alpha.device
+    q, n_pad = alpha.shape
+    n = X.shape[0] if n is None else n
+    ns, d = Xs.shape
+    Xc, Xsc, ellc, osc, ac = (_contig(t, dt) for t in (X, Xs, ell, oscale, alpha))
+    Jm = torch.empty(q, ns, d, dtype=torch.float64, device=dev)
+    ldb = strideB = 0
+    if B is not None:
+        if B.stride(2) != 1:
+            raise ValueError("B must be contiguous along the test points")
+        ldb, strideB = B.stride(1), B.stride(0)
+        if Jv is None:
+            Jv = torch.empty(q, ns, d, dtype=torch.float64, device=dev)
+    nbytes = int(L.cdll.plmc_posterior_dx_partials_bytes(n, ns, d, q))
+    partials = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    _kernel_call(L, "plmc_posterior_dx", dt, (kind_code(kind), _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, d), ellc,
+                 (_hip.ptr(osc), _hip.ptr(ac), n_pad, _hip.ptr(B), ldb, strideB, _hip.ptr(Jm), _hip.ptr(Jv if B is not None else None),
+                  _hip.ptr(partials), q, _hip.stream_ptr(dev)))
+    return Jm, Jv
+
+
+class PosteriorMoments(torch.autograd.Function):
+    """(mean, var) of exact_posterior as a function of the test inputs Xs: forward is _exact_posterior, which also leaves the Jacobians
+    Jm, Jv (q, ns, d); test points do not interact in the marginal moments, so backward is element-wise,
+        gXs[s, k] = sum_l gmean[l, s] Jm[l, s, k] + gvar[l, s] Jv[l, s, k].
+    Hyper-parameters, noise and training data are constants of this node.  settings.predictive_variance_grad(False): Jv is not formed
+    and `var` carries no gradient.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, Xs, kind, X, ell, oscale, noise, y, cache, key):
+        variance = settings.predictive_variance_grad.on()
+        mean, var, Jm, Jv = _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both" if variance else "mean")
+        ctx.save_for_backward(Jm, Jv)
+        ctx.x_dtype = Xs.dtype
+        if not variance:
+            ctx.mark_non_differentiable(var)
+        return mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gmean, gvar):
+        Jm, Jv = ctx.saved_tensors
+        g = (gmean.to(torch.float64)[:, :, None] * Jm).sum(0)
+        if Jv is not None and gvar is not None:
+            g = g + (gvar.to(torch.float64)[:, :, None] * Jv).sum(0)
+        return (g.to(ctx.x_dtype),) + (None,) * 8
+
+
+def posterior_jacobians(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):
+    """(Jm, Jv), (q, ns, d) float64: d mean / dXs and d var / dXs of exact_posterior's marginal moments, read off the kernel's output --
+    no autograd graph."""
+    require_input_grad_kind(kind)
+    with torch.no_grad():
+        return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both")[2:]
 
 
 def trmm_ut(ws, n, Z, shift=None):
@@ -890,6 +1017,27 @@ def mix_posterior(mean_lat, var_lat, Ht, eps=0.0):
     L.call("plmc_mix_posterior", dt, _hip.ptr(ml), _hip.ptr(vl), _hip.ptr(H), q, ns, p, float(eps), _hip.ptr(mean), _hip.ptr(var),
            _hip.stream_ptr(dev))
     return mean, var
+
+
+class MixPosterior(torch.autograd.Function):
+    """mix_posterior as a function of the latent moments (the mixing is linear in them): the values are plmc_mix_posterior's, bit for
+    bit; backward is gmean Ht^T and gvar (Ht^2)^T.  Ht and eps are constants."""
+
+    @staticmethod
+    def forward(ctx, mean_lat, var_lat, Ht, eps):
+        mean, var = mix_posterior(mean_lat, var_lat, Ht, eps)
+        ctx.save_for_backward(Ht.detach().to(mean_lat.dtype))
+        if not ctx.needs_input_grad[1]:
+            ctx.mark_non_differentiable(var)
+        return mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gmean, gvar):
+        (Ht,) = ctx.saved_tensors
+        g_mean = (gmean @ Ht.T).T if ctx.needs_input_grad[0] else None
+        g_var = (gvar @ (Ht * Ht).T).T if ctx.needs_input_grad[1] and gvar is not None else None
+        return g_mean, g_var, None, None
 
 
 def dense_cross(kind, X1, X2, ell, oscale):

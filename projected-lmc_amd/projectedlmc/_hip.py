@@ -87,6 +87,14 @@ _TYPED = {
     "plmc_input_grad_lper": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_input_grad_sum": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "plmc_input_grad_dot": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
+    "plmc_posterior_dx": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_posterior_dx_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -125,6 +133,8 @@ _PLAIN = {
     "plmc_grad_scratch_bytes": ([_L, _I], _L),
     "plmc_grad_scratch_bytes_for": ([_L, _I, _I], _L),
     "plmc_grad_partials_bytes": ([_L, _I], _L),
+    "plmc_posterior_dx_splits": ([_I, _I, _I], _I),
+    "plmc_posterior_dx_partials_bytes": ([_I, _I, _I, _I], _L),
     "plmc_lmc_grad_len": ([_I, _I, _I], _L),
     "plmc_lmc_grad_scratch_bytes": ([_L, _I, _I, _I], _L),
     "plmc_prof_enable": ([_I], _I),

@@ -305,6 +305,18 @@ class ExactGPModel(ExactGP):
         with torch.no_grad():
             return self.input_transform(x)
 
+    def _test_features(self, x):
+        """The features of eval-mode test points.  Where x requires a gradient the graph is kept, with the transform's parameters and
+        buffers detached: the eval-mode posterior is a function of x alone, and a backward pass must not leave a partial gradient on
+        them.  Otherwise as _features(x, grad=False)."""
+        if not (torch.is_grad_enabled() and x.requires_grad):
+            return self._features(x, grad=False)
+        if self.input_transform is None:
+            return x
+        tf = self.input_transform
+        frozen = {k: v.detach() for k, v in list(tf.named_parameters()) + list(tf.named_buffers())}
+        return torch.func.functional_call(tf, frozen, (x,))
+
     def forward(self, x):
         x = self._features(x)
         mean_x = self.mean_module(x)
@@ -323,7 +335,7 @@ class ExactGPModel(ExactGP):
 
     def _posterior(self, x, full_cov=False):
         raw_tx = self.train_inputs[0]
-        tx, x = self._features(raw_tx, grad=False), self._features(x, grad=False)
+        tx, x = self._features(raw_tx, grad=False), self._test_features(x)
         lazy = self.covar_module(tx)
         lik = self.likelihood
         if self.batch_lik:
@@ -343,6 +355,39 @@ class ExactGPModel(ExactGP):
                                           cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_targets))
         mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
         return self._wrap_posterior(mean, v if full_cov else torch.diag_embed(v))
+
+    def _plain_test_inputs(self, x, what):
+        """predictive_gradients reads d / d(features seen by the kernel) off the engine: x must BE those features, and the prior mean
+        must not depend on it."""
+        if self.training:
+            raise RuntimeError("%s is an eval-mode method: call .eval() first" % what)
+        if x.ndimension() == 1:
+            x = x.unsqueeze(-1)
+        plain_mean = isinstance(self.mean_module, (_m.ZeroMean, _m.ConstantMean))
+        if self.input_transform is not None or self.covar_module.select(x) is not x or not plain_mean:
+            raise NotImplementedError("%s serves models without an input_transform, with a kernel on all dimensions and a zero or "
+                                      "constant mean; otherwise differentiate model(x) with x.requires_grad_()" % what)
+        if hasattr(self.covar_module, "inducing_points"):
+            raise NotImplementedError("%s: the inducing-point (SGPR) path has no gradient with respect to the inputs" % what)
+        return x.detach()
+
+    def predictive_gradients(self, x):
+        """(d mean / dx, d variance / dx) of the eval-mode posterior at x (n*, d), shaped (n*, d), or (n*, n_tasks, d) for a batch of
+        tasks: test points do not interact in the marginal moments, so this is the whole Jacobian.  Read off the engine's kernel
+        (plmc_posterior_dx); no autograd graph is built."""
+        x = self._plain_test_inputs(x, "predictive_gradients")
+        raw_tx = self.train_inputs[0]
+        lazy = self.covar_module(raw_tx)
+        lik = self.likelihood
+        noise = lik.noise.reshape(-1) if self.batch_lik else torch.diagonal(lik.task_noise_matrix()).reshape(-1)
+        resid = self._latent_targets() - self.mean_module(raw_tx).reshape(self.n_tasks, -1)
+        Jm, Jv = _engine.posterior_jacobians(lazy.kind, lazy.x1, lazy.ell.detach(), None if lazy.oscale is None else lazy.oscale.detach(),
+                                             noise.detach().to(lazy.ell.dtype), resid.detach(), x, cache=self._prediction_cache(),
+                                             key=_engine.model_state_key(self, raw_tx, self.train_targets))
+        Jm, Jv = Jm.to(x.dtype), Jv.to(x.dtype)
+        if self.n_tasks == 1 and self.train_targets.dim() == 1:
+            return Jm[0], Jv[0]
+        return Jm.transpose(0, 1), Jv.transpose(0, 1)
 
     def _wrap_posterior(self, mean, cov):
         if not self.batch_lik and self.n_tasks > 1:

@@ -291,9 +291,12 @@ class ProjectedGPModel(ExactGPModel):
 
     def _latent_posterior_body(self, x, full_cov=False):
         raw_tx = self.train_inputs[0]
-        tx, x = self._features(raw_tx, grad=False), self._features(x, grad=False)
+        tx, x = self._features(raw_tx, grad=False), self._test_features(x)
         lazy = self.covar_module(tx)
         ytil = self.project_data(self.train_y).detach()
+        if self.latent_ids is not None and torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("the latent-sharded ProjectedGPModel (latent_shard / latent_ids) has no gradient with respect to "
+                                      "the test inputs: its prediction all-reduces the ranks' partial sums -- detach x")
         if hasattr(lazy, "log_prob_batch"):                    # SGPR latents (n_inducing_points)
             with torch.no_grad():
                 noisy = lazy.add_noise(self.projected_noise().detach().to(lazy.ell.dtype))
@@ -342,9 +345,30 @@ class ProjectedGPModel(ExactGPModel):
             parallel.all_reduce_sum(buf)
             mean, var = buf[0], buf[1] + self.eps
             return MultitaskMultivariateNormal(mean, _DiagonalTaskCovariance(var))
-        mean, var = _engine.mix_posterior(mean_lat, v_diag, Ht, self.eps)
+        if mean_lat.requires_grad:
+            # differentiable test inputs: the same values through the mixing's autograd node; `var` carries its graph through
+            # KroneckerSumCovariance(diag=var) to .variance, .stddev and confidence_region()
+            mean, var = _engine.MixPosterior.apply(mean_lat, v_diag, Ht, self.eps)
+        else:
+            mean, var = _engine.mix_posterior(mean_lat, v_diag, Ht, self.eps)
         cov = KroneckerSumCovariance(Ht, cov=v if full_cov else None, var=None if full_cov else v, eps=self.eps, diag=var)
         return MultitaskMultivariateNormal(mean, cov)
+
+
+    def predictive_gradients(self, x):
+        """(d mean / dx, d variance / dx) of the task-space posterior at x (n*, d), each (n*, p, d): the latent Jacobians of the engine's
+        kernel (plmc_posterior_dx) mixed with H, d mean_t = sum_i H_it Jm_i, d var_t = sum_i H_it^2 Jv_i.  No autograd graph is built."""
+        x = self._plain_test_inputs(x, "predictive_gradients")
+        if self.latent_ids is not None:
+            raise NotImplementedError("predictive_gradients: the latent-sharded ProjectedGPModel (latent_shard / latent_ids) is not served")
+        with parametrize.cached(), torch.no_grad():
+            raw_tx = self.train_inputs[0]
+            lazy = self.covar_module(raw_tx)
+            ytil = self.project_data(self.train_y)
+            Jm, Jv = _engine.posterior_jacobians(lazy.kind, lazy.x1, lazy.ell, lazy.oscale, self.projected_noise().to(lazy.ell.dtype), ytil, x,
+                                                 cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_y))
+            Ht = self.lmc_coefficients().to(torch.float64)
+            return (torch.einsum("qt,qsk->stk", Ht, Jm).to(x.dtype), torch.einsum("qt,qsk->stk", Ht * Ht, Jv).to(x.dtype))
 
 
 class _DiagonalTaskCovariance:

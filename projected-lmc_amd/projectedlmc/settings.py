@@ -90,3 +90,16 @@ class prediction_cache(_Value):
     @classmethod
     def value(cls):
         return cls._stack[-1]
+
+
+class predictive_variance_grad(_Value):
+    """predictive_variance_grad(True | False): whether an eval-mode prediction at test inputs that require a gradient carries
+    d var / d x* as well as d mean / d x*.  The variance part needs B = Khat^-1 K*^T = W^T V, a product of q n^2 n* / 2
+    multiply-adds -- about what the cached forward substitution itself costs; the mean part needs alpha = Khat^-1 y only.  False
+    (mean-only work: sensitivities, inversion of the mean): the product is skipped and `variance` comes back without a gradient
+    to x."""
+    _stack = [True]
+
+    @classmethod
+    def on(cls):
+        return cls._stack[-1]
