@@ -194,14 +194,18 @@ int plmc_potrs_aug_kept_f64(double *A, int64_t n_pad, int64_t lda, int naug, int
 
 /*
  * Gather augmented column c of every latent into a contiguous vector z (q x n_pad) and return
- * quad[latent] = sum z^2 in double (the inv_quad term of MVN.log_prob, :1201).
+ * quad[latent] = sum z^2 in double (the inv_quad term of MVN.log_prob, :1201).  All n_pad rows are copied; the sum is carried
+ * in fp64.  Refused before anything is launched: a null pointer, q < 1, n_pad not a positive multiple of plmc_block(),
+ * lda < n_pad, c < 0 or n_pad + c >= lda.
  */
 int plmc_extract_col_f32(const float *A, int64_t n_pad, int64_t lda, int64_t strideA, int c,
                          float *z, double *quad, int q, void *stream);
 int plmc_extract_col_f64(const double *A, int64_t n_pad, int64_t lda, int64_t strideA, int c,
                          double *z, double *quad, int q, void *stream);
 
-/* alpha = W^T z = Khat^-1 y  (q x n_pad).  d logp / d y = -alpha. */
+/* alpha = W^T z = Khat^-1 y  (q x n_pad).  d logp / d y = -alpha.  Only the tiles of W on and below the block diagonal are read
+ * (16-byte vector loads); each sum is carried in fp64 and rounded once.  Refused before anything is launched: a null pointer, q < 1,
+ * n_pad not a positive multiple of plmc_block(), ldw < n_pad, W not 16-byte aligned, ldw or strideW not a multiple of 16 bytes. */
 int plmc_wt_matvec_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, const float *z,
                        float *alpha, int q, void *stream);
 int plmc_wt_matvec_f64(const double *W, int64_t n_pad, int64_t ldw, int64_t strideW, const double *z,
@@ -235,7 +239,11 @@ int plmc_trmm_ut_f64(const double *A, int64_t n_pad, int64_t lda, int64_t stride
 /*
  * Batched "TN" product on the tile engine:  C[b] (=, +=, -=) A[b]^T B[b]  with A: K x M and B: K x N, both stored
  * K-major (row index = contraction index), C: M x N; mode 0 store / 1 add / 2 subtract.  M, N multiples of plmc_block(),
- * K a multiple of 16 (callers pad with zeros), 16-byte aligned pointers / strides.  Replaces the torch.matmul (rocBLAS)
+ * K a multiple of 16 (callers pad with zeros), 16-byte aligned pointers / leading dimensions / strides, lda >= M, ldb >= N,
+ * ldc >= N.  strideA or strideB may be 0 (one operand shared by the batch); with batch > 1 the members of C must not share
+ * elements: |strideC| >= (M - 1) ldc + N, anything else is refused before the launch like every other argument error.  Exactly
+ * the M x N window of every C[b] is written.  Per element |C - exact| <= (K + 4) u (sum_k |A_ki| |B_kj| + |C0_ij|), u = 2^-24 / 2^-53,
+ * the C0 term in modes 1 and 2 (tests/_gemm_ref.py).  Replaces the torch.matmul (rocBLAS)
  * calls of the Cholesky adjoint of the inducing-point interpolation (VariationalMultitaskGPModel :672-683, SGPR :302-303).
  */
 int plmc_gemm_tn_f32(int mode, int M, int N, int K, const float *A, int64_t lda, int64_t strideA, const float *B,
@@ -249,7 +257,9 @@ int plmc_gemm_tn_f64(int mode, int M, int N, int K, const double *A, int64_t lda
  *   PLMC_TRI_A_LOWER  A[k][i] = 0 for k < 128 (i / 128)        PLMC_TRI_B_LOWER  B[k][j] = 0 for k < 128 (j / 128)
  *   PLMC_TRI_A_UPPER  A[k][i] = 0 for k >= 128 (i / 128 + 1)
  *   PLMC_TRI_C_LOWER  only tiles with i / 128 >= j / 128 are computed; the others are left untouched, or, with PLMC_TRI_C_ZERO
- *                     as well (mode 0 only), written as zeros. */
+ *                     as well (mode 0 only), written as zeros.
+ * The skipped range of a declared-zero block is never loaded: what stands there (the never-written W tiles above the block
+ * diagonal of a factor buffer, NaN included) does not reach C.  tests/test_gpu_gemm_tn.py pins this. */
 #define PLMC_TRI_A_LOWER 1
 #define PLMC_TRI_B_LOWER 2
 #define PLMC_TRI_A_UPPER 4
@@ -269,7 +279,12 @@ int plmc_gemm_tn_tri_f64(int mode, int tri, int M, int N, int K, const double *A
  * plmc_mix_posterior: task-space moments of :1144 / :1152, mean[s][t] = sum_i mean_lat[i][s] Ht[i][t],
  *   var[s][t] = sum_i var_lat[i][s] Ht[i][t]^2 + eps.  mean_lat, var_lat: q x ns; Ht: q x p; outputs ns x p.  With latent
  *   sharding a rank passes its local latents (q = their number) and eps = 0, and adds eps after the all-reduce.
- * Both HBM-bound; sums carried in fp64.
+ * Both HBM-bound; sums carried in fp64 and rounded once: |got - exact| <= u |exact| + (L + 4) 2^-53 sum |terms| for a sum of L terms
+ * (tests/_reduce_ref.py).
+ * plmc_posterior_moments loads the augmented columns as 16-byte vectors: A 16-byte aligned, lda and strideA multiples of 16 bytes,
+ *   and lda >= n_pad + (1 + ns rounded up to the 16-byte vector: 4 fp32 / 2 fp64 elements) -- columns n_pad + 1 + ns up to that
+ *   boundary are loaded and not used.  n_pad a positive multiple of plmc_block(), ns >= 1, q >= 1.  Anything else is refused before
+ *   the launch.
  */
 int plmc_posterior_moments_f32(const float *A, int64_t n_pad, int64_t lda, int64_t strideA, int ns, float *mean,
                                float *vsq, int q, void *stream);
@@ -283,7 +298,9 @@ int plmc_mix_posterior_f64(const double *mean_lat, const double *var_lat, const 
 /*
  * kinv_diag = diag(Khat^-1) = column sums of squares of W (q x n_pad): the leave-one-out variances
  * sigma2_i = 1 / [Khat^-1]_ii of `MultitaskGPModel.compute_loo` (:642-656) on the dense (n p) x (n p) system, where
- * the fused gradient kernel (single ARD kernel per matrix) does not apply.  HBM-bound, reads W once.
+ * the fused gradient kernel (single ARD kernel per matrix) does not apply.  HBM-bound, reads W once (the tiles on and below the
+ * block diagonal, 16-byte vector loads), sums carried in fp64.  Refused before anything is launched: a null pointer, q < 1, n_pad
+ * not a positive multiple of plmc_block(), ldw < n_pad, W not 16-byte aligned, ldw or strideW not a multiple of 16 bytes.
  */
 int plmc_w_diag_f32(const float *W, int64_t n_pad, int64_t ldw, int64_t strideW, float *kinv_diag, int q,
                     void *stream);

@@ -51,6 +51,9 @@ int gemm_tn_impl(int mode, int M, int N, int K, const T *A, int64_t lda, int64_t
   PLMC_REQUIRE(lda >= M && ldb >= N && ldc >= N && lda % EPV == 0 && ldb % EPV == 0 && ldc % EPV == 0, "leading dimensions");
   PLMC_REQUIRE(aligned16(A) && aligned16(B) && aligned16(C) && strideA % EPV == 0 && strideB % EPV == 0 && strideC % EPV == 0,
                "16-byte alignment");
+  // two batch members must not write the same elements of C (the tiles of one launch run in any order; plmc_trmm_ut refuses the same)
+  PLMC_REQUIRE(batch == 1 || (strideC < 0 ? -strideC : strideC) >= (int64_t)(M - 1) * ldc + N,
+               "batch stride of C: two batch members would share elements (|strideC| >= (M - 1) ldc + N)");
   const dim3 grid(N / NB, M / NB, batch);
   hipStream_t st = (hipStream_t)stream;
   if (mode == 0) hipLaunchKernelGGL((k_gemm_tn<T, WB_STORE>), grid, dim3(NTHREADS), 0, st, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, K, tri);

@@ -92,7 +92,12 @@ __global__ __launch_bounds__(NTHREADS) void k_mix_posterior(const T *__restrict_
 template <typename T>
 int posterior_moments_impl(const T *A, int64_t n_pad, int64_t lda, int64_t strideA, int ns, T *mean, T *vsq, int q, void *stream) {
   PLMC_REQUIRE(A && mean && vsq, "null pointer");
-  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ns > 0 && q > 0 && lda >= n_pad + 1 + ns, "bad sizes (lda must hold the 1 + ns augmented columns)");
+  constexpr int EPV = Traits<T>::EPV;
+  // the kernel loads whole 16-byte vectors at every augmented column c0 < 1 + ns, c0 a multiple of EPV: the row must hold the 1 + ns
+  // columns rounded up to the vector, and every vector must be aligned
+  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && ns > 0 && q > 0 && lda >= n_pad + ((int64_t)1 + ns + EPV - 1) / EPV * EPV,
+               "bad sizes (lda must hold the 1 + ns augmented columns rounded up to a 16-byte vector)");
+  PLMC_REQUIRE(aligned16(A) && lda % EPV == 0 && strideA % EPV == 0, "16-byte alignment of A, lda and strideA");
   const double bytes = (double)q * n_pad * (1.0 + ns) * sizeof(T);
   ProfScope ps(PK_POST, (hipStream_t)stream, 0.0, bytes);
   constexpr int CPW = 16 * Traits<T>::EPV;                      // augmented columns per workgroup

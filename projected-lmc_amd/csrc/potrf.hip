@@ -1446,6 +1446,7 @@ template <typename T>
 int extract_col_impl(const T *A, int64_t n_pad, int64_t lda, int64_t strideA, int c, T *z, double *quad, int q,
                      void *stream) {
   PLMC_REQUIRE(A && z && quad, "null pointer");
+  PLMC_REQUIRE(q > 0 && n_pad > 0 && n_pad % NB == 0 && lda >= n_pad, "q > 0, n_pad a positive multiple of NB, lda >= n_pad");
   PLMC_REQUIRE(c >= 0 && n_pad + c < lda, "column outside the augmented block");
   ProfScope ps(PK_EXTRACT, (hipStream_t)stream, 0.0, q * 2.0 * n_pad * sizeof(T));
   hipLaunchKernelGGL(k_extract_col<T>, dim3(q), dim3(NTHREADS), 0, (hipStream_t)stream, A, n_pad, lda, strideA, c, z,
@@ -1457,7 +1458,8 @@ template <typename T>
 int wt_matvec_impl(const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *z, T *alpha, int q,
                    void *stream) {
   PLMC_REQUIRE(W && z && alpha, "null pointer");
-  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0, "n_pad must be a multiple of NB");
+  PLMC_REQUIRE(q > 0 && n_pad > 0 && n_pad % NB == 0 && ldw >= n_pad, "q > 0, n_pad a positive multiple of NB, ldw >= n_pad");
+  PLMC_REQUIRE(aligned16(W) && ldw % Traits<T>::EPV == 0 && strideW % Traits<T>::EPV == 0, "16-byte alignment of W, ldw and strideW");
   ProfScope ps(PK_WTMV, (hipStream_t)stream, q * (double)n_pad * n_pad, q * ((double)n_pad * n_pad / 2) * sizeof(T));
   if ((int64_t)q * (n_pad / NB) < 128)                  // a shard of one latent: 32-column workgroups (same sums, four times the workgroups)
     hipLaunchKernelGGL((k_wt_matvec<T, 32>), dim3((unsigned)(n_pad / 32), q), dim3(WTMV_NT / 4), 0, (hipStream_t)stream, W, n_pad, ldw, strideW, z,
@@ -1471,7 +1473,8 @@ int wt_matvec_impl(const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, cons
 template <typename T>
 int w_diag_impl(const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, T *kinv_diag, int q, void *stream) {
   PLMC_REQUIRE(W && kinv_diag, "null pointer");
-  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && q > 0 && aligned16(W), "n_pad must be a multiple of NB");
+  PLMC_REQUIRE(q > 0 && n_pad > 0 && n_pad % NB == 0 && ldw >= n_pad, "q > 0, n_pad a positive multiple of NB, ldw >= n_pad");
+  PLMC_REQUIRE(aligned16(W) && ldw % Traits<T>::EPV == 0 && strideW % Traits<T>::EPV == 0, "16-byte alignment of W, ldw and strideW");
   ProfScope ps(PK_WTMV, (hipStream_t)stream, q * (double)n_pad * n_pad, q * ((double)n_pad * n_pad / 2) * sizeof(T));
   hipLaunchKernelGGL(k_w_diag<T>, dim3((unsigned)(n_pad / NB), q), dim3(WTMV_NT), 0, (hipStream_t)stream, W, n_pad, ldw, strideW,
                      kinv_diag);
