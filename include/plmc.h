@@ -961,6 +961,79 @@ int plmc_posterior_dx_dot_f64(const double *X, int n, const double *Xs, int ns, 
                               *Jv, void *partials, int q, void *stream);
 
 /*
+ * Products with a cross-covariance that is never written, for q latents on the training inputs X (n x d), the test inputs
+ * Xs (ns x d) and r <= plmc_cross_matvec_max_cols() (8) columns V per latent:
+ *     Out[lat][s][c] = sum_{i < n} k_lat(xs_s, x_i) V[lat][i][c]                      (Out: q x ns x r of the element type, contiguous)
+ * k_lat is the noise-free value plmc_assemble_cross* writes for the same table arguments: the same value functions with the accurate
+ * transcendental forms, the output scale included (oscale == NULL: 1), PLMC_SPLINE accepted by the plain entry point.  The posterior mean
+ * at ns points is this with V = alpha = Khat^-1 y, at O(n ns) instead of a sweep over ns augmented columns; a pathwise posterior draw is
+ * this with V = Khat^-1 (y - f_prior(X) - eps) beside plmc_rff_matvec.
+ *   V: row i a training point, ldv >= r elements between rows, strideV between latents.  alpha (q x n_pad) is r = 1, ldv = 1,
+ *   strideV = n_pad; the [alpha | B] rows the W^T product leaves are taken as they are.  No row of V or X at or beyond n and no column of V
+ *   at or beyond r is read; those may hold anything.  Nothing outside Out[.][< ns][< r] is written.
+ *   The value of a pair is of the element type; its products with V and the sums are fp64 in a fixed order without atomics (two calls give
+ *   the same bits), rounded once.  Per element, u = 2^-24 / 2^-53 and b_F the family's bound on one value of plmc_assemble_cross*:
+ *       |Out - exact| <= sum_i b_F |V_ic|  +  u |exact|  +  (n + 4) 2^-53 sum_i |k_i V_ic|.
+ *   With few test points the training rows are split into plmc_cross_matvec_splits(n, ns, q) ranges, one workgroup each per block of 64
+ *   test points and latent, a function of (n, ns, q) alone; their fp64 partial sums go through `partials`,
+ *   plmc_cross_matvec_partials_bytes(n, ns, r, q) bytes (0 with one range: `partials` may then be NULL), and are added in the order of the
+ *   ranges.  The order of the sums is a function of n alone -- segments of 256 rows (n > 16384: n / 64 rounded up to a multiple of 64),
+ *   each summed by its four waves in a fixed order, the segments added in order; `partials` holds one fp64 sum per segment -- so an
+ *   output element has the same bits whether or not the call splits and whatever other test points the call has.  q n ns kernel
+ *   evaluations; no private scratch.
+ * plmc_rff_matvec_*: the prior part of such a draw from m random Fourier features per latent,
+ *     Out[lat][s][c] = scale[lat] sum_{j < m} cos(2 pi (sum_k freq[lat][j][k] xs_s[k] + phase[lat][j])) Wt[lat][j][c]
+ * freq (q x m x d) and phase (q x m) IN REVOLUTIONS, Wt (q x m x r) and Out (q x ns x r) contiguous, scale (q) or NULL for 1, any m > 0,
+ * d <= plmc_max_dim().  The phase is reduced in revolutions term by term (a product with its FMA residual, t - rint(t) exact, the running
+ * sum folded back after every term), so one cosine is within 4 (d + 2) 2^-24 (fp32; 2^-53 for fp64) of the exact one of the same inputs
+ * whatever the phase is, up to 2^18 revolutions per term.  Same skeleton, split (plmc_cross_matvec_splits(m, ns, q),
+ * plmc_cross_matvec_partials_bytes(m, ns, r, q)), fixed-order fp64 sums and refusals.
+ * Bad arguments (a null pointer, n, ns, r or q < 1, r over the cap, ldv < r, strideV < (n - 1) ldv + r with q > 1, the family's limits,
+ * `partials` missing when the call splits) fail through plmc_last_error() before anything is launched.
+ */
+int     plmc_cross_matvec_max_cols(void);
+int     plmc_cross_matvec_splits(int n, int ns, int q);
+int64_t plmc_cross_matvec_partials_bytes(int n, int ns, int r, int q);
+int plmc_cross_matvec_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *oscale, const float *V,
+                          int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *oscale, const double *V,
+                          int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell, const float *oscale, const
+                              float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell, const double *oscale,
+                              const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means, const float
+                             *weights, const float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means, const
+                             double *weights, const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *oscale, const
+                              float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period, const double *oscale,
+                              const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_rq_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *shape, const float *oscale, const
+                             float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_rq_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *shape, const double *oscale,
+                             const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_lper_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *rbf_ell,
+                               const float *oscale, const float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void
+                               *stream);
+int plmc_cross_matvec_lper_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period, const double
+                               *rbf_ell, const double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int
+                               q, void *stream);
+int plmc_cross_matvec_sum_f32(const float *X, int n, const float *Xs, int ns, int d, int ncomp, const int *fam, const float *table, const float
+                              *oscale, const float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_sum_f64(const double *X, int n, const double *Xs, int ns, int d, int ncomp, const int *fam, const double *table, const double
+                              *oscale, const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_dot_f32(const float *X, int n, const float *Xs, int ns, int d, const float *var, const float *offset, int power, const float
+                              *oscale, const float *V, int64_t ldv, int64_t strideV, int r, float *Out, void *partials, int q, void *stream);
+int plmc_cross_matvec_dot_f64(const double *X, int n, const double *Xs, int ns, int d, const double *var, const double *offset, int power, const
+                              double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, double *Out, void *partials, int q, void *stream);
+int plmc_rff_matvec_f32(const float *freq, const float *phase, int m, const float *Xs, int ns, int d, const float *Wt, int r, const float *scale,
+                        float *Out, void *partials, int q, void *stream);
+int plmc_rff_matvec_f64(const double *freq, const double *phase, int m, const double *Xs, int ns, int d, const double *Wt, int r, const double *scale,
+                        double *Out, void *partials, int q, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

@@ -21,3 +21,4 @@ from .sgpr import InducingPointKernel  # noqa: F401
 from . import variational  # noqa: F401
 from .variational import (VariationalMultitaskGPModel, CustomLMCVariationalStrategy, VariationalELBO,  # noqa: F401
                           CholeskyVariationalDistribution, VariationalStrategy, LMCVariationalStrategy)
+from .paths import PosteriorPaths  # noqa: F401

@@ -167,32 +167,32 @@ SUM = "sum"
 _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
         "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
         "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
-        "plmc_posterior_dx": "plmc_posterior_dx_sum"}
+        "plmc_posterior_dx": "plmc_posterior_dx_sum", "plmc_cross_matvec": "plmc_cross_matvec_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
          "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
-         "plmc_posterior_dx": "plmc_posterior_dx_lper"}
+         "plmc_posterior_dx": "plmc_posterior_dx_lper", "plmc_cross_matvec": "plmc_cross_matvec_lper"}
 _DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
         "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
         "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
-        "plmc_posterior_dx": "plmc_posterior_dx_dot"}
+        "plmc_posterior_dx": "plmc_posterior_dx_dot", "plmc_cross_matvec": "plmc_cross_matvec_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
        "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
-       "plmc_posterior_dx": "plmc_posterior_dx_rq"}
+       "plmc_posterior_dx": "plmc_posterior_dx_rq", "plmc_cross_matvec": "plmc_cross_matvec_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
         "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per",
-        "plmc_posterior_dx": "plmc_posterior_dx_per"}
+        "plmc_posterior_dx": "plmc_posterior_dx_per", "plmc_cross_matvec": "plmc_cross_matvec_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
        "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
-       "plmc_posterior_dx": "plmc_posterior_dx_sm"}
+       "plmc_posterior_dx": "plmc_posterior_dx_sm", "plmc_cross_matvec": "plmc_cross_matvec_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
         "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add",
         "plmc_input_grad": "plmc_input_grad_add",
-        "plmc_posterior_dx": "plmc_posterior_dx_add"}
+        "plmc_posterior_dx": "plmc_posterior_dx_add", "plmc_cross_matvec": "plmc_cross_matvec_add"}
 
 
 def sum_kind(members):
@@ -866,6 +866,95 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
     return mean, var
 
 
+def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False):
+    """A factorised workspace WITH the inverse factor whose first augmented columns hold U^-T rhs, rhs (q, P, n): the model's cached one
+    where its key matches and it has room for P columns (the new columns are written and forward-substituted, plmc_write_rhs +
+    plmc_potrs_aug[_kept]); else a new one, kept in `cache` by the rule of exact_posterior (settings.prediction_cache: eager, the second
+    call with one key in lazy mode, or a cached state that is the same and only short of columns; always=True: unless the mode is "off")
+    and otherwise taken from the shared pool."""
+    L = _hip.lib()
+    dt, dev = rhs.dtype, rhs.device
+    q, P, n = rhs.shape
+    st = _hip.stream_ptr(dev)
+    mode = settings.prediction_cache.value() if cache is not None else "off"
+    if key is not None and (is_sum(kind) or is_dot(kind)):
+        key = key + (kind,)
+    ws = cache.ws if cache is not None and mode != "off" else None
+    same_state = ws is not None and key is not None and cache.key == key
+    if same_state and ws.dtype == dt and ws.device == dev and ws.n == n and ws.q == q and ws.naug >= P and ws.with_inverse:
+        cache.hits += 1
+        L.call("plmc_write_rhs", dt, _hip.ptr(rhs), P, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
+        if ws.keep_planes:
+            L.call("plmc_potrs_aug_kept", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, P, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q, _hip.ptr(nzc), st)
+        else:
+            L.call("plmc_potrs_aug", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, P, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q, st)
+        ws.alpha_key = None
+        return ws
+    build = cache is not None and mode != "off" and (always or mode == "eager" or same_state or (key is not None and cache.seen == key))
+    if cache is not None and mode != "off":
+        cache.misses += 1
+        cache.drop()
+    if build:
+        ws = Workspace(n, q, P, dt, dev, with_inverse=True, keep_planes=True)
+    else:
+        if cache is not None and mode != "off":
+            cache.seen = key
+        ws = get_workspace(n, q, P, dt, dev, True)
+    factorize_checked(kind, Xc, ellc, osc, nzc, rhs, ws)
+    ws.alpha_key = None
+    if build:
+        cache.key, cache.ws = key, ws
+    return ws
+
+
+def exact_posterior_mean(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):
+    """Posterior mean of q zero-mean GPs at Xs, (q, ns), as K(Xs, X) alpha with alpha = Khat^-1 y from a factorisation of [Khat | y]
+    (settings.skip_posterior_variances): no augmented columns for the test points, so ns is not bounded by a workspace, and K(Xs, X) is
+    never written (cross_matvec).  alpha is kept with the model's cached workspace (_cached_factor) and reused while the key is unchanged."""
+    _hip.require_device(X, ell, noise, y, Xs)
+    L = _hip.lib()
+    dt, dev = y.dtype, y.device
+    q, n = y.shape
+    with torch.no_grad():
+        Xc, Xsc, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xs, ell, oscale, noise))
+        _check_kernel_shape(L, ellc, kind)
+        full_key = key + (kind,) if key is not None and (is_sum(kind) or is_dot(kind)) else key
+        ws = cache.ws if cache is not None and settings.prediction_cache.value() != "off" else None
+        ready = (ws is not None and full_key is not None and cache.key == full_key and getattr(ws, "alpha_key", None) == full_key
+                 and ws.dtype == dt and ws.device == dev and ws.n == n and ws.q == q)
+        if ready:
+            cache.hits += 1
+            alpha = ws.alpha_kept
+        else:
+            ws = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key)
+            st = _hip.stream_ptr(dev)
+            L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
+            L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z), _hip.ptr(ws.alpha), q, st)
+            alpha = ws.alpha
+            if cache is not None and cache.ws is ws:       # (ws.alpha itself is rewritten by the calls that differentiate predictions)
+                ws.alpha_kept, ws.alpha_key = ws.alpha.clone(), full_key
+        return cross_matvec(kind, Xsc, Xc, ellc, osc, alpha, n=n, ws=ws)
+
+
+def solve_cached(kind, X, ell, oscale, noise, rhs, cache=None, key=None):
+    """Khat^-1 rhs for q latents against the model's cached factor, rhs (q, P, n) -> (q, n, P) K-major: the columns are forward-substituted
+    in the factor buffer (_cached_factor; the cache is built if there is none) and multiplied by W^T on the tile engine as the
+    prediction's input derivative does it (_posterior_jacobians)."""
+    _hip.require_device(X, ell, noise, rhs)
+    L = _hip.lib()
+    dt, dev = rhs.dtype, rhs.device
+    q, P, n = rhs.shape
+    with torch.no_grad():
+        Xc, ellc, osc, nzc, rc = (_contig(t, dt) for t in (X, ell, oscale, noise, rhs))
+        _check_kernel_shape(L, ellc, kind)
+        ws = _cached_factor(kind, Xc, ellc, osc, nzc, rc, cache, key, always=True)
+        buf = _wtv_buffer(ws)
+        ncols = int(L.cdll.plmc_pad(P))
+        L.call("plmc_gemm_tn_tri", dt, 0, 1, ws.n_pad, ncols, ws.n_pad, _hip.ptr(ws.W), ws.ldw, ws.strideW,
+               _hip.ptr(ws.A[:, :, ws.n_pad:]), ws.lda, ws.strideA, _hip.ptr(buf), buf.shape[2], buf.stride(0), q, _hip.stream_ptr(dev))
+        return buf[:, :n, :P].clone()
+
+
 def _wtv_buffer(ws):
     """[alpha | B] = W^T [z | V] of the eval-mode posterior (n_pad rows of naug_pad per latent), kept with the workspace and created on
     first use: the variance part of the prediction's input derivative reads B = Khat^-1 K*^T from its columns 1 ..."""
@@ -930,6 +1019,87 @@ def posterior_dx(kind, X, Xs, ell, oscale, alpha, B, n=None, Jv=None):
                  (_hip.ptr(osc), _hip.ptr(ac), n_pad, _hip.ptr(B), ldb, strideB, _hip.ptr(Jm), _hip.ptr(Jv if B is not None else None),
                   _hip.ptr(partials), q, _hip.stream_ptr(dev)))
     return Jm, Jv
+
+
+def cross_matvec_splits(n, ns, q):
+    """Ranges plmc_cross_matvec / plmc_rff_matvec split n rows into for ns test points and q latents."""
+    return int(_hip.lib().cdll.plmc_cross_matvec_splits(n, ns, q))
+
+
+_cm_scratch = {}
+
+
+def _cross_matvec_scratch(nbytes, dev, ws=None):
+    """fp64 scratch of the range split: the caller's workspace lends its gradient partials when they are large enough; else one pooled
+    tensor per device, grown on demand.  Calls on one stream use it one after the other."""
+    if not nbytes:
+        return None
+    own = getattr(ws, "partials", None)
+    if own is not None and own.numel() * 8 >= nbytes:
+        return own
+    buf = _cm_scratch.get(dev.index)
+    if buf is None or buf.numel() * 8 < nbytes:
+        buf = _cm_scratch[dev.index] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    buf.record_stream(torch.cuda.current_stream(dev))
+    return buf
+
+
+def cross_matvec(kind, Xs, X, ell, oscale, V, n=None, ws=None):
+    """K(Xs, X) V without K(Xs, X) (plmc_cross_matvec): Xs (ns, d), X (n, d), the kind's table (ell, oscale) as everywhere
+    in this module, V (q, rows >= n) -- one column, e.g. alpha (q, n_pad) -- or (q, rows >= n, r) with unit stride along r (a view of
+    the [alpha | B] buffer is taken as it is) -> (q, ns) or (q, ns, r) of V's dtype,
+        out[l, s, c] = sum_{i < n} k_l(xs_s, x_i) V[l, i, c].
+    More columns than plmc_cross_matvec_max_cols() go in chunks.  ws: a workspace whose scratch may be borrowed.  Current stream."""
+    _hip.require_device(X, Xs, ell, V)
+    L = _hip.lib()
+    dt, dev = V.dtype, V.device
+    vec = V.dim() == 2
+    Vv = V.detach().unsqueeze(-1) if vec else V.detach()
+    if Vv.shape[2] > 1 and Vv.stride(2) != 1:
+        raise ValueError("V must be contiguous along its columns")
+    q, r = Vv.shape[0], Vv.shape[2]
+    n = X.shape[0] if n is None else n
+    ns, d = Xs.shape
+    Xc, Xsc, ellc, osc = (_contig(t, dt) for t in (X, Xs, ell, oscale))
+    _check_kernel_shape(L, ellc, kind)
+    ldv, strideV = Vv.stride(1), Vv.stride(0)
+    cap = int(L.cdll.plmc_cross_matvec_max_cols())
+    st = _hip.stream_ptr(dev)
+    out = torch.empty(q, ns, r, dtype=dt, device=dev)
+    for c0 in range(0, r, cap):
+        rc = min(cap, r - c0)
+        part = _cross_matvec_scratch(int(L.cdll.plmc_cross_matvec_partials_bytes(n, ns, rc, q)), dev, ws)
+        dst = out if rc == r else torch.empty(q, ns, rc, dtype=dt, device=dev)
+        _kernel_call(L, "plmc_cross_matvec", dt, (kind_code(kind), _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, d), ellc,
+                     (_hip.ptr(osc), _hip.ptr(Vv[:, :, c0:]), ldv, strideV, rc, _hip.ptr(dst), _hip.ptr(part), q, st))
+        if dst is not out:
+            out[:, :, c0:c0 + rc] = dst
+    return out[:, :, 0] if vec else out
+
+
+def rff_matvec(freq, phase, Xs, Wt, scale=None):
+    """The prior part of a pathwise draw (plmc_rff_matvec): freq (q, m, d) and phase (q, m) in revolutions, Xs (ns, d), Wt (q, m, r),
+    scale (q) | None -> (q, ns, r),  out[l, s, c] = scale_l sum_j cos(2 pi (freq_lj . xs_s + phase_lj)) Wt[l, j, c].  Wider Wt than
+    plmc_cross_matvec_max_cols() goes in chunks.  Current stream."""
+    _hip.require_device(freq, phase, Xs, Wt)
+    L = _hip.lib()
+    dt, dev = Wt.dtype, Wt.device
+    q, m, r = Wt.shape
+    ns, d = Xs.shape
+    fc, pc, Xsc, sc = (_contig(t, dt) for t in (freq, phase, Xs, scale))
+    cap = int(L.cdll.plmc_cross_matvec_max_cols())
+    st = _hip.stream_ptr(dev)
+    out = torch.empty(q, ns, r, dtype=dt, device=dev)
+    for c0 in range(0, r, cap):
+        rc = min(cap, r - c0)
+        part = _cross_matvec_scratch(int(L.cdll.plmc_cross_matvec_partials_bytes(m, ns, rc, q)), dev)
+        Wc = _contig(Wt[:, :, c0:c0 + rc])
+        dst = out if rc == r else torch.empty(q, ns, rc, dtype=dt, device=dev)
+        L.call("plmc_rff_matvec", dt, _hip.ptr(fc), _hip.ptr(pc), m, _hip.ptr(Xsc), ns, d, _hip.ptr(Wc), rc, _hip.ptr(sc), _hip.ptr(dst),
+               _hip.ptr(part), q, st)
+        if dst is not out:
+            out[:, :, c0:c0 + rc] = dst
+    return out
 
 
 class PosteriorMoments(torch.autograd.Function):

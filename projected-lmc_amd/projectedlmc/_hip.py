@@ -95,6 +95,15 @@ _TYPED = {
     "plmc_posterior_dx_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
     "plmc_posterior_dx_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
     "plmc_posterior_dx_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_cross_matvec_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _I, _P, _P, _I, _P],
+    "plmc_rff_matvec": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -135,6 +144,9 @@ _PLAIN = {
     "plmc_grad_partials_bytes": ([_L, _I], _L),
     "plmc_posterior_dx_splits": ([_I, _I, _I], _I),
     "plmc_posterior_dx_partials_bytes": ([_I, _I, _I, _I], _L),
+    "plmc_cross_matvec_max_cols": ([], _I),
+    "plmc_cross_matvec_splits": ([_I, _I, _I], _I),
+    "plmc_cross_matvec_partials_bytes": ([_I, _I, _I, _I], _L),
     "plmc_lmc_grad_len": ([_I, _I, _I], _L),
     "plmc_lmc_grad_scratch_bytes": ([_L, _I, _I, _I], _L),
     "plmc_prof_enable": ([_I], _I),

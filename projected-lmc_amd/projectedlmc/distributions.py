@@ -58,6 +58,29 @@ class KroneckerSumCovariance:
     to_dense = evaluate
 
 
+class ZeroCovariance:
+    """The covariance of a mean-only prediction (settings.skip_posterior_variances): exactly zero, never materialised unless asked.
+    `like`: a tensor with the batch shape and the event size of the distribution, (..., n)."""
+
+    def __init__(self, like):
+        self.like = like
+
+    @property
+    def shape(self):
+        return torch.Size([*self.like.shape, self.like.shape[-1]])
+
+    def __getitem__(self, idx):
+        return ZeroCovariance(self.like[idx])
+
+    def diagonal(self, *a, **k):
+        return torch.zeros_like(self.like)
+
+    def evaluate(self):
+        return torch.zeros(self.shape, dtype=self.like.dtype, device=self.like.device)
+
+    to_dense = evaluate
+
+
 class MultivariateNormal:
     def __init__(self, mean, covariance_matrix, validate_args=False):
         self.loc = mean

@@ -9,9 +9,10 @@ import weakref
 import torch
 
 from . import _engine
+from . import settings
 from . import kernels as _k
 from . import means as _m
-from .distributions import MultivariateNormal, MultitaskMultivariateNormal
+from .distributions import MultivariateNormal, MultitaskMultivariateNormal, ZeroCovariance
 from .likelihoods import GaussianLikelihood
 
 # model -> (input tensor, version, training input, version) already compared equal (kept outside the module's
@@ -111,6 +112,18 @@ def init_lmc_coefficients(train_y, n_latents, QR_form=False):
     if QR_form:
         return U, S
     return (U * S / (n_data - 1) ** 0.5).T
+
+
+def refuse_skip_variances(x, full_cov, model=None):
+    """settings.skip_posterior_variances serves the mean of the exact posterior at constant test inputs only."""
+    what = "settings.skip_posterior_variances(True) together with "
+    if model is not None:
+        raise NotImplementedError(what + model + ": the mean-only route serves the exact models")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError(what + "test inputs that require a gradient (x.requires_grad): the mean-only route carries no "
+                                  "derivative with respect to x -- detach x, or leave the setting off")
+    if full_cov:
+        raise NotImplementedError(what + "full_cov=True: there is no covariance to return")
 
 
 # ------------------------------------------------------------------------------- parametrisations
@@ -345,6 +358,14 @@ class ExactGPModel(ExactGP):
         prior_mean = self.mean_module(tx).reshape(self.n_tasks, -1)
         resid = self._latent_targets() - prior_mean
         xs = self.covar_module.select(x)
+        if settings.skip_posterior_variances.on():             # the mean alone, K(x*, X) alpha without K(x*, X)
+            refuse_skip_variances(x, full_cov, "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None)
+            mean = _engine.exact_posterior_mean(lazy.kind, lazy.x1, lazy.ell.detach(), None if lazy.oscale is None else lazy.oscale.detach(),
+                                                noise.detach().to(lazy.ell.dtype), resid.detach(), xs, cache=self._prediction_cache(),
+                                                key=_engine.model_state_key(self, raw_tx, self.train_targets))
+            with torch.no_grad():
+                mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
+            return self._wrap_posterior(mean, ZeroCovariance(mean))
         if hasattr(lazy, "log_prob_batch"):                    # SGPR predictive moments (sgpr.py)
             with torch.no_grad():
                 mean, v = lazy.add_noise(noise.detach().to(lazy.ell.dtype)).posterior(resid.detach(), xs)
@@ -355,6 +376,12 @@ class ExactGPModel(ExactGP):
                                           cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_targets))
         mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
         return self._wrap_posterior(mean, v if full_cov else torch.diag_embed(v))
+
+    def sample_paths(self, num_paths, num_features=1024, generator=None):
+        """num_paths draws of the posterior AS FUNCTIONS (pathwise conditioning, paths.PosteriorPaths): evaluable at any number of points
+        chosen later, consistent across calls, linear in n*.  Eval mode; the stationary kinds and their additive table."""
+        from .paths import sample_paths
+        return sample_paths(self, num_paths, num_features, generator)
 
     def _plain_test_inputs(self, x, what):
         """predictive_gradients reads d / d(features seen by the kernel) off the engine: x must BE those features, and the prior mean

@@ -334,6 +334,8 @@ class ProjectedGPModel(ExactGPModel):
         (projected_lmc.py:1133-1155).  By default only the latent variances are formed (what
         `.variance` / `.confidence_region()` need); full_cov=True keeps the n* x n* latent blocks.
         With latent sharding the partial sums are all-reduced (the one cross-latent reduction)."""
+        if settings.skip_posterior_variances.on():
+            return self._mean_only_posterior(x, full_cov)
         mean_lat, v = self._latent_posterior(x, full_cov=full_cov)
         Ht = self.lmc_coefficients().detach()
         v_diag = v if not full_cov else torch.diagonal(v, dim1=-2, dim2=-1)
@@ -354,6 +356,25 @@ class ProjectedGPModel(ExactGPModel):
         cov = KroneckerSumCovariance(Ht, cov=v if full_cov else None, var=None if full_cov else v, eps=self.eps, diag=var)
         return MultitaskMultivariateNormal(mean, cov)
 
+
+    def _mean_only_posterior(self, x, full_cov):
+        """settings.skip_posterior_variances: the latent means K(x*, X) alpha (plmc_cross_matvec) mixed to tasks as _posterior mixes them;
+        the variance is exactly 0 (no eps either)."""
+        from .models import refuse_skip_variances
+        with parametrize.cached():
+            raw_tx = self.train_inputs[0]
+            lazy = self.covar_module(self._features(raw_tx, grad=False))
+            refuse_skip_variances(x, full_cov, "the latent-sharded ProjectedGPModel (latent_shard / latent_ids)" if self.latent_ids is not None
+                                  else "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None)
+            xs = self.covar_module.select(self._features(x, grad=False))
+            with torch.no_grad():
+                ytil = self.project_data(self.train_y)
+                mean_lat = _engine.exact_posterior_mean(lazy.kind, lazy.x1, lazy.ell, lazy.oscale, self.projected_noise().to(lazy.ell.dtype), ytil,
+                                                        xs, cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_y))
+                Ht = self.lmc_coefficients().detach()
+                mean, var = _engine.mix_posterior(mean_lat, torch.zeros_like(mean_lat), Ht, 0.0)
+        cov = KroneckerSumCovariance(Ht, var=torch.zeros_like(mean_lat), eps=0.0, diag=var)
+        return MultitaskMultivariateNormal(mean, cov)
 
     def predictive_gradients(self, x):
         """(d mean / dx, d variance / dx) of the task-space posterior at x (n*, d), each (n*, p, d): the latent Jacobians of the engine's

@@ -103,3 +103,20 @@ class predictive_variance_grad(_Value):
     @classmethod
     def on(cls):
         return cls._stack[-1]
+
+
+class skip_posterior_variances(_Value):
+    """skip_posterior_variances(True | False) [gpytorch-knowledge: same name; the covariance becomes zero].  Off by default.  When on, an
+    eval-mode ExactGPModel (without inducing points) or ProjectedGPModel call returns the usual distribution with its variance exactly 0
+    and its mean from K(x*, X) alpha, alpha = Khat^-1 (y - m(X)), formed without K(x*, X) (plmc_cross_matvec): O(n n*)
+    per call once alpha is cached, no augmented columns, so n* is not bounded by the workspace.  alpha lives in the model's prediction
+    cache under the same state key and prediction_cache rule as the factorisation.  Together with test inputs that require a gradient,
+    full_cov=True or the latent-sharded model it raises NotImplementedError."""
+    _stack = [False]
+
+    def __init__(self, state=True):
+        super().__init__(bool(state))
+
+    @classmethod
+    def on(cls):
+        return cls._stack[-1]

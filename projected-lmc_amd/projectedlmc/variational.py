@@ -279,6 +279,10 @@ class VariationalMultitaskGPModel(torch.nn.Module):
     def compute_latent_distrib(self, x, prior=False, **kwargs):
         return self.base_variational_strategy(x, **kwargs)
 
+    def sample_paths(self, num_paths, num_features=1024, generator=None):
+        raise NotImplementedError("sample_paths: the variational model (%s) is not served -- pathwise conditioning here needs the exact "
+                                  "factor of the training covariance" % type(self).__name__)
+
 
 class VariationalELBO(torch.nn.Module):
     """ELBO = (1/n) sum_points E_q[log p(y|f)] - beta * KL / num_data + sum(log priors) / num_data
