@@ -1034,6 +1034,84 @@ int plmc_rff_matvec_f64(const double *freq, const double *phase, int m, const do
                         double *Out, void *partials, int q, void *stream);
 
 /*
+ * Derivative of those products with respect to the test inputs, contracted with weights on the fly: what the gradient of
+ * a pathwise posterior draw f_c(x) needs, without a cross-covariance-sized buffer.  plmc_cross_matvec_dx*_*: arguments as the value's
+ * entry point of the same family, with `const T *G, double *Jx` in the place of `T *Out`,
+ *     Jx[lat][s][k] = sum_{i < n} w_si  d k_lat(xs_s, x_i) / d xs_s[k],      w_si = sum_{c < r} G[lat][s][c] V[lat][i][c]
+ * X (n x d) and Xs (ns x d) raw coordinates as plmc_posterior_dx_* takes them; V as above (ldv, strideV, r <= the cap); G (q x ns x r)
+ * contiguous, the upstream gradient of Out; G == NULL is allowed with r == 1 only and means w_si = V[lat][i][0], the Jacobian of that one
+ * column; Jx (q x ns x d) fp64 like Jm / Jv.  The unit derivative of a pair is evaluated once in the element type: the code and tables of
+ * plmc_posterior_dx_* (accurate forms, a test point on a training point gets nothing from that pair); w_si and every sum are fp64.
+ * Families: those of plmc_posterior_dx_*; the spline kind, the _sum and the _dot entry points are refused by name.
+ *   Summation order: the contract of the values above, not the looser one of plmc_posterior_dx_*.  w over the columns in order; the rows
+ *   in the same segments (256 rows; n > 16384: n / 64 rounded up to a multiple of 64), each summed by its four waves in a fixed order, the
+ *   segments added in order.  The ranges are those of the values: plmc_cross_matvec_dx_splits(n, ns, q) of them, whose fp64 sums -- one
+ *   per segment -- go through `partials`, plmc_cross_matvec_dx_partials_bytes(n, ns, d, q) bytes (0 with one range: `partials` may then be
+ *   NULL).  An element of Jx has the same bits whether or not the call splits, whichever lane owns its test point and however many test
+ *   points the call has; two calls give the same bits.  No atomics, no private scratch; nothing is read from rows >= n of X or V, columns
+ *   >= r or test points >= ns, nothing outside Jx[.][< ns][< d] is written.  q n ns kernel-derivative evaluations.
+ * plmc_rff_matvec_dx_*: the same for the prior part, arguments as plmc_rff_matvec_* with G in front of scale,
+ *     Jx[lat][s][k] = -2 pi scale[lat] sum_{j < m} sin(2 pi (sum_k' freq[lat][j][k'] xs_s[k'] + phase[lat][j])) freq[lat][j][k] w_sj,
+ *     w_sj = sum_{c < r} G[lat][s][c] Wt[lat][j][c]      (G == NULL, r == 1: Wt[lat][j][0])
+ * The phase is reduced in revolutions exactly as the value's; the sine is the accurate one of the element type, within 4 (d + 2) u of the
+ * exact one whatever the phase; its products with w_sj and freq are fp64.  Per element, u = 2^-24 / 2^-53:
+ *     |Jx - exact| <= |scale| 2 pi [4 (d + 2) u sum_j |f_jk| |w_sj|  +  (m + 4) 2^-53 sum_j |sin_j f_jk w_sj|].
+ * Bad arguments (a null pointer, n, ns, r or q < 1, r over the cap, ldv < r, strideV < (n - 1) ldv + r with q > 1, G == NULL with r > 1,
+ * the family's limits, a refused family, `partials` missing when the call splits) fail through plmc_last_error() before anything is launched.
+ */
+int     plmc_cross_matvec_dx_splits(int n, int ns, int q);
+int64_t plmc_cross_matvec_dx_partials_bytes(int n, int ns, int d, int q);
+int plmc_cross_matvec_dx_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *oscale, const float *V,
+                             int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *oscale,
+                             const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx, void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_add_f32(int kind, const float *X, int n, const float *Xs, int ns, int d, int ncomp, const float *ell, const float *oscale,
+                                 const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials, int q,
+                                 void *stream);
+int plmc_cross_matvec_dx_add_f64(int kind, const double *X, int n, const double *Xs, int ns, int d, int ncomp, const double *ell, const double *oscale,
+                                 const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx, void *partials, int q,
+                                 void *stream);
+int plmc_cross_matvec_dx_sm_f32(const float *X, int n, const float *Xs, int ns, int d, int nmix, const float *scales, const float *means,
+                                const float *weights, const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials,
+                                int q, void *stream);
+int plmc_cross_matvec_dx_sm_f64(const double *X, int n, const double *Xs, int ns, int d, int nmix, const double *scales, const double *means,
+                                const double *weights, const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx,
+                                void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_per_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *oscale,
+                                 const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials, int q,
+                                 void *stream);
+int plmc_cross_matvec_dx_per_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
+                                 const double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx,
+                                 void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_rq_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *shape, const float *oscale,
+                                const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_rq_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *shape, const double *oscale,
+                                const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx, void *partials, int q,
+                                void *stream);
+int plmc_cross_matvec_dx_lper_f32(const float *X, int n, const float *Xs, int ns, int d, const float *ell, const float *period, const float *rbf_ell,
+                                  const float *oscale, const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials,
+                                  int q, void *stream);
+int plmc_cross_matvec_dx_lper_f64(const double *X, int n, const double *Xs, int ns, int d, const double *ell, const double *period,
+                                  const double *rbf_ell, const double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, const double *G,
+                                  double *Jx, void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_sum_f32(const float *X, int n, const float *Xs, int ns, int d, int ncomp, const int *fam, const float *table,
+                                 const float *oscale, const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials,
+                                 int q, void *stream);
+int plmc_cross_matvec_dx_sum_f64(const double *X, int n, const double *Xs, int ns, int d, int ncomp, const int *fam, const double *table,
+                                 const double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx,
+                                 void *partials, int q, void *stream);
+int plmc_cross_matvec_dx_dot_f32(const float *X, int n, const float *Xs, int ns, int d, const float *var, const float *offset, int power,
+                                 const float *oscale, const float *V, int64_t ldv, int64_t strideV, int r, const float *G, double *Jx, void *partials,
+                                 int q, void *stream);
+int plmc_cross_matvec_dx_dot_f64(const double *X, int n, const double *Xs, int ns, int d, const double *var, const double *offset, int power,
+                                 const double *oscale, const double *V, int64_t ldv, int64_t strideV, int r, const double *G, double *Jx,
+                                 void *partials, int q, void *stream);
+int plmc_rff_matvec_dx_f32(const float *freq, const float *phase, int m, const float *Xs, int ns, int d, const float *Wt, int r, const float *G,
+                           const float *scale, double *Jx, void *partials, int q, void *stream);
+int plmc_rff_matvec_dx_f64(const double *freq, const double *phase, int m, const double *Xs, int ns, int d, const double *Wt, int r, const double *G,
+                           const double *scale, double *Jx, void *partials, int q, void *stream);
+
+/*
  * The one exchange of the sharded path, for a host without torch.distributed (the Python layer's default
  * is torch.distributed "nccl" = RCCL, `projectedlmc/parallel.py`, which can be switched to these with PLMC_COMM=rccl):
  * a direct RCCL all-reduce (sum, in place) of the fused [loss share | parameter gradients] buffer after backward

@@ -167,32 +167,39 @@ SUM = "sum"
 _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
         "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
         "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
-        "plmc_posterior_dx": "plmc_posterior_dx_sum", "plmc_cross_matvec": "plmc_cross_matvec_sum"}
+        "plmc_posterior_dx": "plmc_posterior_dx_sum", "plmc_cross_matvec": "plmc_cross_matvec_sum",
+        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
          "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
-         "plmc_posterior_dx": "plmc_posterior_dx_lper", "plmc_cross_matvec": "plmc_cross_matvec_lper"}
+         "plmc_posterior_dx": "plmc_posterior_dx_lper", "plmc_cross_matvec": "plmc_cross_matvec_lper",
+         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_lper"}
 _DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
         "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
         "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
-        "plmc_posterior_dx": "plmc_posterior_dx_dot", "plmc_cross_matvec": "plmc_cross_matvec_dot"}
+        "plmc_posterior_dx": "plmc_posterior_dx_dot", "plmc_cross_matvec": "plmc_cross_matvec_dot",
+        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
        "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
-       "plmc_posterior_dx": "plmc_posterior_dx_rq", "plmc_cross_matvec": "plmc_cross_matvec_rq"}
+       "plmc_posterior_dx": "plmc_posterior_dx_rq", "plmc_cross_matvec": "plmc_cross_matvec_rq",
+       "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
         "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per",
-        "plmc_posterior_dx": "plmc_posterior_dx_per", "plmc_cross_matvec": "plmc_cross_matvec_per"}
+        "plmc_posterior_dx": "plmc_posterior_dx_per", "plmc_cross_matvec": "plmc_cross_matvec_per",
+        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
        "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
-       "plmc_posterior_dx": "plmc_posterior_dx_sm", "plmc_cross_matvec": "plmc_cross_matvec_sm"}
+       "plmc_posterior_dx": "plmc_posterior_dx_sm", "plmc_cross_matvec": "plmc_cross_matvec_sm",
+       "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
         "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add",
         "plmc_input_grad": "plmc_input_grad_add",
-        "plmc_posterior_dx": "plmc_posterior_dx_add", "plmc_cross_matvec": "plmc_cross_matvec_add"}
+        "plmc_posterior_dx": "plmc_posterior_dx_add", "plmc_cross_matvec": "plmc_cross_matvec_add",
+        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_add"}
 
 
 def sum_kind(members):
@@ -1099,6 +1106,74 @@ def rff_matvec(freq, phase, Xs, Wt, scale=None):
                _hip.ptr(part), q, st)
         if dst is not out:
             out[:, :, c0:c0 + rc] = dst
+    return out
+
+
+def cross_matvec_dx(kind, Xs, X, ell, oscale, V, G=None, n=None, ws=None):
+    """d (K(Xs, X) V) / dXs contracted with G, without K(Xs, X) (plmc_cross_matvec_dx): Xs (ns, d), X (n, d) raw
+    coordinates, the kind's table (ell, oscale) as everywhere in this module, V (q, rows >= n) or (q, rows >= n, r) as cross_matvec takes
+    it, G (q, ns, r) the upstream gradient of cross_matvec's result -> (q, ns, d) float64,
+        out[l, s, k] = sum_{i < n} (sum_c G[l, s, c] V[l, i, c]) d k_l(xs_s, x_i) / d xs_s[k].
+    G None (one column only): the Jacobian of that column.  More columns than plmc_cross_matvec_max_cols() go in chunks whose float64
+    results are added in chunk order.  ws: a workspace whose scratch may be borrowed.  Current stream."""
+    require_input_grad_kind(kind)
+    _hip.require_device(X, Xs, ell, V, G)
+    L = _hip.lib()
+    dt, dev = V.dtype, V.device
+    Vv = V.detach().unsqueeze(-1) if V.dim() == 2 else V.detach()
+    if Vv.shape[2] > 1 and Vv.stride(2) != 1:
+        raise ValueError("V must be contiguous along its columns")
+    q, r = Vv.shape[0], Vv.shape[2]
+    n = X.shape[0] if n is None else n
+    ns, d = Xs.shape
+    if G is None and r != 1:
+        raise ValueError("cross_matvec_dx: G=None is the Jacobian of ONE column, V has %d" % r)
+    if G is not None and tuple(G.shape) != (q, ns, r):
+        raise ValueError("cross_matvec_dx: G is (q, ns, r) = %s, got %s" % ((q, ns, r), tuple(G.shape)))
+    Xc, Xsc, ellc, osc = (_contig(t, dt) for t in (X, Xs, ell, oscale))
+    _check_kernel_shape(L, ellc, kind)
+    ldv, strideV = Vv.stride(1), Vv.stride(0)
+    cap = int(L.cdll.plmc_cross_matvec_max_cols())
+    st = _hip.stream_ptr(dev)
+    part = _cross_matvec_scratch(int(L.cdll.plmc_cross_matvec_dx_partials_bytes(n, ns, d, q)), dev, ws)
+    out = None
+    for c0 in range(0, r, cap):
+        rc = min(cap, r - c0)
+        Gc = None if G is None else _contig(G[:, :, c0:c0 + rc], dt)
+        dst = torch.empty(q, ns, d, dtype=torch.float64, device=dev)
+        _kernel_call(L, "plmc_cross_matvec_dx", dt, (kind_code(kind), _hip.ptr(Xc), n, _hip.ptr(Xsc), ns, d), ellc,
+                     (_hip.ptr(osc), _hip.ptr(Vv[:, :, c0:]), ldv, strideV, rc, _hip.ptr(Gc), _hip.ptr(dst), _hip.ptr(part), q, st))
+        out = dst if out is None else out + dst
+    return out
+
+
+def rff_matvec_dx(freq, phase, Xs, Wt, G=None, scale=None):
+    """d rff_matvec / dXs contracted with G (plmc_rff_matvec_dx): freq (q, m, d) and phase (q, m) in revolutions, Xs (ns, d), Wt (q, m, r),
+    G (q, ns, r) | None (r = 1: the Jacobian of the one column), scale (q) | None -> (q, ns, d) float64,
+        out[l, s, k] = -2 pi scale_l sum_j sin(2 pi (freq_lj . xs_s + phase_lj)) freq_ljk sum_c G[l, s, c] Wt[l, j, c].
+    Wider Wt than plmc_cross_matvec_max_cols() goes in chunks whose float64 results are added in chunk order.  Current stream."""
+    _hip.require_device(freq, phase, Xs, Wt, G)
+    L = _hip.lib()
+    dt, dev = Wt.dtype, Wt.device
+    q, m, r = Wt.shape
+    ns, d = Xs.shape
+    if G is None and r != 1:
+        raise ValueError("rff_matvec_dx: G=None is the Jacobian of ONE column, Wt has %d" % r)
+    if G is not None and tuple(G.shape) != (q, ns, r):
+        raise ValueError("rff_matvec_dx: G is (q, ns, r) = %s, got %s" % ((q, ns, r), tuple(G.shape)))
+    fc, pc, Xsc, sc = (_contig(t, dt) for t in (freq, phase, Xs, scale))
+    cap = int(L.cdll.plmc_cross_matvec_max_cols())
+    st = _hip.stream_ptr(dev)
+    part = _cross_matvec_scratch(int(L.cdll.plmc_cross_matvec_dx_partials_bytes(m, ns, d, q)), dev)
+    out = None
+    for c0 in range(0, r, cap):
+        rc = min(cap, r - c0)
+        Wc = _contig(Wt[:, :, c0:c0 + rc])
+        Gc = None if G is None else _contig(G[:, :, c0:c0 + rc], dt)
+        dst = torch.empty(q, ns, d, dtype=torch.float64, device=dev)
+        L.call("plmc_rff_matvec_dx", dt, _hip.ptr(fc), _hip.ptr(pc), m, _hip.ptr(Xsc), ns, d, _hip.ptr(Wc), rc, _hip.ptr(Gc), _hip.ptr(sc),
+               _hip.ptr(dst), _hip.ptr(part), q, st)
+        out = dst if out is None else out + dst
     return out
 
 

@@ -104,6 +104,15 @@ _TYPED = {
     "plmc_cross_matvec_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
     "plmc_cross_matvec_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _I, _P, _P, _I, _P],
     "plmc_rff_matvec": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_cross_matvec_dx_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
+    "plmc_rff_matvec_dx": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -147,6 +156,8 @@ _PLAIN = {
     "plmc_cross_matvec_max_cols": ([], _I),
     "plmc_cross_matvec_splits": ([_I, _I, _I], _I),
     "plmc_cross_matvec_partials_bytes": ([_I, _I, _I, _I], _L),
+    "plmc_cross_matvec_dx_splits": ([_I, _I, _I], _I),
+    "plmc_cross_matvec_dx_partials_bytes": ([_I, _I, _I, _I], _L),
     "plmc_lmc_grad_len": ([_I, _I, _I], _L),
     "plmc_lmc_grad_scratch_bytes": ([_L, _I, _I, _I], _L),
     "plmc_prof_enable": ([_I], _I),

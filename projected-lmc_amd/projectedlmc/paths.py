@@ -63,7 +63,9 @@ def _refuse(model):
 class PosteriorPaths:
     """num_paths posterior draws of one model as functions (model.sample_paths).  paths(x), x (n*, d), any n* ->
     (num_paths, n*) for a single-output ExactGPModel, (num_paths, n*, n_tasks) for a batch of tasks, (num_paths, n*, p) for
-    ProjectedGPModel (latents mixed by H as the posterior mean is, no observation noise added).  Under no_grad.
+    ProjectedGPModel (latents mixed by H as the posterior mean is, no observation noise added).  Under no_grad;
+    paths(x, differentiable=True) attaches the result to the graph of an x that requires a gradient, paths.jacobian(x) returns
+    d paths / dx without a graph.
     Read-only tensors: freq (q, M, d) and phase (q, M) in revolutions, feature_scale (q, M) = sqrt(2 os / m) per feature, w (P, q, M),
     eps (P, q, n) and v (q, n, P) = Khat^-1 (y - m(X) - f_prior(X) - eps).  The paths belong to the model's parameters and data at the
     time they were drawn."""
@@ -121,25 +123,87 @@ class PosteriorPaths:
         new._v = new._solve()
         return new
 
-    def __call__(self, x):
-        if x.requires_grad:
+    def _latents(self, xs):
+        """(q, n*, P): the latent draws at the kernel's features xs (n*, d'), the two fused products."""
+        lat = _engine.rff_matvec(self._freq, self._phase, xs, self._Wt)
+        return lat + _engine.cross_matvec(self._kind, xs, self._X, self._ell, self._osc, self._v)
+
+    def _latents_dx(self, xs, G=None, column=None):
+        """(q, n*, d') float64: d _latents / d xs contracted with G (q, n*, P), or the Jacobian of path `column` (G None)."""
+        Wt, v = self._Wt, self._v
+        if G is None:
+            Wt, v = Wt[:, :, column:column + 1], v[:, :, column:column + 1]
+        return (_engine.cross_matvec_dx(self._kind, xs, self._X, self._ell, self._osc, v, G)
+                + _engine.rff_matvec_dx(self._freq, self._phase, xs, Wt, G))
+
+    def _outputs(self, lat, xf):
+        """The latent draws (q, n*, P) as the model's outputs: mixed by H, or with the prior mean of the features xf."""
+        m = self._model
+        if self._projected:
+            Ht = m.lmc_coefficients().detach().to(lat.dtype)
+            return torch.einsum("qsc,qp->csp", lat, Ht)
+        lat = lat + m.mean_module(xf).reshape(m.n_tasks, -1).to(lat.dtype)[:, :, None]
+        if m.n_tasks == 1 and m.train_targets.dim() == 1:
+            return lat[0].T
+        return lat.permute(2, 1, 0)
+
+    def __call__(self, x, differentiable=False):
+        """The paths at x (n*, d).  differentiable=True: where x requires a gradient the result is attached to its graph -- the two
+        products and their input derivative (plmc_cross_matvec_dx, plmc_rff_matvec_dx) are one node over the kernel's
+        features, the mixing, the prior mean and an input_transform plain autograd around it (the transform's parameters detached, as
+        the differentiable prediction takes them).  Same values, bit for bit; once differentiable.  An x that needs no gradient is
+        evaluated as without the keyword."""
+        m = self._model
+        if differentiable and torch.is_grad_enabled() and x.requires_grad:
+            if x.ndimension() == 1:
+                x = x.unsqueeze(-1)
+            _engine.require_input_grad_kind(self._kind)
+            xf = m._test_features(x)
+            xs = m.covar_module.select(xf).to(self._ell.dtype)
+            return self._outputs(_PathLatents.apply(xs, self), xf)
+        if x.requires_grad and not differentiable:
             raise NotImplementedError("PosteriorPaths: an x that requires a gradient is not served -- paths carry no derivative with "
                                       "respect to x; detach it")
-        m = self._model
         with torch.no_grad():
             if x.ndimension() == 1:
                 x = x.unsqueeze(-1)
             xf = m._features(x, grad=False)
             xs = m.covar_module.select(xf).to(self._ell.dtype)
-            lat = _engine.rff_matvec(self._freq, self._phase, xs, self._Wt)
-            lat = lat + _engine.cross_matvec(self._kind, xs, self._X, self._ell, self._osc, self._v)    # (q, n*, P)
+            return self._outputs(self._latents(xs), xf)                                                  # (q, n*, P) mixed
+
+    def jacobian(self, x):
+        """d paths(x) / dx, shaped paths(x).shape + (d,): test points do not interact in a path, so this is the whole Jacobian.  No graph
+        is built.  It COSTS ONE GRADIENT PER PATH -- a G = NULL, r = 1 pair of kernel calls each -- so for a scalar objective of the paths
+        paths(x, differentiable=True) and one backward pass is num_paths times cheaper.  x as predictive_gradients takes it: the model has
+        no input_transform, a kernel on all dimensions and a zero or constant mean."""
+        m = self._model
+        x = m._plain_test_inputs(x, "PosteriorPaths.jacobian")
+        with torch.no_grad():
+            xs = x.to(self._ell.dtype)
+            J = torch.stack([self._latents_dx(xs, column=c) for c in range(self.num_paths)])             # (P, q, n*, d) float64
             if self._projected:
-                Ht = m.lmc_coefficients().detach().to(lat.dtype)
-                return torch.einsum("qsc,qp->csp", lat, Ht)
-            lat = lat + m.mean_module(xf).reshape(m.n_tasks, -1).to(lat.dtype)[:, :, None]
+                Ht = m.lmc_coefficients().detach().to(J.dtype)
+                return torch.einsum("cqsk,qp->cspk", J, Ht).to(x.dtype)
             if m.n_tasks == 1 and m.train_targets.dim() == 1:
-                return lat[0].T
-            return lat.permute(2, 1, 0)
+                return J[:, 0].to(x.dtype)
+            return J.permute(0, 2, 1, 3).to(x.dtype)
+
+
+class _PathLatents(torch.autograd.Function):
+    """PosteriorPaths._latents as a function of the kernel's features: backward is _latents_dx with the upstream gradient as G, summed over
+    the latents.  The draws, the weights and the hyper-parameters are constants of this node.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, xs, paths):
+        ctx.paths = paths
+        ctx.save_for_backward(xs)
+        return paths._latents(xs.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (xs,) = ctx.saved_tensors
+        return ctx.paths._latents_dx(xs, g.contiguous()).sum(0).to(xs.dtype), None
 
 
 def sample_paths(model, num_paths, num_features=1024, generator=None):
