@@ -833,6 +833,84 @@ int plmc_loo_operand_f64(const double *Kinv, int64_t n_pad, int64_t ldk, int64_t
                          int64_t ldx, int64_t strideX, int n, int q, void *stream);
 
 /*
+ * Weighted kernel-gradient sum: the gradient epilogues and reductions of plmc_kinv_grad*_vd_* behind the product of two general
+ * operands.  For q latents with N points Z (N x d) each and the family's table theta,
+ *     grad[latent][t] = sum_{i <= j < N} c_ij (At^T Bt)_ij dKhat(Z)_ij / dtheta_t ,   c_ii = 1, c_ij = 2 for i < j,
+ * Khat(Z) = K(Z, Z) + noise I.  For a symmetric At^T Bt this is the full sum over i, j < N; for any other product it is the sum over the
+ * upper triangle with these weights (what lies below the diagonal of At^T Bt is not formed).  The noise slot is sum_{i < N} (At^T Bt)_ii.
+ * Use: the gradient of a loss of the posterior moments with respect to hyper-parameters and noise is this sum over the stacked points
+ * Z = [X; X*] with a product of rank n* + 2 (or 2 for a loss of the mean alone), DESIGN.md 7.14.
+ *
+ * plmc_weighted_grad*_: the arguments of the family's plmc_kinv_grad*_vd_* with (W, n_pad, ldw, strideW, alpha, X, n) replaced by
+ *   (At, Bt, r_pad, N_pad, ld, stride, Z, N) and without Kinv, ldk, strideK, kinv_diag, eig_lo and Vd.
+ *   At, Bt: r_pad x N_pad per latent, K-major (row = contraction index), leading dimension ld, batch stride `stride` (elements); every
+ *   row in [0, r_pad) is contracted and every column in [0, N_pad) enters a tile.  ZERO PADDING IS THE CALLER'S DUTY: rows that carry
+ *   nothing and the columns [N, N_pad) of both operands must hold exact zeros (a NaN there reaches the sums of the last block row).
+ *   Columns [N_pad, ld) and whatever lies behind the last latent's r_pad rows are not read; Z is read for rows < N only.
+ *   r_pad a positive multiple of 16, N_pad a multiple of plmc_block() and >= N > 0, ld >= N_pad with 16-byte aligned rows, both pointers
+ *   and `stride` 16-byte aligned, stride >= r_pad ld when q > 1.
+ *   grad: the family's gradient table, same layout and width as plmc_kinv_grad*_vd_* writes it (double):
+ *     plain [d ell: d | d noise | d oscale]; _add [ncomp x d | noise | ncomp]; _sm [scales: nmix x d | means: nmix x d | noise | weights:
+ *     nmix]; _per [ell: d | period: d | noise | oscale]; _rq [ell: d | alpha | noise | oscale]; _lper [ell: d | period: d | rbf_ell: d |
+ *     noise | oscale]; _sum [table: ncomp x (3 d + 1) | noise | oscale: ncomp]; _dot [var: d | offset | noise | oscale].
+ *   partials: the family's size call evaluated at N_pad -- plmc_grad_partials_bytes(N_pad, q * ncomp), plmc_sm_grad_partials_bytes,
+ *   plmc_per_grad_partials_bytes, plmc_lper_grad_partials_bytes, plmc_sum_grad_partials_bytes -- as for the `_vd` calls.
+ *   Both element types form the product with the matrix instructions of that type (fp32: v_mfma_f32_16x16x4_f32 whatever PLMC_SPLIT
+ *   says: the operands have no eigenvalue bound to scale a 16-bit split by).  Per-tile sums in fp64, reduced in a fixed order: two calls
+ *   with the same arguments return the same bits.  q N_pad^2 r_pad flop (upper tiles only).
+ * Bad arguments -- a null pointer, N <= 0, r_pad or N_pad off their granularity, ld < N_pad, d, components or power beyond the family's
+ * plmc_*_max_* -- fail through plmc_last_error() before anything is launched.
+ */
+int plmc_weighted_grad_f32(int kind, const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,
+                           const float *Z, int N, int d, const float *ell, const float *oscale, double *grad, void *partials, int q,
+                           void *stream);
+int plmc_weighted_grad_f64(int kind, const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,
+                           const double *Z, int N, int d, const double *ell, const double *oscale, double *grad, void *partials, int q,
+                           void *stream);
+int plmc_weighted_grad_add_f32(int kind, const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,
+                               const float *Z, int N, int d, int ncomp, const float *ell, const float *oscale, double *grad, void *partials,
+                               int q, void *stream);
+int plmc_weighted_grad_add_f64(int kind, const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,
+                               const double *Z, int N, int d, int ncomp, const double *ell, const double *oscale, double *grad,
+                               void *partials, int q, void *stream);
+int plmc_weighted_grad_sm_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                              int N, int d, int nmix, const float *scales, const float *means, const float *weights, double *grad,
+                              void *partials, int q, void *stream);
+int plmc_weighted_grad_sm_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const double *Z,
+                              int N, int d, int nmix, const double *scales, const double *means, const double *weights, double *grad,
+                              void *partials, int q, void *stream);
+int plmc_weighted_grad_per_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                               int N, int d, const float *ell, const float *period, const float *oscale, double *grad, void *partials,
+                               int q, void *stream);
+int plmc_weighted_grad_per_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const double *Z,
+                               int N, int d, const double *ell, const double *period, const double *oscale, double *grad, void *partials,
+                               int q, void *stream);
+int plmc_weighted_grad_rq_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                              int N, int d, const float *ell, const float *alpha, const float *oscale, double *grad, void *partials, int q,
+                              void *stream);
+int plmc_weighted_grad_rq_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const double *Z,
+                              int N, int d, const double *ell, const double *alpha, const double *oscale, double *grad, void *partials,
+                              int q, void *stream);
+int plmc_weighted_grad_lper_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                                int N, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
+                                double *grad, void *partials, int q, void *stream);
+int plmc_weighted_grad_lper_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,
+                                const double *Z, int N, int d, const double *ell, const double *period, const double *rbf_ell,
+                                const double *oscale, double *grad, void *partials, int q, void *stream);
+int plmc_weighted_grad_sum_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                               int N, int d, int ncomp, const int *fam, const float *table, const float *oscale, double *grad,
+                               void *partials, int q, void *stream);
+int plmc_weighted_grad_sum_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const double *Z,
+                               int N, int d, int ncomp, const int *fam, const double *table, const double *oscale, double *grad,
+                               void *partials, int q, void *stream);
+int plmc_weighted_grad_dot_f32(const float *At, const float *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const float *Z,
+                               int N, int d, const float *var, const float *offset, int power, const float *oscale, double *grad,
+                               void *partials, int q, void *stream);
+int plmc_weighted_grad_dot_f64(const double *At, const double *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride, const double *Z,
+                               int N, int d, const double *var, const double *offset, int power, const double *oscale, double *grad,
+                               void *partials, int q, void *stream);
+
+/*
  * Input gradients of the exact log density: d log N(y; 0, Khat) / dX for q latents that share the inputs X (n x d), the row-wise
  * pull-back of Omega = alpha alpha^T - Khat^-1 through the kernel's input derivative:
  *     gX[lat][i][k] = sum_{j < n, j != i} (alpha_i alpha_j - P_ij) d k_lat(x_i, x_j) / d x_i[k]          (gX: q x n x d doubles, contiguous)

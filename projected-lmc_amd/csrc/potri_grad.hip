@@ -797,6 +797,138 @@ int loo_operand_impl(const T *Kinv, int64_t n_pad, int64_t ldk, int64_t strideK,
   return launch_status(__func__);
 }
 
+// ---- weighted kernel-gradient sum: the gradient epilogues above behind the product of two GENERAL operands.
+//     grad[l][t] = sum_{i <= j < N} c_ij (At_l^T Bt_l)_ij dKhat_l(Z)_ij / dtheta_t,   c_ii = 1, c_ij = 2
+// (include/plmc.h, "Weighted kernel-gradient sum"; DESIGN.md 7.14: the gradient of a loss of the posterior moments with respect to the
+// hyper-parameters is this sum over the stacked points Z = [X; X*]).  At, Bt: r_pad x N_pad per latent, K-major like W, every row
+// contracted -- the tile (ib, jb) is the product of column strip ib of At and column strip jb of Bt over ALL r_pad rows, as for the
+// leave-one-out gradient, but of two different operands, so that only the upper tiles of a symmetric At^T Bt are formed.  The epilogue
+// text reduces (alpha_i alpha_j - acc_ij) dKhat_ij / dtheta and its reduction halves the sum: `alpha` is a vector of zeros that is never
+// read from memory (ZeroVector), so the family's reduction leaves -1/2 of the wanted sum, and k_scale_table multiplies the finished
+// table by -2, a power of two: sign and 1/2 of the marginal-likelihood form cancel without a rounding.  (Scaling the tile in front of
+// the epilogue instead kept a second copy of the accumulators in registers: 64 / 128 more per lane, scratch in one instantiation.)
+// Nothing is stored.
+// One upper tile per workgroup in the order of k_kinv_grad (latent fastest); fp32 on v_mfma_f32_16x16x4_f32 (no split engine: the
+// operands have no eigenvalue bound to scale by).
+template <typename T> struct ZeroVector {
+  __device__ __forceinline__ T operator[](int64_t) const { return T(0); }
+};
+#define PLMC_WEIGHTED_TILE_PRODUCT                                                                                                             \
+  const int m = (int)(n_pad / NB);                                                                                                             \
+  const int lat = (int)blockIdx.x % nlat;                                                                                                      \
+  int ib, jb;                                                                                                                                  \
+  tri_decode((int)blockIdx.x / nlat, ib, jb);                                                                                                  \
+  __shared__ __align__(16) T smem[tile_smem_elems<T>()];                                                                                       \
+  Acc<T> acc;                                                                                                                                  \
+  acc.zero();                                                                                                                                  \
+  tile_mainloop<T, false, true>(acc, At + (int64_t)lat * strideAB + (int64_t)ib * NB, ldab, Bt + (int64_t)lat * strideAB + (int64_t)jb * NB,   \
+                                ldab, (int)r_pad, smem);                                                                                       \
+  const ZeroVector<T> alpha;                                                                                                                   \
+  T *const Kinv = nullptr, *const kinv_diag = nullptr;                                                                                         \
+  constexpr int64_t ldk = 0, strideK = 0;                                                                                                      \
+  const int tid = threadIdx.x;                                                                                                                 \
+  constexpr bool live = true
+
+// occupancy floor: that of the matching k_kinv_grad / k_kinv_grad_add instantiation, except where the same epilogue text behind this tile
+// product needs a few registers more than the floor leaves (as k_loo_grad found, LOO_MIN_WAVES): no instantiation uses scratch
+// (profiles/weighted_grad_resource_usage.md)
+template <typename T, int DCAP> constexpr int WG_MIN_WAVES = LOO_MIN_WAVES<T, DCAP>;
+
+template <typename T, int DCAP, bool SPLINE = false>
+__global__ __launch_bounds__(NTHREADS, (WG_MIN_WAVES<T, DCAP>)) void k_weighted_grad(int kind, const T *__restrict__ At, const T *__restrict__ Bt,
+                                                                                    int64_t r_pad, int64_t n_pad, int64_t ldab, int64_t strideAB,
+                                                                                    const T *__restrict__ X, int n, int d,
+                                                                                    const T *__restrict__ ell, const T *__restrict__ oscale,
+                                                                                    double *__restrict__ partials, int nlat) {
+  PLMC_WEIGHTED_TILE_PRODUCT;
+#define PLMC_KINV_KEEP (sizeof(T) == 4)
+#include "kinv_epilogue.inc"
+#undef PLMC_KINV_KEEP
+}
+
+template <typename T, CovFamily F, int DC = 0>
+__global__ __launch_bounds__(NTHREADS, (table_min_waves<T, F, DC>())) void k_weighted_grad_add(
+    int kind, int ncomp, const T *__restrict__ At, const T *__restrict__ Bt, int64_t r_pad, int64_t n_pad, int64_t ldab, int64_t strideAB,
+    const T *__restrict__ X, int n, int d, const T *__restrict__ ell, const T *__restrict__ oscale, double *__restrict__ partials, int nlat,
+    const T *__restrict__ means, const T *__restrict__ third) {
+  PLMC_WEIGHTED_TILE_PRODUCT;
+#include "kinv_epilogue_table.inc"
+}
+
+// table[0 .. count) *= factor, one workgroup (the finished gradient table of a call: q rows of at most a few hundred doubles)
+__global__ void k_scale_table(double *__restrict__ table, int count, double factor) {
+  for (int e = threadIdx.x; e < count; e += blockDim.x) table[e] *= factor;
+}
+// entries per latent of the family's gradient table, as its reduction kernel writes it (k_reduce_grad*)
+inline int grad_table_width(const CovTable &t) {
+  const int d = t.d, g = t.ncomp;
+  switch (t.route()) {
+    case COV_PER: return 2 * d + 2;
+    case COV_LPER: return 3 * d + 2;
+    case COV_SUM: return g * (3 * d + 2) + 1;
+    case COV_RQ: case COV_DOT: return d + 3;
+    case COV_SM: return g * (2 * d + 1) + 1;
+    case COV_ADD: return g * (d + 1) + 1;
+    case COV_PLAIN: break;
+  }
+  return d + 2;
+}
+
+// The sibling of loo_grad_impl for the weighted sum: the same table, the same partial sums (sized by the same calls, at N_pad), the same
+// reductions.  Z: the N points the table's kernel is evaluated on (rows < N are read); operand rows [r, r_pad) and columns [N, N_pad)
+// must be zero (the caller's duty); columns [N_pad, ld) are not read.
+template <typename T>
+int weighted_grad_impl(const CovTable &table, const T *At, const T *Bt, int64_t r_pad, int64_t n_pad, int64_t ld, int64_t stride, const T *Z, int n,
+                       double *grad, void *partials, int q, void *stream, bool check_only = false) {
+  if (table.single_member())          // a sum of one member IS that member: its family's own path
+    return sum_single_member<T>(table, n_pad, q, grad, partials, stream, [&](const CovTable &mt, double *fg, bool check) {
+      return weighted_grad_impl<T>(mt, At, Bt, r_pad, n_pad, ld, stride, Z, n, fg, partials, q, stream, check);
+    });
+  constexpr int64_t EPV = 16 / (int64_t)sizeof(T);
+  PLMC_REQUIRE_TABLE(table);
+  const CovFamily family = table.route();
+  const int kind = table.kernel_kind(), d = table.d, ncomp = table.ncomp;
+  const T *ell = (const T *)table.ell, *oscale = (const T *)table.oscale, *second = (const T *)table.second, *third = (const T *)table.third;
+  PLMC_REQUIRE(table.kind >= 0 && table.kind <= 4, "unknown kernel kind");
+  PLMC_REQUIRE(At && Bt && Z && ell && grad && partials, "null pointer");
+  PLMC_REQUIRE(n > 0, "need N > 0");
+  PLMC_REQUIRE(n_pad > 0 && n_pad % NB == 0 && n <= n_pad && n_pad < ((int64_t)1 << 31), "N_pad must be a multiple of the block size, at least N");
+  PLMC_REQUIRE(r_pad > 0 && r_pad % BK == 0 && r_pad < ((int64_t)1 << 31), "r_pad must be a positive multiple of 16");
+  PLMC_REQUIRE(ld >= n_pad && ld % EPV == 0, "ld must be at least N_pad, its rows 16-byte aligned");
+  PLMC_REQUIRE(q == 1 || stride >= r_pad * ld, "stride too small");
+  PLMC_REQUIRE(d > 0 && d <= MAX_DIM && q > 0, "need 0<d<=plmc_max_dim(), q>0");
+  PLMC_REQUIRE(aligned16(At) && aligned16(Bt) && stride % EPV == 0, "unaligned operands");
+  const int m = (int)(n_pad / NB);
+  PLMC_REQUIRE((int64_t)q * ((int64_t)m * (m + 1) / 2) < ((int64_t)1 << 31), "too many tiles for one launch");
+  if (check_only) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  double *part = reinterpret_cast<double *>(partials);
+  const double np = (double)n_pad;
+  const dim3 grid(q * (m * (m + 1) / 2)), block(NTHREADS);
+#define PLMC_LAUNCH_WG(DC, SP) \
+  hipLaunchKernelGGL((k_weighted_grad<T, DC, SP>), grid, block, 0, st, kind, At, Bt, r_pad, n_pad, ld, stride, Z, n, d, ell, oscale, part, q)
+#define PLMC_LAUNCH_WT(F, DC) \
+  hipLaunchKernelGGL((k_weighted_grad_add<T, F, DC>), grid, block, 0, st, kind, ncomp, At, Bt, r_pad, n_pad, ld, stride, Z, n, d, ell, oscale, part, q, \
+                     second, third)
+  {
+    ProfScope ps(PK_KINV_GRAD, st, q * np * np * (double)r_pad, q * np * (double)r_pad * 2 * sizeof(T));
+    switch (family) {
+      default: with_capacity<0>(family, d, [&](auto f, auto dc) { PLMC_LAUNCH_WT(decltype(f)::value, decltype(dc)::value); }); break;
+      case COV_ADD: PLMC_LAUNCH_WT(COV_ADD, 0); break;
+      case COV_PLAIN:
+        if (d <= 4) PLMC_LAUNCH_WG(4, false);
+        else if (d <= 8) PLMC_LAUNCH_WG(8, false);
+        else if (d <= 16) { if (kind == K_SPLINE) PLMC_LAUNCH_WG(16, true); else PLMC_LAUNCH_WG(16, false); }
+        else { if (kind == K_SPLINE) PLMC_LAUNCH_WG(32, true); else PLMC_LAUNCH_WG(32, false); }
+    }
+  }
+#undef PLMC_LAUNCH_WT
+#undef PLMC_LAUNCH_WG
+  launch_reduce_grad<T>(table, part, m, q, grad, st);
+  hipLaunchKernelGGL(k_scale_table, dim3(1), dim3(256), 0, st, grad, q * grad_table_width(table), -2.0);
+  return launch_status(__func__);
+}
+
 // ---- a heterogeneous sum of ONE member is that member's family: its own kernels run on the whole batch, bit for bit.  They read (q, d)
 // rows, the sum's records are 3 d + 1 apart, so the owned slots are re-laid behind the partial sums (SUM_TAIL_BYTES per latent, counted
 // by plmc_sum_grad_partials_bytes): rows [ell | period | rbf_ell: q x d each | alpha: q], then the family's gradient table, which
@@ -897,7 +1029,8 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
 // The entry points of the families (api_common.hpp, PLMC_FAMILY_ENTRIES): the only place the covariance tables of this file are built from
 // flat arguments.  plmc_kinv_grad*_vd_*: `partials` is sized by plmc_grad_partials_bytes, for a spectral mixture, a locally periodic
 // kernel and a sum by their own plmc_*_grad_partials_bytes.  plmc_loo_grad*: the leave-one-out pseudo-likelihood (include/plmc.h,
-// "Leave-one-out objective"), the family's gradient table of 1/2 (beta beta^T - Xop^T Xop).
+// "Leave-one-out objective"), the family's gradient table of 1/2 (beta beta^T - Xop^T Xop).  plmc_weighted_grad*: the family's gradient
+// table weighted by the upper triangle of At^T Bt (include/plmc.h, "Weighted kernel-gradient sum").
 #define PLMC_GRAD_ENTRY(SUF, T, INFIX, LEAD, PARAMS, TABLE)                                                                                     \
   int plmc_kinv_grad##INFIX##_vd_##SUF(PLMC_LEAD_##LEAD const T *W, int64_t n_pad, int64_t ldw, int64_t strideW, const T *alpha, const T *X,    \
                                        int n, int d, PLMC_UNPACK PARAMS, double *grad, T *Kinv, int64_t ldk, int64_t strideK, T *kinv_diag,     \
@@ -907,6 +1040,10 @@ int64_t plmc_grad_partials_bytes(int64_t n_pad, int q) {
   int plmc_loo_grad##INFIX##_##SUF(PLMC_LEAD_##LEAD const T *Xop, int64_t n_pad, int64_t krows, int64_t ldx, int64_t strideX, const T *beta,    \
                                    const T *X, int n, int d, PLMC_UNPACK PARAMS, double *grad, void *partials, int q, void *stream) {           \
     return plmc::loo_grad_impl<T>(TABLE, Xop, n_pad, krows, ldx, strideX, beta, X, n, grad, partials, q, stream);                               \
+  }                                                                                                                                             \
+  int plmc_weighted_grad##INFIX##_##SUF(PLMC_LEAD_##LEAD const T *At, const T *Bt, int64_t r_pad, int64_t N_pad, int64_t ld, int64_t stride,    \
+                                        const T *Z, int N, int d, PLMC_UNPACK PARAMS, double *grad, void *partials, int q, void *stream) {      \
+    return plmc::weighted_grad_impl<T>(TABLE, At, Bt, r_pad, N_pad, ld, stride, Z, N, grad, partials, q, stream);                               \
   }
 PLMC_FAMILY_ENTRIES(PLMC_GRAD_ENTRY, f32, float)
 PLMC_FAMILY_ENTRIES(PLMC_GRAD_ENTRY, f64, double)

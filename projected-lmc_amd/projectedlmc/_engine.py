@@ -166,37 +166,37 @@ RQ = "rq"
 SUM = "sum"
 _SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
         "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
-        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
+        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_weighted_grad": "plmc_weighted_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
         "plmc_posterior_dx": "plmc_posterior_dx_sum", "plmc_cross_matvec": "plmc_cross_matvec_sum",
         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sum"}
 _LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
          "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
-         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
+         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_weighted_grad": "plmc_weighted_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
          "plmc_posterior_dx": "plmc_posterior_dx_lper", "plmc_cross_matvec": "plmc_cross_matvec_lper",
          "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_lper"}
 _DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
         "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
-        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
+        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_weighted_grad": "plmc_weighted_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
         "plmc_posterior_dx": "plmc_posterior_dx_dot", "plmc_cross_matvec": "plmc_cross_matvec_dot",
         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_dot"}
 _RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
        "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
-       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
+       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_weighted_grad": "plmc_weighted_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
        "plmc_posterior_dx": "plmc_posterior_dx_rq", "plmc_cross_matvec": "plmc_cross_matvec_rq",
        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_rq"}
 _PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
         "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
-        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_input_grad": "plmc_input_grad_per",
+        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_weighted_grad": "plmc_weighted_grad_per", "plmc_input_grad": "plmc_input_grad_per",
         "plmc_posterior_dx": "plmc_posterior_dx_per", "plmc_cross_matvec": "plmc_cross_matvec_per",
         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_per"}
 _SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
        "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
-       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
+       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_weighted_grad": "plmc_weighted_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
        "plmc_posterior_dx": "plmc_posterior_dx_sm", "plmc_cross_matvec": "plmc_cross_matvec_sm",
        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sm"}
 _ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
         "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
-        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add",
+        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add", "plmc_weighted_grad": "plmc_weighted_grad_add",
         "plmc_input_grad": "plmc_input_grad_add",
         "plmc_posterior_dx": "plmc_posterior_dx_add", "plmc_cross_matvec": "plmc_cross_matvec_add",
         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_add"}
@@ -794,6 +794,14 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     on the first call, "off" never.
     Xs.requires_grad (with gradients enabled): the moments come from the autograd node PosteriorMoments, which carries d mean / dXs and
     d var / dXs; hyper-parameters, noise and training data stay constants.  Without it nothing below changes."""
+    if settings.posterior_hyper_grad.on() and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (ell, oscale, noise, y)):
+        # hyper-parameters, noise or targets carry a graph: the node that differentiates the moments in them (and in Xs, if it asks)
+        if full_cov:
+            raise NotImplementedError("full_cov=True under settings.posterior_hyper_grad: only the marginal moments (mean, variance) are "
+                                      "differentiable with respect to hyper-parameters, noise and targets -- predict with full_cov=False")
+        if Xs.requires_grad:
+            require_input_grad_kind(kind)
+        return PosteriorHyperMoments.apply(Xs, ell, oscale, noise, y, kind, X, cache, key)
     if torch.is_grad_enabled() and Xs.requires_grad:
         if full_cov:
             raise NotImplementedError("full_cov=True together with test inputs that require a gradient: only the marginal moments "
@@ -804,10 +812,11 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov, cache, key)
 
 
-def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, dx=None):
+def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, dx=None, keep=None):
     """exact_posterior's work.  dx = "mean" | "both": also the Jacobians of the marginal moments with respect to Xs, -> (mean, var, Jm,
     Jv | None) (_posterior_jacobians); they need the inverse factor, so a miss builds the cache at once where there is one (a caller
-    who differentiates predictions will call again) and takes a pooled workspace WITH the inverse factor where there is none."""
+    who differentiates predictions will call again) and takes a pooled workspace WITH the inverse factor where there is none.
+    keep (a dict, PosteriorHyperMoments): the workspace is chosen as for dx and handed back in keep["ws"]."""
     _hip.require_device(X, ell, noise, y, Xs)
     L = _hip.lib()
     dt, dev = y.dtype, y.device
@@ -828,13 +837,13 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
     # build: eager mode; lazy mode on the second call with one key; or the cached state is the same and only its capacity is short
     same_state = cache is not None and cache.ws is not None and key is not None and cache.key == key
     build = cache is not None and mode != "off" and not hit and (mode == "eager" or same_state or (key is not None and cache.seen == key)
-                                                                 or dx is not None)
+                                                                 or dx is not None or keep is not None)
     if not hit and not build:
         if cache is not None and mode != "off":
             cache.drop()                                   # (a stale factorisation of another state goes now, not at the next build)
             cache.seen = key
             cache.misses += 1
-        ws = get_workspace(n, q, 1 + ns, dt, dev, dx is not None)
+        ws = get_workspace(n, q, 1 + ns, dt, dev, dx is not None or keep is not None)
         factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)
     else:
         if hit:
@@ -860,6 +869,8 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
     mean = torch.empty(q, ns, dtype=dt, device=dev)
     vsq = torch.empty(q, ns, dtype=dt, device=dev)
     L.call("plmc_posterior_moments", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, ns, _hip.ptr(mean), _hip.ptr(vsq), q, st)
+    if keep is not None:
+        keep["ws"] = ws
     if full_cov:
         V = ws.A[:, :, ws.n_pad + 1:ws.n_pad + 1 + ns]             # (q, n_pad, ns) strided view, K-major
         Kss = dense_cross(kind, Xsc, Xsc, ellc, osc)
@@ -1204,6 +1215,185 @@ class PosteriorMoments(torch.autograd.Function):
         return (g.to(ctx.x_dtype),) + (None,) * 8
 
 
+def _grad_partials(L, n_pad, q, ell, kind, dtype, device):
+    """The per-tile partial sums of the family's gradient kernels at n_pad, by the library's own size calls (as Workspace sizes them)."""
+    esz = torch.empty((), dtype=dtype).element_size()
+    ncomp, per = n_components(ell, kind), _per_kind(kind)
+    nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(n_pad, q, ncomp, esz) if is_sm(ell)
+                 else L.cdll.plmc_sum_grad_partials_bytes(n_pad, q, ncomp, esz) if per == SUM
+                 else L.cdll.plmc_lper_grad_partials_bytes(n_pad, q, esz) if per == LPER
+                 else L.cdll.plmc_per_grad_partials_bytes(n_pad, q, esz) if per
+                 else L.cdll.plmc_grad_partials_bytes(n_pad, q * ncomp))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def weighted_grad(kind, Z, ell, oscale, At, Bt, N):
+    """plmc_weighted_grad on caller-owned buffers (include/plmc.h, "Weighted kernel-gradient sum"): Z (N, d), the kind's table (ell, oscale)
+    as everywhere in this module, At, Bt (q, r_pad, ld) K-major with unit stride along ld >= plmc_pad(N), zeros in the rows that carry
+    nothing and in the columns [N, plmc_pad(N)) -> (d/d ell, d/d noise, d/d oscale | None) float64, shaped like the table,
+        g[l][t] = sum_{i <= j < N} c_ij (At_l^T Bt_l)_ij d Khat_l(Z)_ij / d theta_t,   c_ii = 1, c_ij = 2.
+    Current stream."""
+    _hip.require_device(Z, ell, At, Bt)
+    L = _hip.lib()
+    dt, dev = At.dtype, At.device
+    if At.dim() != 3 or At.shape != Bt.shape or At.stride() != Bt.stride() or At.stride(2) != 1 or Bt.dtype != dt:
+        raise ValueError("weighted_grad: At and Bt are (q, r_pad, ld) of one dtype, shape and layout, contiguous along ld")
+    q, r_pad, ld = At.shape[0], At.shape[1], At.stride(1)
+    N_pad = int(L.cdll.plmc_pad(N))
+    Zc, ellc, osc = (_contig(t, dt) for t in (Z, ell, oscale))
+    _check_kernel_shape(L, ellc, kind)
+    if ellc.shape[0] != q:
+        raise ValueError("weighted_grad: the table has %d latents, the operands %d" % (ellc.shape[0], q))
+    grad = torch.empty(q, grad_table_width(ellc, kind), dtype=torch.float64, device=dev)
+    partials = _grad_partials(L, N_pad, q, ellc, kind, dt, dev)
+    _kernel_call(L, "plmc_weighted_grad", dt, (kind_code(kind), _hip.ptr(At), _hip.ptr(Bt), r_pad, N_pad, ld, At.stride(0), _hip.ptr(Zc), N,
+                 Zc.shape[1]), ellc, (_hip.ptr(osc), _hip.ptr(grad), _hip.ptr(partials), q, _hip.stream_ptr(dev)))
+    return _split_grad_table(grad, ellc.shape, None if osc is None else osc.shape)
+
+
+_OPERAND_BLOCK, _OPERAND_DEPTH = 128, 16        # plmc_block() and the stage depth of the tile engine (include/plmc.h): the operands' padding
+
+
+def posterior_hyper_operands(alpha, B, gm, gv, n, ns, u=None):
+    """The operands of the weighted kernel-gradient sum behind d L / d theta for a loss L(mean, var) of the posterior moments at ns test
+    points; plain torch on any device.  alpha = Khat^-1 y (q, >= n), B = Khat^-1 K(X, X*) (q, >= n, >= ns) | None, gm =
+    dL / d mean (q, ns), gv = dL / d var (q, ns) | None.  Over the stacked points Z = [X; X*] (N = n + ns), with u = B gm = dL / dy:
+        Qt rows   c < ns: [ b_c^T | -e_c^T ]     ns: [ alpha^T | 0 ]      ns + 1: [ u^T | -gm^T ]
+        Pt rows   c < ns: gv_c Qt[c]             ns: -1/2 Qt[ns + 1]      ns + 1: -1/2 Qt[ns]
+    so that M = Pt^T Qt = sum_c gv_c q_c q_c^T - 1/2 (a u~^T + u~ a^T) is symmetric, its test x test block is diag(gv), and
+        dL / d theta = sum_{i, j < N} M_ij d Khat(Z)_ij / d theta,   dL / d noise = sum_i M_ii - sum_s gv_s
+    (the latent variance at a test point carries no noise: the caller subtracts).  gv None or B None: a loss of the mean alone -- only the
+    last two rows (r = 2), and u must be given (u = Khat^-1 K(X, X*) gm; B is never formed).
+    -> (Pt, Qt, u): Pt, Qt (q, r_pad, N_pad) of alpha's dtype, exact zeros in rows [r, r_pad) and columns [N, N_pad); u (q, n)."""
+    q, dt, dev = alpha.shape[0], alpha.dtype, alpha.device
+    variance = B is not None and gv is not None
+    gm = gm.to(dt)
+    if u is None:
+        if B is None:
+            raise ValueError("posterior_hyper_operands: without B, u = Khat^-1 K(X, X*) gm must be given")
+        u = torch.bmm(B[:, :n, :ns], gm.unsqueeze(-1)).squeeze(-1)
+    u = u[:, :n].to(dt)
+    r, N = (ns + 2 if variance else 2), n + ns
+    r_pad = -(-r // _OPERAND_DEPTH) * _OPERAND_DEPTH
+    N_pad = -(-N // _OPERAND_BLOCK) * _OPERAND_BLOCK
+    Qt = torch.zeros(q, r_pad, N_pad, dtype=dt, device=dev)
+    Pt = torch.zeros(q, r_pad, N_pad, dtype=dt, device=dev)
+    r0 = ns if variance else 0
+    if variance:
+        Qt[:, :ns, :n] = B[:, :n, :ns].transpose(1, 2)
+        idx = torch.arange(ns, device=dev)
+        Qt[:, idx, n + idx] = -1.0
+        Pt[:, :ns] = gv.to(dt)[:, :, None] * Qt[:, :ns]
+    Qt[:, r0, :n] = alpha[:, :n]
+    Qt[:, r0 + 1, :n] = u
+    Qt[:, r0 + 1, n:N] = -gm
+    Pt[:, r0] = -0.5 * Qt[:, r0 + 1]
+    Pt[:, r0 + 1] = -0.5 * Qt[:, r0]
+    return Pt, Qt, u
+
+
+def _vtw_buffer(ws):
+    """[alpha^T ; B^T] = [z | V]^T W of the eval-mode posterior (naug_pad rows of n_pad per latent: the test points are the ROWS, as the
+    operands of the weighted kernel-gradient sum want them), kept with the workspace and created on first use."""
+    buf = getattr(ws, "vtw", None)
+    if buf is None:
+        buf = ws.vtw = torch.empty(ws.q, ws.naug_pad, ws.n_pad, dtype=ws.dtype, device=ws.device)
+    return buf
+
+
+hyper_grad_counters = {"b_products": 0, "weighted_grad_calls": 0, "mean_only_solves": 0}    # what the differentiable prediction launched (tests)
+
+
+def _alpha_and_bt(ws, ns, variance):
+    """alpha = W^T z into ws.alpha and, with `variance`, [alpha^T ; B^T] = [z | V]^T W on the tile engine, already transposed for
+    posterior_hyper_operands: the product of _posterior_jacobians with its operands exchanged -- W, the lower triangle of its block of the
+    factor buffer, is now the B operand (PLMC_TRI_B_LOWER skips the blocks above its diagonal, which are never written).  Row 0 is
+    alpha^T, test point s stands in row 1 + s.  -> B^T (q, ns, n_pad) view | None."""
+    L = _hip.lib()
+    dt, q = ws.dtype, ws.q
+    st = _hip.stream_ptr(ws.device)
+    L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
+    L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z), _hip.ptr(ws.alpha), q, st)
+    if not variance:
+        return None
+    buf = _vtw_buffer(ws)
+    nrows = int(L.cdll.plmc_pad(1 + ns))
+    L.call("plmc_gemm_tn_tri", dt, 0, 2, nrows, ws.n_pad, ws.n_pad, _hip.ptr(ws.A[:, :, ws.n_pad:]), ws.lda, ws.strideA,
+           _hip.ptr(ws.W), ws.ldw, ws.strideW, _hip.ptr(buf), buf.shape[2], buf.stride(0), q, st)                          # 2: PLMC_TRI_B_LOWER
+    hyper_grad_counters["b_products"] += 1
+    return buf[:, 1:1 + ns]
+
+
+class PosteriorHyperMoments(torch.autograd.Function):
+    """(mean, var) of exact_posterior as a function of the kernel's table (ell, oscale), the noise and the targets y as well as of the
+    test inputs Xs (settings.posterior_hyper_grad).  Forward is _exact_posterior -- the values are those of the path
+    without the setting -- on a workspace with the inverse factor, from which it keeps alpha = Khat^-1 y and, unless
+    settings.predictive_variance_grad(False), B^T = K(X*, X) Khat^-1.  Backward builds the operands (posterior_hyper_operands), makes ONE
+    plmc_weighted_grad call on Z = [X; Xs] and returns d ell, d oscale, d noise (less sum gvar: the latent variance carries no noise)
+    and d y = u = B gmean; d Xs as PosteriorMoments returns it when Xs requires a gradient.  Mean-only: r = 2, B is never formed, u comes
+    from one cross_matvec and one solve against the cached factor.  If the factorisation took a jitter, these are the gradients of the
+    jittered model.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, Xs, ell, oscale, noise, y, kind, X, cache, key):
+        variance = settings.predictive_variance_grad.on()
+        x_grad = ctx.needs_input_grad[0]
+        keep = {}
+        out = _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key,
+                               dx=("both" if variance else "mean") if x_grad else None, keep=keep)
+        mean, var = out[0], out[1]
+        Jm, Jv = (out[2], out[3]) if x_grad else (None, None)
+        ws = keep["ws"]
+        n, ns = ws.n, Xs.shape[0]
+        if x_grad:                   # _posterior_jacobians has left alpha and, with `variance`, [alpha | B] = W^T [z | V] in the workspace
+            Bt = ws.wtv[:, :n, 1:1 + ns].transpose(1, 2).contiguous() if variance else None
+        else:
+            Bt = _alpha_and_bt(ws, ns, variance)
+            Bt = None if Bt is None else Bt[:, :, :n].clone()
+        alpha = ws.alpha[:, :n].clone()
+        dt = y.dtype
+        ctx.save_for_backward(alpha, Bt, Jm, Jv, *(_contig(t, dt) for t in (X, Xs, ell, oscale, noise)))
+        ctx.kind, ctx.cache, ctx.key, ctx.variance = kind, cache, key, variance
+        ctx.dtypes = tuple(None if t is None else t.dtype for t in (Xs, ell, oscale, noise, y))
+        if not variance:
+            ctx.mark_non_differentiable(var)
+        return mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gmean, gvar):
+        alpha, Bt, Jm, Jv, X, Xs, ell, oscale, noise = ctx.saved_tensors
+        kind, variance = ctx.kind, ctx.variance and gvar is not None
+        dt = alpha.dtype
+        n, ns = X.shape[0], Xs.shape[0]
+        need = ctx.needs_input_grad
+        g_Xs = None
+        if need[0]:
+            g_Xs = (gmean.to(torch.float64)[:, :, None] * Jm).sum(0)
+            if Jv is not None and variance:
+                g_Xs = g_Xs + (gvar.to(torch.float64)[:, :, None] * Jv).sum(0)
+            g_Xs = g_Xs.to(ctx.dtypes[0])
+        g_ell = g_os = g_noise = g_y = None
+        if any(need[1:5]):
+            gm = gmean.to(dt).contiguous()
+            u = None
+            if not variance:         # u = Khat^-1 (K(X, X*) gm): one column through the cached factor
+                hyper_grad_counters["mean_only_solves"] += 1
+                rhs = cross_matvec(kind, X, Xs, ell, oscale, gm, n=ns)
+                u = solve_cached(kind, X, ell, oscale, noise, rhs.reshape(rhs.shape[0], 1, n), ctx.cache, ctx.key)[:, :, 0]
+            Pt, Qt, u = posterior_hyper_operands(alpha, Bt.transpose(1, 2) if variance else None, gm, gvar if variance else None, n, ns, u=u)
+            if any(need[1:4]):
+                hyper_grad_counters["weighted_grad_calls"] += 1
+                t_ell, t_noise, t_os = weighted_grad(kind, torch.cat([X, Xs]), ell, oscale, Pt, Qt, n + ns)
+                if variance:
+                    t_noise = t_noise - gvar.to(torch.float64).sum(-1)
+                g_ell = t_ell.to(ctx.dtypes[1]) if need[1] else None
+                g_os = t_os.to(ctx.dtypes[2]) if need[2] and t_os is not None else None
+                g_noise = t_noise.to(ctx.dtypes[3]) if need[3] else None
+            g_y = u.to(ctx.dtypes[4]) if need[4] else None
+        return g_Xs, g_ell, g_os, g_noise, g_y, None, None, None, None
+
+
 def posterior_jacobians(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):
     """(Jm, Jv), (q, ns, d) float64: d mean / dXs and d var / dXs of exact_posterior's marginal moments, read off the kernel's output --
     no autograd graph."""
@@ -1266,23 +1456,33 @@ def mix_posterior(mean_lat, var_lat, Ht, eps=0.0):
 
 class MixPosterior(torch.autograd.Function):
     """mix_posterior as a function of the latent moments (the mixing is linear in them): the values are plmc_mix_posterior's, bit for
-    bit; backward is gmean Ht^T and gvar (Ht^2)^T.  Ht and eps are constants."""
+    bit; backward is gmean Ht^T and gvar (Ht^2)^T.  eps is a constant, and so is Ht unless it requires a gradient
+    (settings.posterior_hyper_grad): then gHt = mean_lat gmean + 2 Ht o (var_lat gvar), plain torch."""
 
     @staticmethod
     def forward(ctx, mean_lat, var_lat, Ht, eps):
         mean, var = mix_posterior(mean_lat, var_lat, Ht, eps)
-        ctx.save_for_backward(Ht.detach().to(mean_lat.dtype))
-        if not ctx.needs_input_grad[1]:
+        h_grad = ctx.needs_input_grad[2]
+        ctx.save_for_backward(Ht.detach().to(mean_lat.dtype), *((mean_lat.detach(), var_lat.detach()) if h_grad else ()))
+        ctx.h_dtype = Ht.dtype
+        if not (ctx.needs_input_grad[1] or h_grad):
             ctx.mark_non_differentiable(var)
         return mean, var
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gmean, gvar):
-        (Ht,) = ctx.saved_tensors
+        Ht = ctx.saved_tensors[0]
         g_mean = (gmean @ Ht.T).T if ctx.needs_input_grad[0] else None
         g_var = (gvar @ (Ht * Ht).T).T if ctx.needs_input_grad[1] and gvar is not None else None
-        return g_mean, g_var, None, None
+        g_Ht = None
+        if ctx.needs_input_grad[2]:
+            mean_lat, var_lat = ctx.saved_tensors[1:]
+            g_Ht = mean_lat @ gmean
+            if gvar is not None:
+                g_Ht = g_Ht + 2.0 * Ht * (var_lat @ gvar)
+            g_Ht = g_Ht.to(ctx.h_dtype)
+        return g_mean, g_var, g_Ht, None
 
 
 def dense_cross(kind, X1, X2, ell, oscale):

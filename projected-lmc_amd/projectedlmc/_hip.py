@@ -79,6 +79,14 @@ _TYPED = {
     "plmc_loo_grad_dot": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
     "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
+    "plmc_weighted_grad": [_I, _P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_add": [_I, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_per": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_lper": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_sum": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_rq": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_dot": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
+    "plmc_weighted_grad_sm": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_input_grad": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _I, _P],
     "plmc_input_grad_add": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
     "plmc_input_grad_sm": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],

@@ -8,6 +8,8 @@ shapes of gpytorch.distributions.MultivariateNormal] -- the reference's syntheti
 `covar` may be a dense tensor, a kernels.LazyKernel (prior of a batch of GPs: log_prob goes to
 the HIP engine) or one of the structured covariances below (never materialised unless asked).
 """
+import math
+
 import torch
 
 from .kernels import LazyKernel
@@ -42,6 +44,20 @@ class KroneckerSumCovariance:
         if self.task_noise is not None:
             dg = dg + torch.diagonal(self.task_noise)[None, :]
         return dg.reshape(-1)
+
+    def log_prob_flat(self, diff):
+        """log N(diff; 0, this covariance), diff (n, p), for latent VARIANCES (full_cov=False): the points are independent and each has
+        the p x p covariance sum_i var_i(s) h_i h_i^T + eps I (+ task noise) -- n small Cholesky factors, plain torch, differentiable in
+        the variances, the mixing matrix and the task noise.  Full latent covariances are not served."""
+        if self.cov is not None:
+            raise NotImplementedError("log_prob of the task-space posterior is implemented for latent variances (full_cov=False) only")
+        Ht = self.Ht.to(diff.dtype)
+        C = torch.einsum("qs,qa,qb->sab", self.var, Ht, Ht) + self.eps * torch.eye(self.p, dtype=diff.dtype, device=diff.device)
+        if self.task_noise is not None:
+            C = C + self.task_noise
+        Lc = torch.linalg.cholesky(C)
+        z = torch.linalg.solve_triangular(Lc, diff.unsqueeze(-1), upper=False).squeeze(-1)
+        return -0.5 * (z * z).sum() - torch.diagonal(Lc, dim1=-2, dim2=-1).log().sum() - 0.5 * diff.numel() * math.log(2.0 * math.pi)
 
     def evaluate(self):
         if self.cov is None:
@@ -207,8 +223,12 @@ class MultivariateNormal:
             y = diff.reshape(q, -1)
             lp = _engine.exact_latent_log_prob(c.kind, c.x1, c.ell, c.oscale, c.noise.reshape(-1), y)
             return lp.reshape(self.batch_shape)
-        raise NotImplementedError("log_prob is implemented for kernel priors (HIP engine) only; "
-                                  "dense / predictive covariances are out of the hot-path scope")
+        if torch.is_tensor(c):          # a dense predictive covariance (n* x n*, usually diagonal): plain torch, differentiable
+            Lc = torch.linalg.cholesky(c)
+            z = torch.linalg.solve_triangular(Lc, diff.unsqueeze(-1), upper=False).squeeze(-1)
+            return (-0.5 * (z * z).sum(-1) - torch.diagonal(Lc, dim1=-2, dim2=-1).log().sum(-1)
+                    - 0.5 * diff.shape[-1] * math.log(2.0 * math.pi))
+        raise NotImplementedError("log_prob is implemented for kernel priors (HIP engine) and dense predictive covariances only")
 
 
 class MultitaskMultivariateNormal(MultivariateNormal):

@@ -272,6 +272,20 @@ class ExactGP(torch.nn.Module):
         return self._posterior(x, **kwargs)
 
 
+def refuse_hyper_grad(full_cov, path=None, input_transform=None):
+    """What settings.posterior_hyper_grad does not serve says so by name: a silently partial gradient is worse than a refusal."""
+    head = "settings.posterior_hyper_grad (predictions differentiable in hyper-parameters, noise and targets): "
+    if path is not None:
+        raise NotImplementedError(head + "%s is not served -- the exact posterior of ExactGPModel and of the unsharded ProjectedGPModel is" % path)
+    if full_cov:
+        raise NotImplementedError(head + "full_cov=True is not served: only the marginal moments (mean, variance) carry the gradient")
+    if settings.skip_posterior_variances.on():
+        raise NotImplementedError(head + "settings.skip_posterior_variances is not served: its mean carries no gradient")
+    if input_transform is not None and any(p.requires_grad for p in input_transform.parameters()):
+        raise NotImplementedError(head + "an input_transform with parameters that require a gradient is not served -- the gradient with "
+                                  "respect to the training inputs through the posterior is not built; freeze the transform's parameters")
+
+
 class ExactGPModel(ExactGP):
     """Standard exact GP; a batch of `n_tasks` independent GPs via batch dimensions
     (projected_lmc.py:264-321)."""
@@ -358,6 +372,10 @@ class ExactGPModel(ExactGP):
         prior_mean = self.mean_module(tx).reshape(self.n_tasks, -1)
         resid = self._latent_targets() - prior_mean
         xs = self.covar_module.select(x)
+        # settings.posterior_hyper_grad: the posterior keeps the graph of the kernel's table, the noise and y - m(X)
+        hyper = settings.posterior_hyper_grad.on() and torch.is_grad_enabled()
+        if hyper:
+            refuse_hyper_grad(full_cov, "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None, self.input_transform)
         if settings.skip_posterior_variances.on():             # the mean alone, K(x*, X) alpha without K(x*, X)
             refuse_skip_variances(x, full_cov, "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None)
             mean = _engine.exact_posterior_mean(lazy.kind, lazy.x1, lazy.ell.detach(), None if lazy.oscale is None else lazy.oscale.detach(),
@@ -370,9 +388,10 @@ class ExactGPModel(ExactGP):
             with torch.no_grad():
                 mean, v = lazy.add_noise(noise.detach().to(lazy.ell.dtype)).posterior(resid.detach(), xs)
             return self._wrap_posterior(mean + self.mean_module(x).reshape(self.n_tasks, -1), torch.diag_embed(v))
-        mean, v = _engine.exact_posterior(lazy.kind, lazy.x1, lazy.ell.detach(),
-                                          None if lazy.oscale is None else lazy.oscale.detach(),
-                                          noise.detach().to(lazy.ell.dtype), resid.detach(), xs, full_cov=full_cov,
+        keep = (lambda t: t) if hyper else (lambda t: t.detach())
+        mean, v = _engine.exact_posterior(lazy.kind, lazy.x1, keep(lazy.ell),
+                                          None if lazy.oscale is None else keep(lazy.oscale),
+                                          keep(noise).to(lazy.ell.dtype), keep(resid), xs, full_cov=full_cov,
                                           cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_targets))
         mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
         return self._wrap_posterior(mean, v if full_cov else torch.diag_embed(v))

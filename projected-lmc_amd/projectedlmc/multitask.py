@@ -13,6 +13,7 @@ import copy
 import torch
 
 from . import _lmc_engine
+from . import settings
 from . import kernels as _k
 from . import means as _m
 from .distributions import MultitaskMultivariateNormal
@@ -99,6 +100,9 @@ class MultitaskGPModel(ExactGPModel):
 
     def _posterior(self, x, **kwargs):
         """Eval mode: exact task posterior from one augmented factorisation of the dense system."""
+        if settings.posterior_hyper_grad.on() and torch.is_grad_enabled():
+            from .models import refuse_hyper_grad
+            refuse_hyper_grad(False, "MultitaskGPModel (dense LMC / ICM)")
         tx = self.train_inputs[0]
         lazy = self.covar_module(tx)
         Sigma = self.likelihood.task_noise_matrix(lazy.B.dtype)

@@ -293,7 +293,15 @@ class ProjectedGPModel(ExactGPModel):
         raw_tx = self.train_inputs[0]
         tx, x = self._features(raw_tx, grad=False), self._test_features(x)
         lazy = self.covar_module(tx)
-        ytil = self.project_data(self.train_y).detach()
+        # settings.posterior_hyper_grad: the latent posterior keeps the graph of the latent kernels' tables, the projected noise and the
+        # projected data; _posterior keeps that of the mixing matrix
+        hyper = settings.posterior_hyper_grad.on() and torch.is_grad_enabled()
+        keep = (lambda t: t) if hyper else (lambda t: t.detach())
+        if hyper:
+            from .models import refuse_hyper_grad
+            refuse_hyper_grad(full_cov, "the latent-sharded ProjectedGPModel (latent_shard / latent_ids)" if self.latent_ids is not None
+                              else "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None, self.input_transform)
+        ytil = keep(self.project_data(self.train_y))
         if self.latent_ids is not None and torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError("the latent-sharded ProjectedGPModel (latent_shard / latent_ids) has no gradient with respect to "
                                       "the test inputs: its prediction all-reduces the ranks' partial sums -- detach x")
@@ -302,8 +310,8 @@ class ProjectedGPModel(ExactGPModel):
                 noisy = lazy.add_noise(self.projected_noise().detach().to(lazy.ell.dtype))
                 return noisy.posterior(ytil, self.covar_module.select(x), full_cov=full_cov)
         ids = self.latent_ids
-        ell, osc, noise = lazy.ell.detach(), lazy.oscale, self.projected_noise().detach().to(lazy.ell.dtype)
-        osc = None if osc is None else osc.detach()
+        ell, osc, noise = keep(lazy.ell), lazy.oscale, keep(self.projected_noise()).to(lazy.ell.dtype)
+        osc = None if osc is None else keep(osc)
         if ids is not None:
             ell, noise, ytil = ell[ids], noise[ids], ytil[ids]
             osc = None if osc is None else osc[ids]
@@ -335,9 +343,14 @@ class ProjectedGPModel(ExactGPModel):
         `.variance` / `.confidence_region()` need); full_cov=True keeps the n* x n* latent blocks.
         With latent sharding the partial sums are all-reduced (the one cross-latent reduction)."""
         if settings.skip_posterior_variances.on():
+            if settings.posterior_hyper_grad.on() and torch.is_grad_enabled():
+                from .models import refuse_hyper_grad
+                refuse_hyper_grad(full_cov)
             return self._mean_only_posterior(x, full_cov)
         mean_lat, v = self._latent_posterior(x, full_cov=full_cov)
-        Ht = self.lmc_coefficients().detach()
+        Ht = self.lmc_coefficients()
+        if not (settings.posterior_hyper_grad.on() and torch.is_grad_enabled()):
+            Ht = Ht.detach()
         v_diag = v if not full_cov else torch.diagonal(v, dim1=-2, dim2=-1)
         if self.latent_ids is not None:
             # this rank's latents: partial sums of mean and variance (plmc_mix_posterior), then the one all-reduce
@@ -347,9 +360,10 @@ class ProjectedGPModel(ExactGPModel):
             parallel.all_reduce_sum(buf)
             mean, var = buf[0], buf[1] + self.eps
             return MultitaskMultivariateNormal(mean, _DiagonalTaskCovariance(var))
-        if mean_lat.requires_grad:
-            # differentiable test inputs: the same values through the mixing's autograd node; `var` carries its graph through
-            # KroneckerSumCovariance(diag=var) to .variance, .stddev and confidence_region()
+        if mean_lat.requires_grad or Ht.requires_grad:
+            # differentiable test inputs (or, under settings.posterior_hyper_grad, hyper-parameters and mixing matrix): the same
+            # values through the mixing's autograd node; `var` carries its graph through KroneckerSumCovariance(diag=var) to
+            # .variance, .stddev and confidence_region()
             mean, var = _engine.MixPosterior.apply(mean_lat, v_diag, Ht, self.eps)
         else:
             mean, var = _engine.mix_posterior(mean_lat, v_diag, Ht, self.eps)

@@ -105,6 +105,27 @@ class predictive_variance_grad(_Value):
         return cls._stack[-1]
 
 
+class posterior_hyper_grad(_Value):
+    """posterior_hyper_grad(True | False): whether an eval-mode prediction is differentiable with respect to the kernel's
+    hyper-parameters, the noise and the training targets (and through them the prior mean and, for ProjectedGPModel, the mixing matrix),
+    as it is behind gpytorch: `loss = -likelihood(model(x_val)).log_prob(y_val); loss.backward()` fills every `.grad`.  Off by default:
+    every prediction then treats them as constants, exactly as before.  When on (and gradients are enabled and something requires
+    one), the exact posterior of ExactGPModel (no inducing points) and of the unsharded ProjectedGPModel keeps the graph; backward is
+    one weighted kernel-gradient sum over the stacked training and test points (plmc_weighted_grad) of rank n* + 2, or
+    2 for a loss of the mean alone (predictive_variance_grad(False): the variance then carries no gradient).  If the cached
+    factorisation took a jitter, the gradient is that of the jittered model.  full_cov=True, the SGPR and variational paths,
+    MultitaskGPModel, the latent-sharded ProjectedGPModel, skip_posterior_variances and an input_transform with parameters that require
+    a gradient raise NotImplementedError while it is on."""
+    _stack = [False]
+
+    def __init__(self, state=True):
+        super().__init__(bool(state))
+
+    @classmethod
+    def on(cls):
+        return cls._stack[-1]
+
+
 class skip_posterior_variances(_Value):
     """skip_posterior_variances(True | False) [gpytorch-knowledge: same name; the covariance becomes zero].  Off by default.  When on, an
     eval-mode ExactGPModel (without inducing points) or ProjectedGPModel call returns the usual distribution with its variance exactly 0

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _var_engine
+from . import settings
 from . import kernels as _k
 from . import means as _m
 from .distributions import MultivariateNormal, MultitaskMultivariateNormal
@@ -252,6 +253,9 @@ class VariationalMultitaskGPModel(torch.nn.Module):
     def __call__(self, x, **kwargs):
         if x.ndimension() == 1:
             x = x.unsqueeze(-1)
+        if not self.training and settings.posterior_hyper_grad.on() and torch.is_grad_enabled():
+            from .models import refuse_hyper_grad
+            refuse_hyper_grad(False, "the variational model (VariationalMultitaskGPModel)")
         return self.variational_strategy(x, **kwargs)
 
     def lscales(self, unpacked=True):
