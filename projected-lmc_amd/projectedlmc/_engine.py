@@ -6,7 +6,6 @@ What it replaces in the reference: the gpytorch evaluation chain behind
 `latent_output.log_prob(proj_target)` (projected_lmc.py:1200-1201), ExactMarginalLogLikelihood
 (experiments.py:233) and `loss.backward()` (experiments.py:270); see SURVEY.md 8a rows a1-a4.
 """
-import ctypes
 import math
 import os
 
@@ -15,6 +14,7 @@ import torch
 from . import _hip
 from . import settings
 from .kernels import dot_power
+from ._families import FAMILIES, LPER, OPERATIONS, PER, RQ, SUM, Sm, family_of, is_sum, sum_members     # noqa: F401 (re-exported)
 from ._pivot import PivotCheck, deferred_pivot_checks, walk      # noqa: F401 (deferred_pivot_checks: re-exported for callers)
 
 LOG2PI = math.log(2.0 * math.pi)
@@ -57,15 +57,8 @@ class Workspace:
             self.ldw, self.strideW = self.lda, self.strideA
             self.alpha = torch.empty(q, self.n_pad, dtype=dtype, device=device)
             # per-tile partial sums of the gradient kernel; the 16-bit planes of W it multiplies are left in Vd by the sweep
-            # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none
-            # (a spectral-mixture table: the library's own size call for it, include/plmc.h "Spectral-mixture kernel")
-            # (a periodic table likewise: "Periodic kernel"; `per` is that kind or the locally periodic one, which has its own size call)
-            nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(self.n_pad, q, ncomp, esz) if sm
-                         else L.cdll.plmc_sum_grad_partials_bytes(self.n_pad, q, ncomp, esz) if per == SUM
-                         else L.cdll.plmc_lper_grad_partials_bytes(self.n_pad, q, esz) if per == LPER
-                         else L.cdll.plmc_per_grad_partials_bytes(self.n_pad, q, esz) if per
-                         else L.cdll.plmc_grad_partials_bytes(self.n_pad, q * ncomp))
-            self.partials = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+            # (plmc_kinv_grad_vd), except with PLMC_SPLIT=0 / fp64, which need none.  (sm, per) name the family whose size call it is
+            self.partials = torch.empty(_partials_bytes(L, self.n_pad, q, esz, ncomp, sm, per) // 8, dtype=torch.float64, device=device)
 
 
 _ws_cache = {}
@@ -130,89 +123,14 @@ def _contig(t, dtype=None):
     return t.contiguous()
 
 
-# ---- the kernel's hyper-parameters.  Every function below takes `ell`, `oscale` either as (q, d), (q) | None -- one ARD kernel per
-# latent -- or as the COMPONENT TABLE of an additive kernel, ell (q, G, d) with +inf (1 / ell = 0) on the dimensions a component
-# ignores and oscale (q, G) | None (include/plmc.h, "Additive kernels"; additive.py builds it).  The table goes to the `_add` entry
-# points, which take G in front of ell; everything else (workspaces, pivot checks, streams, caches) does not look at the kernel.
-# Kind "sm" (kernels.SpectralMixtureKernel): `ell` is the two planes of its table stacked, (q, 2, M, d) = [scales | means], `oscale` its
-# weights (q, M) | None; it goes to the `_sm` entry points, which take no kind and (M, scales, means) in the place of (G, ell)
-# (include/plmc.h, "Spectral-mixture kernel").  The gradient table [d scales | d means | d noise | d weights] splits like the others.
-# Kind "periodic" (kernels.PeriodicKernel): `ell` is the two rows of its table stacked, (q, 2, d) = [lengthscales | periods], `oscale`
-# (q) | None; it goes to the `_per` entry points, which take no kind and (ell, period) in the place of ell (include/plmc.h, "Periodic
-# kernel").  Its table has the rank of an additive one, so the functions that size things take the kind beside it.  The gradient table
-# [d lengthscales | d periods | d noise | d oscale] splits like the others.
-# Kind "rq" (kernels.RQKernel): `ell` is its table (q, d + 1) = [lengthscales | alpha], `oscale` (q) | None; it goes to the `_rq` entry
-# points, which take no kind and (ell, alpha) in the place of ell (include/plmc.h, "Rational-quadratic kernel").  Its table has the rank of
-# a plain one, so what reads the input dimension off the table takes the kind beside it.  The gradient table [d lengthscales | d alpha |
-# d noise | d oscale] splits like the others: its first d + 1 entries are the gradient of the table.
-# Kind "locally_periodic" (kernels.ProductKernel of a periodic and an RBF kernel): `ell` is the three rows of its table stacked,
-# (q, 3, d) = [periodic lengthscales | periods | RBF lengthscales], `oscale` (q) | None; it goes to the `_lper` entry points, which take no
-# kind and (ell, period, rbf_ell) in the place of ell (include/plmc.h, "Locally periodic kernel").  Like the periodic table it has the
-# rank of an additive one and travels with its kind.  The gradient table [d lengthscales | d periods | d RBF lengthscales | d noise |
-# d oscale] splits like the others.
-# Kind "sum(<member>,<member>,...)" (additive.AdditiveKernel with mixed members): the member kinds travel in the kind string, `ell` is
-# the table (q, G, 3 d + 1) of records [lengthscales | periods | RBF lengthscales: d each | alpha] of which a member reads its own slots
-# only, `oscale` (q, G); it goes to the `_sum` entry points, which take no kind and (G, fam, table) in the place of ell, `fam` a host array
-# of the members' codes (include/plmc.h, "Sums of kernel families").  The table has the rank of an additive one; its gradient table
-# [d table | d noise | d oscale] splits like the others.
-# Kind "linear" / "poly<P>" (kernels.LinearKernel, PolynomialKernel): the dot-product family.  `ell` is its table (q, d + 1) =
-# [variances | offset], `oscale` (q) | None; it goes to the `_dot` entry points, which take no kind and (variances, offset, P) in the place
-# of ell, P a host int read off the kind string (kernels.dot_power; include/plmc.h, "Dot-product kernels").  The table has the rank and
-# the width of the rational-quadratic one and is sized and split like it: [d variances | d offset | d noise | d oscale].  The kernel is
-# not stationary: what needs k(x, x) hands the table to kernels.prior_diagonal.
-PER = "periodic"
-LPER = "locally_periodic"
-RQ = "rq"
-SUM = "sum"
-_SUM = {"plmc_assemble": "plmc_assemble_sum", "plmc_assemble_cross": "plmc_assemble_cross_sum",
-        "plmc_factorize_ex": "plmc_factorize_sum_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sum_vd",
-        "plmc_loo_grad": "plmc_loo_grad_sum", "plmc_weighted_grad": "plmc_weighted_grad_sum", "plmc_input_grad": "plmc_input_grad_sum",
-        "plmc_posterior_dx": "plmc_posterior_dx_sum", "plmc_cross_matvec": "plmc_cross_matvec_sum",
-        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sum"}
-_LPER = {"plmc_assemble": "plmc_assemble_lper", "plmc_assemble_cross": "plmc_assemble_cross_lper",
-         "plmc_factorize_ex": "plmc_factorize_lper_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_lper_vd",
-         "plmc_loo_grad": "plmc_loo_grad_lper", "plmc_weighted_grad": "plmc_weighted_grad_lper", "plmc_input_grad": "plmc_input_grad_lper",
-         "plmc_posterior_dx": "plmc_posterior_dx_lper", "plmc_cross_matvec": "plmc_cross_matvec_lper",
-         "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_lper"}
-_DOT = {"plmc_assemble": "plmc_assemble_dot", "plmc_assemble_cross": "plmc_assemble_cross_dot",
-        "plmc_factorize_ex": "plmc_factorize_dot_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_dot_vd",
-        "plmc_loo_grad": "plmc_loo_grad_dot", "plmc_weighted_grad": "plmc_weighted_grad_dot", "plmc_input_grad": "plmc_input_grad_dot",
-        "plmc_posterior_dx": "plmc_posterior_dx_dot", "plmc_cross_matvec": "plmc_cross_matvec_dot",
-        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_dot"}
-_RQ = {"plmc_assemble": "plmc_assemble_rq", "plmc_assemble_cross": "plmc_assemble_cross_rq",
-       "plmc_factorize_ex": "plmc_factorize_rq_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_rq_vd",
-       "plmc_loo_grad": "plmc_loo_grad_rq", "plmc_weighted_grad": "plmc_weighted_grad_rq", "plmc_input_grad": "plmc_input_grad_rq",
-       "plmc_posterior_dx": "plmc_posterior_dx_rq", "plmc_cross_matvec": "plmc_cross_matvec_rq",
-       "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_rq"}
-_PER = {"plmc_assemble": "plmc_assemble_per", "plmc_assemble_cross": "plmc_assemble_cross_per",
-        "plmc_factorize_ex": "plmc_factorize_per_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_per_vd",
-        "plmc_loo_grad": "plmc_loo_grad_per", "plmc_weighted_grad": "plmc_weighted_grad_per", "plmc_input_grad": "plmc_input_grad_per",
-        "plmc_posterior_dx": "plmc_posterior_dx_per", "plmc_cross_matvec": "plmc_cross_matvec_per",
-        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_per"}
-_SM = {"plmc_assemble": "plmc_assemble_sm", "plmc_assemble_cross": "plmc_assemble_cross_sm",
-       "plmc_factorize_ex": "plmc_factorize_sm_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_sm_vd",
-       "plmc_loo_grad": "plmc_loo_grad_sm", "plmc_weighted_grad": "plmc_weighted_grad_sm", "plmc_input_grad": "plmc_input_grad_sm",
-       "plmc_posterior_dx": "plmc_posterior_dx_sm", "plmc_cross_matvec": "plmc_cross_matvec_sm",
-       "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_sm"}
-_ADD = {"plmc_assemble": "plmc_assemble_add", "plmc_assemble_cross": "plmc_assemble_cross_add",
-        "plmc_factorize_ex": "plmc_factorize_add_ex", "plmc_kinv_grad_vd": "plmc_kinv_grad_add_vd",
-        "plmc_kernel_vjp": "plmc_kernel_vjp_add", "plmc_loo_grad": "plmc_loo_grad_add", "plmc_weighted_grad": "plmc_weighted_grad_add",
-        "plmc_input_grad": "plmc_input_grad_add",
-        "plmc_posterior_dx": "plmc_posterior_dx_add", "plmc_cross_matvec": "plmc_cross_matvec_add",
-        "plmc_cross_matvec_dx": "plmc_cross_matvec_dx_add"}
-
+# ---- the kernel's hyper-parameters.  Every function below takes a kind with its table `ell` and `oscale`: (q, d), (q) | None -- one ARD
+# kernel per latent -- or what the kind's covariance family makes of them.  _families has one row per family: its table's layout, the
+# form of its entry points, its shape check, its component count and the size call of its gradient partials.  The functions here ask
+# the row; everything else (workspaces, pivot checks, streams, caches) does not look at the kernel.
 
 def sum_kind(members):
     """The kind string of a heterogeneous sum of these member kinds."""
     return "%s(%s)" % (SUM, ",".join(members))
-
-
-def is_sum(kind):
-    return isinstance(kind, str) and kind.startswith(SUM + "(")
-
-
-def sum_members(kind):
-    return kind[len(SUM) + 1:-1].split(",")
 
 
 def is_dot(kind):
@@ -226,144 +144,59 @@ def is_sm(ell):
 def _per_kind(kind):
     """The kind if its table is a stack of (q, d) rows with one row of partial sums per tile (periodic, locally periodic), SUM for a
     heterogeneous sum (whatever its members: the key of its workspace), else False."""
-    return SUM if is_sum(kind) else (kind if kind in (PER, LPER) else False)
+    return family_of(kind).per_kind
 
 
 def n_components(ell, kind=None):
-    if kind in (PER, LPER):
-        return 1
-    return ell.shape[2] if ell.dim() == 4 else (ell.shape[1] if ell.dim() == 3 else 1)
+    return family_of(kind, ell.dim()).ncomp(ell)
 
 
 def kind_code(kind):
-    """The library's code of a kernel kind; the spectral mixture has entry points of its own and no code, the periodic, the locally
-    periodic, the rational-quadratic and the dot-product kernels likewise: their name stands in the code's place and sends _kernel_call
-    to them."""
-    return None if kind == "sm" else (kind if kind in (PER, LPER, RQ) or is_sum(kind) or is_dot(kind) else _hip.KIND[kind])
+    """The library's code of a kernel kind.  The families whose entry points take none have no code: the spectral mixture's is None (its
+    table's rank names it), the name of every other stands in the code's place and sends _kernel_call to its family."""
+    return None if kind == "sm" else (_hip.KIND[kind] if family_of(kind).lead_kind else kind)
 
 
 def grad_table_width(ell, kind=None):
-    """Entries per latent of the gradient table: [d/d ell (ell[0].numel()) | d/d noise | d/d oscale (one per component)];
-    spectral mixture: ell[0] is the two planes (2, M, d), [d/d scales | d/d means | d/d noise | d/d weights];
-    periodic: ell[0] is the two rows (2, d), [d/d lengthscales | d/d periods | d/d noise | d/d oscale];
-    locally periodic: ell[0] is the three rows (3, d), [d/d lengthscales | d/d periods | d/d RBF lengthscales | d/d noise | d/d oscale];
-    rational quadratic: ell[0] is (d + 1), [d/d lengthscales | d/d alpha | d/d noise | d/d oscale];
-    dot product: ell[0] is (d + 1), [d/d variances | d/d offset | d/d noise | d/d oscale]."""
+    """Entries per latent of the gradient table: [d/d table (ell[0].numel()) | d/d noise | d/d oscale (one per component)]."""
     return ell[0].numel() + 1 + n_components(ell, kind)
 
 
 def _check_kernel_shape(L, ell, kind=None):
-    if is_sum(kind):
-        members, d = sum_members(kind), (ell.shape[-1] - 1) // 3
-        if ell.dim() != 3 or ell.shape[-1] != 3 * d + 1 or d < 1 or ell.shape[1] != len(members):
-            raise ValueError("the table of a sum of G kernels is (q, G, 3 d + 1) = [lengthscales | periods | RBF lengthscales | alpha] per member")
-        unknown = [m_ for m_ in members if m_ not in _hip.FAM]
-        if unknown:
-            raise ValueError("a sum takes the stationary kinds, periodic, rq and locally_periodic members, not %s" % ", ".join(unknown))
-        if d > L.cdll.plmc_sum_max_dim() or len(members) > L.cdll.plmc_sum_max_components():
-            raise ValueError("sum of %d kernels on %d dimensions exceeds plmc_sum_max_components()=%d / plmc_sum_max_dim()=%d"
-                             % (len(members), d, L.cdll.plmc_sum_max_components(), L.cdll.plmc_sum_max_dim()))
-        return
-    if is_dot(kind):
-        d, P = ell.shape[-1] - 1, dot_power(kind)
-        if ell.dim() != 2 or d < 1:
-            raise ValueError("a dot-product kernel's table is (q, d + 1) = [variances | offset]")
-        if d > L.cdll.plmc_dot_max_dim() or P < 1 or P > L.cdll.plmc_dot_max_power():
-            raise ValueError("dot-product kernel of power %d on %d dimensions exceeds plmc_dot_max_power()=%d / plmc_dot_max_dim()=%d"
-                             % (P, d, L.cdll.plmc_dot_max_power(), L.cdll.plmc_dot_max_dim()))
-        return
-    d = ell.shape[-1] - (1 if kind == RQ else 0)
-    if kind == RQ:
-        if ell.dim() != 2 or d < 1:
-            raise ValueError("a rational-quadratic kernel's table is (q, d + 1) = [lengthscales | alpha]")
-        if d > L.cdll.plmc_rq_max_dim():
-            raise ValueError("rational-quadratic kernel on %d dimensions exceeds plmc_rq_max_dim()=%d" % (d, L.cdll.plmc_rq_max_dim()))
-        return
-    if d > L.cdll.plmc_max_dim():
-        raise ValueError("input dimension %d exceeds plmc_max_dim()=%d" % (d, L.cdll.plmc_max_dim()))
-    if kind == PER:
-        if ell.dim() != 3 or ell.shape[1] != 2:
-            raise ValueError("a periodic kernel's table is (q, 2, d) = [lengthscales | periods]")
-        if d > L.cdll.plmc_per_max_dim():
-            raise ValueError("periodic kernel on %d dimensions exceeds plmc_per_max_dim()=%d" % (d, L.cdll.plmc_per_max_dim()))
-    elif kind == LPER:
-        if ell.dim() != 3 or ell.shape[1] != 3:
-            raise ValueError("a locally periodic kernel's table is (q, 3, d) = [periodic lengthscales | periods | RBF lengthscales]")
-        if d > L.cdll.plmc_lper_max_dim():
-            raise ValueError("locally periodic kernel on %d dimensions exceeds plmc_lper_max_dim()=%d" % (d, L.cdll.plmc_lper_max_dim()))
-    elif is_sm(ell):
-        if d > L.cdll.plmc_sm_max_dim() or n_components(ell) > L.cdll.plmc_sm_max_mixtures():
-            raise ValueError("spectral mixture with %d components on %d dimensions exceeds plmc_sm_max_mixtures()=%d / plmc_sm_max_dim()=%d"
-                             % (n_components(ell), d, L.cdll.plmc_sm_max_mixtures(), L.cdll.plmc_sm_max_dim()))
-    elif n_components(ell) > L.cdll.plmc_max_components():
-        raise ValueError("%d additive components exceed plmc_max_components()=%d" % (n_components(ell), L.cdll.plmc_max_components()))
+    family_of(kind, ell.dim()).check(L, ell, kind)
+
+
+def _partials_bytes(L, n_pad, q, esz, ncomp=1, sm=False, per=False):
+    """Bytes of the per-tile partial sums of the gradient kernels at n_pad, by the size call of the family that a workspace's key names:
+    `sm`, else `per` (True, PER, LPER or SUM: _per_kind), else the plain call, which the other families share (one row of partial sums
+    per tile, latent and component)."""
+    fam = Sm if sm else next(f for f in FAMILIES if f.per_kind == (PER if per is True else per))
+    return int(fam.partials_bytes(L.cdll, n_pad, q, ncomp, esz))
+
+
+def _table_workspace(n, q, naug, dtype, device, need_grad, ell, kind):
+    """The workspace of a kind's table: keyed by what its family's gradient partials depend on."""
+    return get_workspace(n, q, naug, dtype, device, need_grad, n_components(ell, kind), is_sm(ell), _per_kind(kind))
 
 
 def _kernel_call(L, base, dt, head, ell, tail, stream=None):
-    """Entry point `base`(*head, ell, *tail), or its additive form (*head, G, ell, *tail) for a component table, or its spectral-mixture
-    form (*head[1:], M, scales, means, *tail), or its periodic form (*head[1:], lengthscales, periods, *tail) when head[0] is PER, or its
-    locally periodic form (*head[1:], lengthscales, periods, RBF lengthscales, *tail) when head[0] is LPER, or its rational-quadratic form
-    (*head[1:], lengthscales, alpha, *tail) when head[0] is RQ, or its dot-product form (*head[1:], variances, offset, P, *tail) when head[0]
-    is "linear" or "poly<P>".
-    A heterogeneous sum (head[0] a "sum(...)" kind) goes to its form (*head[1:], G, fam, table, *tail); it copies nothing.
+    """Entry point `base`(*head, ell, *tail) in the form of the family that (head[0], ell) belongs to (_families): head[0], the kind's
+    code or name, stays in front for the families that take a code and is dropped for the others, and the family's flat arguments stand
+    in ell's place.  What a family passes beside the table itself -- contiguous copies of its rows or planes, a sum's host array of member
+    codes -- is made once per table and kind and kept on the table: the 3-4 calls of a step share it.
     `stream`: the side stream the call is queued on, if not the current one."""
-    if is_sum(head[0]):
-        fam = getattr(ell, "_sum_fam", None)                 # the host array of member codes, read by the library during the call
-        if fam is None or fam[0] != head[0]:
-            codes = [_hip.FAM[m_] for m_ in sum_members(head[0])]
-            fam = ell._sum_fam = (head[0], (ctypes.c_int * len(codes))(*codes))
-        L.call(_SUM[base], dt, *head[1:], ell.shape[1], ctypes.addressof(fam[1]), _hip.ptr(ell), *tail)
-        return
-    if isinstance(head[0], str) and is_dot(head[0]):
-        rows = getattr(ell, "_dot_rows", None)               # split once per table, as the rational-quadratic kernel's rows below
-        if rows is None:
-            d = ell.shape[1] - 1
-            rows = ell._dot_rows = (ell[:, :d].contiguous(), ell[:, d].contiguous())
-        if stream is not None:
-            rows[0].record_stream(stream)
-            rows[1].record_stream(stream)
-        L.call(_DOT[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), dot_power(head[0]), *tail)
-        return
-    if isinstance(head[0], str) and head[0] == RQ:
-        rows = getattr(ell, "_rq_rows", None)                # split once per table, as the periodic kernel's rows below
-        if rows is None:
-            d = ell.shape[1] - 1
-            rows = ell._rq_rows = (ell[:, :d].contiguous(), ell[:, d].contiguous())
-        if stream is not None:
-            rows[0].record_stream(stream)
-            rows[1].record_stream(stream)
-        L.call(_RQ[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), *tail)
-        return
-    if isinstance(head[0], str) and head[0] == LPER:
-        rows = getattr(ell, "_lper_rows", None)              # split once per table, as the periodic kernel's rows below
-        if rows is None:
-            rows = ell._lper_rows = (ell[:, 0].contiguous(), ell[:, 1].contiguous(), ell[:, 2].contiguous())
-        if stream is not None:
-            for r in rows:
-                r.record_stream(stream)
-        L.call(_LPER[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), _hip.ptr(rows[2]), *tail)
-        return
-    if isinstance(head[0], str) and head[0] == PER:
-        rows = getattr(ell, "_per_rows", None)               # split once per table, as the spectral mixture's planes below
-        if rows is None:
-            rows = ell._per_rows = (ell[:, 0].contiguous(), ell[:, 1].contiguous())
-        if stream is not None:
-            rows[0].record_stream(stream)
-            rows[1].record_stream(stream)
-        L.call(_PER[base], dt, *head[1:], _hip.ptr(rows[0]), _hip.ptr(rows[1]), *tail)
-    elif ell.dim() == 4:
-        planes = getattr(ell, "_sm_planes", None)            # split once per table: the 3-4 calls of a step share the two copies
-        if planes is None:
-            planes = ell._sm_planes = (ell[:, 0].contiguous(), ell[:, 1].contiguous())
-        scales, means = planes
-        if stream is not None:
-            scales.record_stream(stream)
-            means.record_stream(stream)
-        L.call(_SM[base], dt, *head[1:], ell.shape[2], _hip.ptr(scales), _hip.ptr(means), *tail)
-    elif ell.dim() == 3:
-        L.call(_ADD[base], dt, *head, ell.shape[1], _hip.ptr(ell), *tail)
-    else:
-        L.call(base, dt, *head, _hip.ptr(ell), *tail)
+    kind = head[0]
+    fam = family_of(kind, ell.dim())
+    kept = ()
+    if fam.split is not None:
+        cached = getattr(ell, "_family_split", None)
+        if cached is None or cached[0] != kind:
+            cached = ell._family_split = (kind, fam.split(ell, kind))
+        kept = cached[1]
+        if stream is not None and fam.split_on_device:
+            for t in kept:
+                t.record_stream(stream)
+    L.call(OPERATIONS[base][0] % fam.infix, dt, *(head if fam.lead_kind else head[1:]), *fam.flat(ell, kept, kind), *tail)
 
 
 def _split_grad_table(g, ell_shape, os_shape):
@@ -449,10 +282,9 @@ class ExactLatentLogProb(torch.autograd.Function):
         q, n = y.shape
         d = X.shape[1]
         _check_kernel_shape(L, ell, kind)
-        G = n_components(ell, kind)
         need_grad = any(ctx.needs_input_grad[1:5]) or table is not None or x_grad
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), _per_kind(kind))
+        ws = _table_workspace(n, q, 1, dt, dev, need_grad, ell, kind)
         st = _hip.stream_ptr(dev)
         grad = table if table is not None else (torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=dev) if need_grad else None)
         check = settings.check_cholesky.on()
@@ -505,7 +337,7 @@ class ExactLatentLogProb(torch.autograd.Function):
             if check and info.failed():
                 def attempt(jit):
                     nonlocal ws
-                    ws = get_workspace(n, q, 1, dt, dev, need_grad, G, is_sm(ell), _per_kind(kind))   # waits for the failed attempt's gradient kernel
+                    ws = _table_workspace(n, q, 1, dt, dev, need_grad, ell, kind)   # waits for the failed attempt's gradient kernel
                     return enqueue(nzc + jit)
 
                 logp = walk(dt, info, attempt)[1]
@@ -611,7 +443,7 @@ def exact_loo(kind, X, ell, oscale, noise, y):
     d = X.shape[1]
     Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
     _check_kernel_shape(L, ellc, kind)
-    ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), _per_kind(kind))
+    ws = _table_workspace(n, q, 1, dt, dev, True, ellc, kind)
     st = _hip.stream_ptr(dev)
     factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
     L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z),
@@ -711,7 +543,7 @@ class ExactLooLogProb(torch.autograd.Function):
         _check_kernel_shape(L, ell, kind)
         need_grad = any(ctx.needs_input_grad[1:5])
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
-        ws = get_workspace(n, q, 1, dt, dev, True, n_components(ellc, kind), is_sm(ellc), _per_kind(kind))
+        ws = _table_workspace(n, q, 1, dt, dev, True, ellc, kind)
         st = _hip.stream_ptr(dev)
         factorize_checked(kind, Xc, ellc, osc, nzc, yc.reshape(q, 1, n), ws)
         L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
@@ -1218,12 +1050,7 @@ class PosteriorMoments(torch.autograd.Function):
 def _grad_partials(L, n_pad, q, ell, kind, dtype, device):
     """The per-tile partial sums of the family's gradient kernels at n_pad, by the library's own size calls (as Workspace sizes them)."""
     esz = torch.empty((), dtype=dtype).element_size()
-    ncomp, per = n_components(ell, kind), _per_kind(kind)
-    nbytes = int(L.cdll.plmc_sm_grad_partials_bytes(n_pad, q, ncomp, esz) if is_sm(ell)
-                 else L.cdll.plmc_sum_grad_partials_bytes(n_pad, q, ncomp, esz) if per == SUM
-                 else L.cdll.plmc_lper_grad_partials_bytes(n_pad, q, esz) if per == LPER
-                 else L.cdll.plmc_per_grad_partials_bytes(n_pad, q, esz) if per
-                 else L.cdll.plmc_grad_partials_bytes(n_pad, q * ncomp))
+    nbytes = _partials_bytes(L, n_pad, q, esz, n_components(ell, kind), is_sm(ell), _per_kind(kind))
     return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
 
 

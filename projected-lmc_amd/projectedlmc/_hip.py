@@ -9,49 +9,26 @@ import os
 
 import torch
 
+from ._families import FAM, KIND, entry_argtypes, ptr      # noqa: F401 (KIND, FAM, ptr: this module's names for its callers)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PLMC_LIB: dev override (a variant build of the same library, tools/wb_race_probe.py); never a fallback
 LIB_PATH = os.environ.get("PLMC_LIB") or os.path.join(_HERE, "libplmc_hip.so")
 
 ABI_VERSION = 4          # include/plmc.h: plmc_version()
-KIND = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "spline": 4}
-# member codes of a heterogeneous sum (include/plmc.h, PLMC_FAM_*): the stationary kind codes and three more
-FAM = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "periodic": 16, "rq": 17, "locally_periodic": 18}
 
 _c = ctypes
 _P = _c.c_void_p
 _I = _c.c_int
 _L = _c.c_int64
 
-# name -> argtypes, for the per-dtype entry points (suffix added below)
+# name -> argtypes, for the per-dtype entry points (suffix added below): every family form of the operations that have one per
+# covariance family (_families.OPERATIONS x FAMILIES), and the entry points that do not look at a covariance table
 _TYPED = {
-    "plmc_assemble": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_add": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_per": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_lper": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_sum": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_rq": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_dot": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _I, _P],
-    "plmc_assemble_sm": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P],
+    **entry_argtypes(),
     "plmc_write_rhs": [_P, _I, _I, _P, _L, _L, _I, _I, _I, _P],
-    "plmc_assemble_cross": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _L, _L, _I, _P],
-    "plmc_assemble_cross_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _L, _I, _P],
     "plmc_potrf": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P],
     "plmc_potrf_ex": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_ex": [_I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_add_ex": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_per_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_lper_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_sum_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_rq_ex": [_P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_dot_ex": [_P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
-    "plmc_factorize_sm_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
     "plmc_potrs_aug_kept": [_P, _L, _L, _I, _L, _L, _P, _I, _P, _P],
     "plmc_extract_col": [_P, _L, _L, _L, _I, _P, _P, _I, _P],
@@ -62,70 +39,12 @@ _TYPED = {
     "plmc_gemm_tn_tri": [_I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _P],
     "plmc_kinv_grad": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P],
     "plmc_kinv_grad_ex": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P],
-    "plmc_kinv_grad_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_add_vd": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_per_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_lper_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_sum_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_rq_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_dot_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_kinv_grad_sm_vd": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],
-    "plmc_loo_grad": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_add": [_I, _P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_per": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_lper": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_sum": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_rq": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_dot": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
-    "plmc_loo_grad_sm": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
     "plmc_loo_operand": [_P, _L, _L, _L, _P, _P, _L, _L, _L, _I, _I, _P],
-    "plmc_weighted_grad": [_I, _P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_add": [_I, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_per": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_lper": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_sum": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_rq": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_dot": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P],
-    "plmc_weighted_grad_sm": [_P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _I, _P],
-    "plmc_input_grad_add": [_I, _P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P],
-    "plmc_input_grad_sm": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad_per": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad_rq": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad_lper": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad_sum": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
-    "plmc_input_grad_dot": [_P, _L, _L, _L, _P, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P],
-    "plmc_posterior_dx": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_posterior_dx_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _P],
-    "plmc_cross_matvec_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _I, _P, _P, _I, _P],
     "plmc_rff_matvec": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_sm": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_per": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_rq": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_lper": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_sum": [_P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
-    "plmc_cross_matvec_dx_dot": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _L, _L, _I, _P, _P, _P, _I, _P],
     "plmc_rff_matvec_dx": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P],
     "plmc_lmc_assemble": [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P],
     "plmc_lmc_cross": [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _L, _L, _P],
     "plmc_lmc_kinv_grad": [_I, _P, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "plmc_kernel_vjp": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _L, _L, _P, _P, _P, _I, _P],
-    "plmc_kernel_vjp_add": [_I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P, _P, _P, _I, _P],
     "plmc_qr_small": [_P, _I, _I, _L, _P, _L, _P, _L, _P],
     "plmc_comm_allreduce_sum": [_P, _L, _P],
     "plmc_posterior_moments": [_P, _L, _L, _L, _I, _P, _P, _I, _P],
@@ -294,10 +213,6 @@ def lib():
     if _lib is None:
         _lib = _Lib()
     return _lib
-
-
-def ptr(t):
-    return None if t is None else _c.c_void_p(t.data_ptr())
 
 
 class StreamHandle(_c.c_void_p):
