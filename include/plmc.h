@@ -193,6 +193,39 @@ int plmc_potrs_aug_kept_f64(double *A, int64_t n_pad, int64_t lda, int naug, int
                             const double *eig_lo, void *stream);
 
 /*
+ * Bordered update of a finished factorisation: condition a factor buffer WITH the inverse factor on m new rows without a new sweep
+ * (gpytorch's get_fantasy_model [gpytorch-knowledge, unverified offline]).  Per latent, with Khat = U^T U, W = U^-T and the
+ * bordered matrix [[Khat, K12], [K12^T, K22]]:
+ *     V = W K12,  S = K22 - V^T V,  U22 = chol(S)^T,  W22 = U22^-T,  W21 = -W22 (W^T V)^T,
+ *     U' = [[U, V], [0, U22]],  W' = [[W, 0], [W21, W22]],  logdet' = logdet + 2 sum log diag U22.
+ * The caller has already run plmc_assemble_cross_* + plmc_potrs_aug[_kept]_* on the source, as a cached prediction does: the first m
+ * augmented columns of the source hold V (rows >= n zero).  n <= n_pad_src live rows (n < n_pad_src: a factor inside a larger buffer
+ * with identity padding).  K22: (q, m, m) dense, symmetric, noise and jitter on its diagonal.  1 <= m <= plmc_block(); the caller loops
+ * for more.  n_pad_dst >= plmc_pad(n + m).  logdet: q doubles, in: that of the source, out: extended.  info: q ints, out: 0, or
+ * 1 + n + k for the first pivot k of S that is not positive (that latent's new rows are then undefined; the others are not affected).
+ * S and its pivots are carried in fp64 for both element types (k_diag<double> on the 128 x 128 block) and rounded once.
+ * scratch: q * plmc_factor_extend_scratch_bytes(n_pad_src, m, element bytes) bytes, 16-byte aligned (it holds (W^T V)^T, V^T V, the
+ * fp64 block and W21 before its sign); the size call returns -1 for arguments the entry point would refuse.
+ * A_dst == A_src is allowed with identical geometry and n + m <= n_pad: the copy is skipped and rows [n, n + m) are written in place.
+ * Any other overlap of the two buffers is refused.
+ * Effect: A_dst satisfies the with-inverse post-condition of plmc_potrf_* for n + m live rows -- the element-wise upper triangle of
+ * columns [0, n_pad_dst) is U' with exactly the identity on the padded rows; the W' tiles on and below the block diagonal are all
+ * written, explicit zeros above the diagonal inside the diagonal blocks, the identity on its padded part; W tiles above the block
+ * diagonal are never touched.  Of the source only the U tiles on and above and the W tiles on and below the block diagonal and the first
+ * 128 augmented columns are read; its padding identity is not copied.  The destination's augmented block [n_pad_dst, wcol0_dst) is
+ * zeroed (ready for plmc_write_rhs_*); its Vd is not an input of later plmc_potrs_aug_* calls and stays caller-allocated scratch (the
+ * kept planes of plmc_potrs_aug_kept_f32 do NOT exist for an extended factor).  Everything runs on `stream`; fixed-order sums, no
+ * atomics.  The O(n^2) part is the tile copy (HBM-bound, skipped in place); the rest is 3 products of one 128-column tile.
+ */
+int64_t plmc_factor_extend_scratch_bytes(int64_t n_pad, int m, int elem_bytes);
+int plmc_factor_extend_f32(const float *A_src, int n, int64_t n_pad_src, int64_t lda_src, int64_t wcol0_src, int64_t strideA_src, int m,
+                           const float *K22, float *A_dst, int64_t n_pad_dst, int64_t lda_dst, int64_t wcol0_dst, int64_t strideA_dst,
+                           double *logdet, int *info, void *scratch, int q, void *stream);
+int plmc_factor_extend_f64(const double *A_src, int n, int64_t n_pad_src, int64_t lda_src, int64_t wcol0_src, int64_t strideA_src, int m,
+                           const double *K22, double *A_dst, int64_t n_pad_dst, int64_t lda_dst, int64_t wcol0_dst, int64_t strideA_dst,
+                           double *logdet, int *info, void *scratch, int q, void *stream);
+
+/*
  * Gather augmented column c of every latent into a contiguous vector z (q x n_pad) and return
  * quad[latent] = sum z^2 in double (the inv_quad term of MVN.log_prob, :1201).  All n_pad rows are copied; the sum is carried
  * in fp64.  Refused before anything is launched: a null pointer, q < 1, n_pad not a positive multiple of plmc_block(),

@@ -695,7 +695,7 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
             cache.misses += 1
             cache.drop()
             ws = Workspace(n, q, 1 + ns, dt, dev, with_inverse=True, keep_planes=True)
-            factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)
+            ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)      # (extend_cached_factor: the new diagonal carries it too)
             cache.key, cache.ws = key, ws
     # mean = V^T z and |v|^2 per test point: one pass over the augmented columns (plmc_posterior_moments)
     mean = torch.empty(q, ns, dtype=dt, device=dev)
@@ -750,11 +750,65 @@ def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False):
         if cache is not None and mode != "off":
             cache.seen = key
         ws = get_workspace(n, q, P, dt, dev, True)
-    factorize_checked(kind, Xc, ellc, osc, nzc, rhs, ws)
+    ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, rhs, ws)
     ws.alpha_key = None
     if build:
         cache.key, cache.ws = key, ws
     return ws
+
+
+def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
+    """The cached factorisation of a model on X (n, d) conditioned on m new inputs Xnew (m, d) without a new sweep: a NEW
+    workspace of n + m live rows that meets the sweep's post-condition with the inverse factor (plmc_factor_extend, O(n^2 m)), so that every
+    eval-mode path works on it unchanged; the model's own cache (built first through _cached_factor if absent) is read, not changed --
+    only its augmented columns are used for V = U^-T K(X, Xnew), as a cached prediction uses them.  Chunks of min(plmc_block(), naug) new
+    rows: the first call copies base -> destination, the later ones extend the destination in place on its own augmented columns.  The new
+    diagonal carries noise + the jitter the cached factor was built with.  The destination has the capacity (naug) of the base and keeps no
+    planes of the split engine.  Returns the workspace, or None if a pivot of a Schur block was not positive (read once): the caller then
+    has no extended factor and its first prediction factorises through the usual ladder."""
+    _hip.require_device(X, ell, noise, y, Xnew)
+    L = _hip.lib()
+    dt, dev = y.dtype, y.device
+    q, n = y.shape
+    m = Xnew.shape[0]
+    with torch.no_grad():
+        Xc, Xn, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xnew, ell, oscale, noise))
+        _check_kernel_shape(L, ellc, kind)
+        base = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key, always=True)
+        if cache is None or cache.ws is not base:
+            return None                                    # (settings.prediction_cache "off": there is no cache to extend)
+        base.alpha_key = None
+        st = _hip.stream_ptr(dev)
+        k, d = kind_code(kind), Xc.shape[1]
+        dst = Workspace(n + m, q, base.naug, dt, dev, with_inverse=True, keep_planes=False)
+        dst.jitter = float(getattr(base, "jitter", 0.0))
+        dst.logdet.copy_(base.logdet)
+        dst.alpha_key = None
+        diag = nzc.reshape(-1) + dst.jitter
+        esz = torch.empty((), dtype=dt).element_size()
+        scratch = torch.empty(q * int(L.cdll.plmc_factor_extend_scratch_bytes(dst.n_pad, 1, esz)), dtype=torch.uint8, device=dev)
+        Xall = torch.cat([Xc, Xn]).contiguous()
+        step = min(base.NB, base.naug)
+        # (what stands in the other columns of the base's first 128-column strip is substituted along and ignored: plmc_factor_extend
+        # reads V from the first c columns only, and the base's next prediction rewrites the block)
+        cur, live = base, n
+        while live < n + m:
+            c = min(step, n + m - live)
+            Xl, Xs = Xall[:live], Xall[live:live + c].clone()
+            _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(Xl), live, _hip.ptr(Xs), c, d), ellc, (_hip.ptr(osc), _hip.ptr(cur.A), cur.lda,
+                         cur.strideA, cur.n_pad, cur.n_pad, q, st))
+            if cur.keep_planes:
+                L.call("plmc_potrs_aug_kept", dt, _hip.ptr(cur.A), cur.n_pad, cur.lda, c, cur.wcol0, cur.strideA, _hip.ptr(cur.Vd), q, _hip.ptr(nzc), st)
+            else:
+                L.call("plmc_potrs_aug", dt, _hip.ptr(cur.A), cur.n_pad, cur.lda, c, cur.wcol0, cur.strideA, _hip.ptr(cur.Vd), q, st)
+            K22 = dense_cross(kind, Xs, Xs, ellc, osc)
+            K22.diagonal(dim1=1, dim2=2).add_(diag[:, None])
+            L.call("plmc_factor_extend", dt, _hip.ptr(cur.A), live, cur.n_pad, cur.lda, cur.wcol0, cur.strideA, c, _hip.ptr(K22), _hip.ptr(dst.A),
+                   dst.n_pad, dst.lda, dst.wcol0, dst.strideA, _hip.ptr(dst.logdet), _hip.ptr(dst.info), _hip.ptr(scratch), q, st)
+            cur, live = dst, live + c
+        if PivotCheck.eager(dst).failed():
+            return None
+        return dst
 
 
 def exact_posterior_mean(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):

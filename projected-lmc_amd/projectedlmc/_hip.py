@@ -31,6 +31,7 @@ _TYPED = {
     "plmc_potrf_ex": [_P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P],
     "plmc_potrs_aug": [_P, _L, _L, _I, _L, _L, _P, _I, _P],
     "plmc_potrs_aug_kept": [_P, _L, _L, _I, _L, _L, _P, _I, _P, _P],
+    "plmc_factor_extend": [_P, _I, _L, _L, _L, _L, _I, _P, _P, _L, _L, _L, _L, _P, _P, _P, _I, _P],
     "plmc_extract_col": [_P, _L, _L, _L, _I, _P, _P, _I, _P],
     "plmc_wt_matvec": [_P, _L, _L, _L, _P, _P, _I, _P],
     "plmc_w_diag": [_P, _L, _L, _L, _P, _I, _P],
@@ -58,6 +59,7 @@ _PLAIN = {
     "plmc_vd_blocks_for": ([_L, _L, _I], _L),
     "plmc_vd_blocks_keep": ([_L, _L], _L),
     "plmc_split_scales_offset": ([_L, _L], _L),
+    "plmc_factor_extend_scratch_bytes": ([_L, _I, _I], _L),
     "plmc_max_dim": ([], _I),
     "plmc_max_components": ([], _I),
     "plmc_sm_max_mixtures": ([], _I),

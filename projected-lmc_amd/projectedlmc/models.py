@@ -286,6 +286,12 @@ def refuse_hyper_grad(full_cov, path=None, input_transform=None):
                                   "respect to the training inputs through the posterior is not built; freeze the transform's parameters")
 
 
+def refuse_fantasy(path):
+    """What get_fantasy_model does not serve says so by name."""
+    raise NotImplementedError("get_fantasy_model (condition a fitted model on new observations without refactorising): %s is not served -- "
+                              "the eval-mode ExactGPModel and the unsharded ProjectedGPModel with a prediction cache are" % path)
+
+
 class ExactGPModel(ExactGP):
     """Standard exact GP; a batch of `n_tasks` independent GPs via batch dimensions
     (projected_lmc.py:264-321)."""
@@ -401,6 +407,68 @@ class ExactGPModel(ExactGP):
         chosen later, consistent across calls, linear in n*.  Eval mode; the stationary kinds and their additive table."""
         from .paths import sample_paths
         return sample_paths(self, num_paths, num_features, generator)
+
+    # -- fantasy models: condition on new observations through a bordered update of the cached factorisation (DESIGN.md 7.15)
+    def _cache_key_tensors(self):
+        """the training tensors the model's cache key is made of beside its parameters and buffers (_posterior)"""
+        return self.train_inputs[0], self.train_targets
+
+    def _engine_targets(self):
+        """the latent targets y (q, n) the engine is given (_posterior)"""
+        tx = self._features(self.train_inputs[0], grad=False)
+        return self._latent_targets() - self.mean_module(tx).reshape(self.n_tasks, -1)
+
+    def _latent_noise(self):
+        lik = self.likelihood
+        return lik.noise.reshape(-1) if self.batch_lik else torch.diagonal(lik.task_noise_matrix()).reshape(-1)
+
+    def _append_train_data(self, inputs, targets):
+        """[X; X_new] and the targets in the layout of train_targets: (n,), (n_tasks, n) or (n, n_tasks) (_latent_targets)"""
+        tx, y = self.train_inputs[0], self.train_targets
+        n = tx.shape[0]
+        targets = targets.to(y)
+        along = 0 if (y.dim() == 1 or not (y.shape[-1] == n and y.shape[0] == self.n_tasks)) else -1
+        if y.dim() != targets.dim() or targets.shape[along] != inputs.shape[0]:
+            raise ValueError("get_fantasy_model: targets of shape %s do not continue train_targets of shape %s for %d new inputs"
+                             % (tuple(targets.shape), tuple(y.shape), inputs.shape[0]))
+        self.train_inputs = (torch.cat([tx, inputs.to(tx)]),)
+        self.train_targets = torch.cat([y, targets], dim=along)
+
+    def get_fantasy_model(self, inputs, targets):
+        """A new eval-mode model on [X; inputs] / [y; targets] whose cached factorisation was extended by the m new rows in O(n^2 m)
+        (plmc_factor_extend) instead of factorised again: gpytorch's get_fantasy_model [gpytorch-knowledge, unverified offline], the step
+        a Bayesian-optimisation or active-learning loop takes after choosing a point.  The model itself, its cache and its predictions
+        are unchanged; the copy shares no parameter with it.  Every eval-mode path works on the copy; a fantasy model of a fantasy model
+        works.  If a pivot of the border is not positive the copy simply has no cache and its first prediction factorises as usual.
+        The copy's cache has the capacity of this model's (predict on this model first with as many test points as the copy will see),
+        and keeps no planes of the split engine."""
+        if self.training:
+            raise RuntimeError("get_fantasy_model is an eval-mode method: call .eval() first")
+        if hasattr(self.covar_module, "inducing_points"):
+            refuse_fantasy("an inducing-point (SGPR) model")
+        if settings.prediction_cache.value() == "off":
+            refuse_fantasy('settings.prediction_cache("off") (there is no cached factorisation to extend)')
+        if inputs.ndimension() == 1:
+            inputs = inputs.unsqueeze(-1)
+        import copy
+        from torch.nn.utils import parametrize
+        with torch.no_grad(), parametrize.cached():
+            raw_tx = self.train_inputs[0]
+            inputs = inputs.detach().to(raw_tx)
+            lazy = self.covar_module(self._features(raw_tx, grad=False))
+            xnew = self.covar_module.select(self._features(inputs, grad=False))
+            ws = _engine.extend_cached_factor(lazy.kind, lazy.x1, lazy.ell, lazy.oscale, self._latent_noise().to(lazy.ell.dtype),
+                                              self._engine_targets(), xnew, self._prediction_cache(),
+                                              _engine.model_state_key(self, *self._cache_key_tensors()))
+        new = copy.deepcopy(self)
+        with torch.no_grad():
+            new._append_train_data(inputs, targets.detach())
+        if ws is not None:
+            cache = new._prediction_cache()
+            key = _engine.model_state_key(new, *new._cache_key_tensors())
+            cache.key = key + (lazy.kind,) if (_engine.is_sum(lazy.kind) or _engine.is_dot(lazy.kind)) else key
+            cache.ws = ws
+        return new
 
     def _plain_test_inputs(self, x, what):
         """predictive_gradients reads d / d(features seen by the kernel) off the engine: x must BE those features, and the prior mean

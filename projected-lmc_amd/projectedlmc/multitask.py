@@ -98,6 +98,10 @@ class MultitaskGPModel(ExactGPModel):
         covar_x = self.covar_module(x)
         return MultitaskMultivariateNormal(mean_x, covar_x)
 
+    def get_fantasy_model(self, inputs, targets):
+        from .models import refuse_fantasy
+        refuse_fantasy("MultitaskGPModel (dense LMC / ICM)")
+
     def _posterior(self, x, **kwargs):
         """Eval mode: exact task posterior from one augmented factorisation of the dense system."""
         if settings.posterior_hyper_grad.on() and torch.is_grad_enabled():

@@ -319,6 +319,35 @@ class ProjectedGPModel(ExactGPModel):
                                        full_cov=full_cov, cache=self._prediction_cache(),
                                        key=_engine.model_state_key(self, raw_tx, self.train_y) + (tuple(ids) if ids is not None else ()))
 
+    # -- fantasy models (ExactGPModel.get_fantasy_model): the q latent factorisations are extended; the observations are
+    # task-space rows (m, p), projected by the copy like the rest of train_y
+    def _cache_key_tensors(self):
+        return self.train_inputs[0], self.train_y
+
+    def _engine_targets(self):
+        return self.project_data(self.train_y)
+
+    def _latent_noise(self):
+        return self.projected_noise()
+
+    def _append_train_data(self, inputs, targets):
+        tx, Y = self.train_inputs[0], self.train_y
+        targets = targets.to(Y)
+        if targets.dim() != 2 or targets.shape != (inputs.shape[0], Y.shape[1]):
+            raise ValueError("get_fantasy_model: targets of shape %s are not %d task-space rows of %d tasks"
+                             % (tuple(targets.shape), inputs.shape[0], Y.shape[1]))
+        self.train_inputs = (torch.cat([tx, inputs.to(tx)]),)
+        self.train_y = torch.cat([Y, targets])
+        if hasattr(self, "Y_squared_norm"):
+            self.Y_squared_norm = (self.train_y ** 2).sum()
+        self.train_targets = torch.zeros_like(self.train_y)
+
+    def get_fantasy_model(self, inputs, targets):
+        if self.latent_ids is not None:
+            from .models import refuse_fantasy
+            refuse_fantasy("the latent-sharded ProjectedGPModel (latent_shard / latent_ids)")
+        return super().get_fantasy_model(inputs, targets)
+
     def compute_loo(self, output=None):
         """LOO moments of the q latent GPs on the projected data, (n x q) each
         (projected_lmc.py:1108-1119)."""

@@ -283,6 +283,10 @@ class VariationalMultitaskGPModel(torch.nn.Module):
     def compute_latent_distrib(self, x, prior=False, **kwargs):
         return self.base_variational_strategy(x, **kwargs)
 
+    def get_fantasy_model(self, inputs, targets):
+        from .models import refuse_fantasy
+        refuse_fantasy("the variational model (VariationalMultitaskGPModel)")
+
     def sample_paths(self, num_paths, num_features=1024, generator=None):
         raise NotImplementedError("sample_paths: the variational model (%s) is not served -- pathwise conditioning here needs the exact "
                                   "factor of the training covariance" % type(self).__name__)
