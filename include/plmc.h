@@ -1296,6 +1296,112 @@ int plmc_kernel_vjp_f64(int kind, const double *X1, int n1, const double *X2, in
                         int64_t strideG, double *gX1, double *gEll, double *gOs, int q, void *stream);
 
 /*
+ * Per-point noise: Khat = K + diag(noise[lat] + pnoise[lat][i]) -- a known or modelled observation variance per training point beside the
+ * latent's scalar one (replicated simulator runs, Monte-Carlo standard errors, a parametric noise model, down-weighted observations).
+ * Two operations, in the form of every family (PLMC_FAMILY_ENTRIES) and both element types:
+ *   plmc_assemble<infix>_pn_*      the arguments of plmc_assemble<infix>_* with `pnoise, stride_pn` behind `noise`;
+ *   plmc_factorize<infix>_pn_ex_*  the arguments of plmc_factorize<infix>_ex_* with `pnoise, stride_pn` behind `noise`: the fused call, same
+ *                                  schedule (the first group's rows in front of the chain, the rest on the helper stream); the scan for
+ *                                  the scales of the split engine reads the assembled diagonal, so it sees the per-point values.
+ * Contract.  For i < n: A_ii = fl(a_ii + pnoise[lat * stride_pn + i]), where a_ii is exactly the value the entry point without `_pn`
+ * writes (the kernel's k(x_i, x_i) and noise[lat] in their existing rounding) -- ONE further IEEE addition.  Every other element the call
+ * writes is bit-identical to that entry point's output, the identity padding (rows and columns >= n, diagonal 1) included.
+ * stride_pn = 0 shares one vector (n values) between the latents; otherwise stride_pn >= n and latent `lat` reads pnoise + lat * stride_pn.
+ * pnoise == NULL ("null pointer") or 0 < stride_pn < n ("bad sizes") is an argument error, reported through plmc_last_error before anything
+ * is launched.  The values must be finite and >= 0; the kernels do not look.
+ * Eigenvalue bound: lambda_min(Khat) >= noise[lat] + min_i pnoise[lat][i], so for plmc_factorize*_pn_ex_* eig_lo[lat] must not exceed
+ * noise[lat] + min_i pnoise[lat * stride_pn + i] (the callers of plmc_potrf_ex_* / plmc_potrs_aug_kept_* behind plmc_assemble*_pn_* pass
+ * the same bound).  The sweep, the gradient kernels and every other entry point are unchanged: d logp / d pnoise_i =
+ * 1/2 (alpha_i^2 - (Khat^-1)_ii) comes from alpha and the `kinv_diag` output of plmc_kinv_grad*_vd_*.
+ */
+int plmc_assemble_pn_f32(int kind, const float *X, int n, int d, const float *ell, const float *oscale, const float *noise, const float *pnoise,
+                         int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_pn_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale, const double *noise, const double *pnoise,
+                         int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_factorize_pn_ex_f32(int kind, const float *X, int n, int d, const float *ell, const float *oscale, const float *noise, const float *pnoise,
+                             int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
+                             int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_pn_ex_f64(int kind, const double *X, int n, int d, const double *ell, const double *oscale, const double *noise,
+                             const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, double *Vd,
+                             double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_add_pn_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, const float *noise,
+                             const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_add_pn_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, const double *noise,
+                             const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_factorize_add_pn_ex_f32(int kind, const float *X, int n, int d, int ncomp, const float *ell, const float *oscale, const float *noise,
+                                 const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,
+                                 double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_add_pn_ex_f64(int kind, const double *X, int n, int d, int ncomp, const double *ell, const double *oscale, const double *noise,
+                                 const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA,
+                                 double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_sm_pn_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                            const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_sm_pn_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                            const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q,
+                            void *stream);
+int plmc_factorize_sm_pn_ex_f32(const float *X, int n, int d, int nmix, const float *scales, const float *means, const float *weights,
+                                const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug,
+                                int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_sm_pn_ex_f64(const double *X, int n, int d, int nmix, const double *scales, const double *means, const double *weights,
+                                const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug,
+                                int64_t strideA, double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_per_pn_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                             const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_per_pn_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                             const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_factorize_per_pn_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *oscale, const float *noise,
+                                 const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,
+                                 double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_per_pn_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *oscale, const double *noise,
+                                 const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA,
+                                 double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_rq_pn_f32(const float *X, int n, int d, const float *ell, const float *alpha, const float *oscale, const float *noise,
+                            const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_rq_pn_f64(const double *X, int n, int d, const double *ell, const double *alpha, const double *oscale, const double *noise,
+                            const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_factorize_rq_pn_ex_f32(const float *X, int n, int d, const float *ell, const float *alpha, const float *oscale, const float *noise,
+                                const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd,
+                                double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_rq_pn_ex_f64(const double *X, int n, int d, const double *ell, const double *alpha, const double *oscale, const double *noise,
+                                const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA,
+                                double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_lper_pn_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
+                              const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q,
+                              void *stream);
+int plmc_assemble_lper_pn_f64(const double *X, int n, int d, const double *ell, const double *period, const double *rbf_ell, const double *oscale,
+                              const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q,
+                              void *stream);
+int plmc_factorize_lper_pn_ex_f32(const float *X, int n, int d, const float *ell, const float *period, const float *rbf_ell, const float *oscale,
+                                  const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug,
+                                  int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_lper_pn_ex_f64(const double *X, int n, int d, const double *ell, const double *period, const double *rbf_ell,
+                                  const double *oscale, const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad,
+                                  int64_t lda, int naug, int64_t strideA, double *Vd, double *logdet, int *info, int with_inverse, int q,
+                                  const double *eig_lo, void *stream);
+int plmc_assemble_sum_pn_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale, const float *noise,
+                             const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_sum_pn_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
+                             const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q,
+                             void *stream);
+int plmc_factorize_sum_pn_ex_f32(const float *X, int n, int d, int ncomp, const int *fam, const float *table, const float *oscale,
+                                 const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug,
+                                 int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_sum_pn_ex_f64(const double *X, int n, int d, int ncomp, const int *fam, const double *table, const double *oscale,
+                                 const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug,
+                                 int64_t strideA, double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+int plmc_assemble_dot_pn_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale, const float *noise,
+                             const float *pnoise, int64_t stride_pn, float *A, int64_t lda, int64_t strideA, int q, void *stream);
+int plmc_assemble_dot_pn_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
+                             const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t lda, int64_t strideA, int q,
+                             void *stream);
+int plmc_factorize_dot_pn_ex_f32(const float *X, int n, int d, const float *var, const float *offset, int power, const float *oscale,
+                                 const float *noise, const float *pnoise, int64_t stride_pn, float *A, int64_t n_pad, int64_t lda, int naug,
+                                 int64_t strideA, float *Vd, double *logdet, int *info, int with_inverse, int q, const float *eig_lo, void *stream);
+int plmc_factorize_dot_pn_ex_f64(const double *X, int n, int d, const double *var, const double *offset, int power, const double *oscale,
+                                 const double *noise, const double *pnoise, int64_t stride_pn, double *A, int64_t n_pad, int64_t lda, int naug,
+                                 int64_t strideA, double *Vd, double *logdet, int *info, int with_inverse, int q, const double *eig_lo, void *stream);
+
+/*
  * Reduced Householder QR of ONE small matrix A (m x n row-major, plmc_qr_max() >= m >= n >= 1) in a single
  * launch: Q (m x n, orthonormal columns), R (n x n upper triangular, the lower part is written as zeros).
  * Replaces `torch.linalg.qr(self.H)` of LMCMixingMatrix.QR in bulk mode (projected_lmc.py:864-875, called at

@@ -275,7 +275,15 @@ struct AssembleJob {
   CovTable table;
   int n;
   const void *X, *noise;
+  const void *pnoise = nullptr;      // per-point noise (plmc_factorize*_pn_ex_*): stride_pn elements between the latents' vectors, 0 = one for all
+  int64_t stride_pn = 0;
 };
+// the per-point arguments of the *_pn entry points, checked before anything is launched
+#define PLMC_REQUIRE_POINT_NOISE(pnoise, stride_pn, n)                                                                                        \
+  do {                                                                                                                                        \
+    PLMC_REQUIRE((pnoise) != nullptr, "null pointer");                                                                                        \
+    PLMC_REQUIRE((stride_pn) == 0 || (stride_pn) >= (n), "bad sizes (stride_pn is 0, one vector for every latent, or >= n)");                 \
+  } while (0)
 // block rows ib0 .. ib0 + nrows - 1 of the covariance matrices (assemble.hip), the first ncols block columns (< 0: all) without the
 // leading skip x skip block triangle; elem_bytes 4 / 8
 int assemble_rows(const AssembleJob &job, int elem_bytes, void *A, int64_t lda, int64_t strideA, int q, int ib0, int nrows, void *stream,

@@ -8,14 +8,35 @@
 
 namespace plmc {
 
+// ---- the noise on the diagonal as the tile walks take it (NZ): the latent's scalar `T` -- the code of the entry points without a per-point
+// vector, as it was -- or PointNoise, the scalar and the latent's per-point vector (plmc_assemble*_pn_*): A_ii = (a_ii + nz) + pn[i], a_ii
+// in the rounding of the scalar form.  The vector is read in diagonal tiles only (a workgroup-uniform condition), once per row: an
+// unconditional load at the index clamped into the vector, and the element-wise select the scalar form already has -- no predicated load.
+template <typename T> struct PointNoise { T nz; const T *pn; };
+template <typename T> struct RowNoise { T nz, pv; };
+template <typename T> __device__ __forceinline__ T row_noise(T nz, int, int, bool) { return nz; }
+template <typename T> __device__ __forceinline__ RowNoise<T> row_noise(const PointNoise<T> &z, int gi, int n, bool diag_tile) {
+  RowNoise<T> r{z.nz, T(0)};
+  if (diag_tile) r.pv = z.pn[gi < n ? gi : n - 1];
+  return r;
+}
+// what a kernel hands to its tile walk for latent `lat`
+template <typename T, bool PN>
+__device__ __forceinline__ auto diag_noise_of(const T *noise, const T *pnoise, int64_t stride_pn, int lat) {
+  if constexpr (PN) return PointNoise<T>{noise[lat], pnoise + (int64_t)lat * stride_pn};
+  else return noise[lat];
+}
+template <typename T> __device__ __forceinline__ T add_noise(T v, T nz) { return v + nz; }
+template <typename T> __device__ __forceinline__ T add_noise(T v, const RowNoise<T> &z) { return (v + z.nz) + z.pv; }
+
 // ---- additive kernels: K = sum_{g < G} os_g k(|(x - x') / ell_g|) + noise I, G <= MAX_COMP components of one stationary kind, each with
 // its own d lengthscales; ell_g[k] = +inf (1 / ell = 0) takes dimension k out of component g.  The inputs are staged RAW, once: the
 // differences x - x' are formed once per element and scaled per component (one rounding each), so a component costs d multiplies,
 // d multiply-adds and one kernel profile.  Same tiling, padding and row-range interface as the kernels above.
 // The tile walk is shared by every kernel that is a table of components (additive, spectral mixture): `value(xr, xc)` is the noise-free
 // covariance of one row against a pair of columns, from their raw coordinates.
-template <typename T, int DCAP, class F>
-__device__ __forceinline__ void assemble_tile_table(const T *xi, const T *xj, int ldu, const F value, T nz, T *Al, int64_t lda,
+template <typename T, int DCAP, class F, class NZ>
+__device__ __forceinline__ void assemble_tile_table(const T *xi, const T *xj, int ldu, const F value, NZ nz, T *Al, int64_t lda,
                                                     int ib, int jb, int n, bool edge) {
   typedef Pair<T> T2;
   const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
@@ -37,10 +58,11 @@ __device__ __forceinline__ void assemble_tile_table(const T *xi, const T *xj, in
     for (int pp = 0; pp < 2; ++pp) v[pp] = value(xr, x2[pp]);
     T o[4] = {v[0].x, v[0].y, v[1].x, v[1].y};
     if (edge) {
+      const auto rn = row_noise<T>(nz, gi, n, ib == jb);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int gj = jb * NB + c0 + c;
-        if (gi < n && gj < n) { if (gi == gj) o[c] += nz; }
+        if (gi < n && gj < n) { if (gi == gj) o[c] = add_noise<T>(o[c], rn); }
         else o[c] = (gi == gj) ? T(1) : T(0);             // identity padding keeps the padded factor trivial
       }
     }
@@ -92,7 +114,8 @@ template <typename T, int DCAP> struct AddTable {
     }
     if (tid < G) par[MAX_COMP * DCAP + tid] = oscale ? oscale[(int64_t)lat * G + tid] : T(1);
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     const T *w = par, *osl = par + MAX_COMP * DCAP;
     if (kind == K_RBF) assemble_tile_table<T, DCAP>(xi, xj, ldu, AddPairValue<T, DCAP, K_RBF>{w, osl, G}, nz, Al, lda, ib, jb, n, edge);
@@ -146,7 +169,8 @@ template <typename T, int DCAP> struct SmTable {
     }
     if (tid < M) par[2 * SM_MAX_MIX * DCAP + tid] = weights ? weights[(int64_t)lat * M + tid] : T(1);
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, SmPairValue<T, DCAP>{par, par + SM_MAX_MIX * DCAP, par + 2 * SM_MAX_MIX * DCAP, M}, nz, Al, lda,
                                  ib, jb, n, edge);
@@ -185,7 +209,8 @@ template <typename T, int DCAP> struct PerTable {
     }
     if (tid == 0) par[3 * DCAP] = oscale ? oscale[lat] : T(1);
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, PerPairValue<T, DCAP>{par, par + DCAP, par + 2 * DCAP, par[3 * DCAP]}, nz, Al, lda, ib, jb, n,
                                  edge);
@@ -227,7 +252,8 @@ template <typename T, int DCAP> struct RqTable {
       par[DCAP + 2] = oscale ? oscale[lat] : T(1);
     }
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, RqPairValue<T, DCAP>{par, par[DCAP], par[DCAP + 1], par[DCAP + 2]}, nz, Al, lda, ib, jb, n, edge);
   }
@@ -265,7 +291,8 @@ template <typename T, int DCAP> struct DotTable {
       par[DCAP + 1] = oscale ? oscale[lat] : T(1);
     }
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, DotPairValue<T, DCAP>{par, par[DCAP], par[DCAP + 1], P}, nz, Al, lda, ib, jb, n, edge);
   }
@@ -306,7 +333,8 @@ template <typename T, int DCAP> struct LperTable {
     }
     if (tid == 0) par[4 * DCAP] = oscale ? oscale[lat] : T(1);
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, LperPairValue<T, DCAP>{par, par + DCAP, par + 2 * DCAP, par + 3 * DCAP, par[4 * DCAP]}, nz, Al,
                                  lda, ib, jb, n, edge);
@@ -384,7 +412,8 @@ template <typename T, int DCAP> struct SumTable {
       }
     }
   }
-  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, T nz, T *Al, int64_t lda, int ib, int jb, int n,
+  template <class NZ>
+  __device__ __forceinline__ void tile(const T *xi, const T *xj, int ldu, const T *par, NZ nz, T *Al, int64_t lda, int ib, int jb, int n,
                                        bool edge) const {
     assemble_tile_table<T, DCAP>(xi, xj, ldu, SumPairValue<T, DCAP>{par, fams, G}, nz, Al, lda, ib, jb, n, edge);
   }

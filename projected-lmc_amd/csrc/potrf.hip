@@ -1527,6 +1527,21 @@ int64_t plmc_split_scales_offset(int64_t n_pad, int64_t lda) { return plmc::VdLa
 PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_ENTRY, f32, float)
 PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_ENTRY, f64, double)
 #undef PLMC_FACTORIZE_ENTRY
+// ... with a per-point noise vector on the diagonal (plmc_assemble*_pn_* + plmc_potrf_ex_*): the job carries it, the sweep is the same --
+// its scan for the fp16 scales reads the assembled diagonal, per-point values included
+#define PLMC_FACTORIZE_PN_ENTRY(SUF, T, INFIX, LEAD, PARAMS, TABLE)                                                                           \
+  int plmc_factorize##INFIX##_pn_ex_##SUF(PLMC_LEAD_##LEAD const T *X, int n, int d, PLMC_UNPACK PARAMS, const T *noise, const T *pnoise,     \
+                                          int64_t stride_pn, T *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, T *Vd,             \
+                                          double *logdet, int *info, int with_inverse, int q, const T *eig_lo, void *stream) {               \
+    PLMC_REQUIRE(n_pad == plmc_pad(n), "n_pad must be plmc_pad(n)");                                                                          \
+    PLMC_REQUIRE_POINT_NOISE(pnoise, stride_pn, n);                                                                                           \
+    const plmc::AssembleJob job{TABLE, n, X, noise, pnoise, stride_pn};                                                                       \
+    PLMC_REQUIRE_TABLE(job.table);                                                                                                            \
+    return potrf_any<T>(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, eig_lo, stream, &job);                               \
+  }
+PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_PN_ENTRY, f32, float)
+PLMC_FAMILY_ENTRIES(PLMC_FACTORIZE_PN_ENTRY, f64, double)
+#undef PLMC_FACTORIZE_PN_ENTRY
 int plmc_potrf_f32(float *A, int64_t n_pad, int64_t lda, int naug, int64_t strideA, float *Vd, double *logdet,
                    int *info, int with_inverse, int q, void *stream) {
   return potrf_f32_any(A, n_pad, lda, naug, strideA, Vd, logdet, info, with_inverse, q, nullptr, stream);

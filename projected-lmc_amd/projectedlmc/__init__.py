@@ -10,7 +10,7 @@ from . import settings, constraints, kernels, means, likelihoods, distributions,
 from .priors import NormalPrior, MultivariateNormalPrior  # noqa: F401
 from .kernels import RBFKernel, MaternKernel, SplineKernel, SpectralMixtureKernel, PeriodicKernel, RQKernel, LinearKernel, PolynomialKernel, ProductKernel, ScaleKernel, MultitaskKernel, LCMKernel, IndexKernel  # noqa: F401
 from .means import ZeroMean, ConstantMean, MultitaskMean, LinearMean, PolynomialMean  # noqa: F401
-from .likelihoods import GaussianLikelihood, MultitaskGaussianLikelihood  # noqa: F401
+from .likelihoods import GaussianLikelihood, MultitaskGaussianLikelihood, FixedNoiseGaussianLikelihood  # noqa: F401
 from .distributions import MultivariateNormal, MultitaskMultivariateNormal  # noqa: F401
 from .mlls import ExactMarginalLogLikelihood, LeaveOneOutPseudoLikelihood  # noqa: F401
 from .models import (ExactGPModel, handle_covar_, init_lmc_coefficients, ScalarParam,  # noqa: F401

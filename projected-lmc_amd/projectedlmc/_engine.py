@@ -207,11 +207,42 @@ def _split_grad_table(g, ell_shape, os_shape):
     return g[:, :ne].reshape(ell_shape), g[:, ne], (None if os_shape is None else g[:, ne + 1:].reshape(os_shape))
 
 
-def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
+# ---- per-point noise.  Beside `noise` (q), one variance per latent, the functions that say so take `pnoise`: (n) -- one vector for every
+# latent -- or (q, n), added to the diagonal behind the scalar (include/plmc.h, "Per-point noise").  Jitter goes on the
+# scalar part; wherever `noise` is an eigenvalue bound, noise + min_i pnoise stands in its place.  A function of this module that has no
+# `pnoise` argument does not serve it, and its callers refuse (refuse_point_noise) instead of dropping the vector.
+
+def point_noise(pnoise, q, n, dtype):
+    """The vector as the library takes it: detached, contiguous, of the call's dtype; (n) or (q, n)."""
+    if pnoise is None:
+        return None
+    if pnoise.dim() not in (1, 2) or pnoise.shape[-1] != n or (pnoise.dim() == 2 and pnoise.shape[0] != q):
+        raise ValueError("per-point noise is (n) = (%d) or (q, n) = (%d, %d), got %s" % (n, q, n, tuple(pnoise.shape)))
+    return _contig(pnoise, dtype)
+
+
+def _pn_args(pn):
+    """(pnoise, stride_pn) of the *_pn entry points: stride 0 shares one vector between the latents"""
+    return _hip.ptr(pn), (0 if pn.dim() == 1 else pn.shape[-1])
+
+
+def noise_bound(noise, pn):
+    """What stands where `noise` is passed as a lower bound on the eigenvalues of Khat: noise + min_i pnoise, (q)."""
+    return noise if pn is None else (noise + pn.amin(-1)).contiguous()
+
+
+def refuse_point_noise(what):
+    raise NotImplementedError("%s does not serve per-point noise (FixedNoiseGaussianLikelihood): the vector would be dropped from the "
+                              "diagonal -- use the marginal likelihood and the eval-mode predictions of ExactGPModel, or a "
+                              "GaussianLikelihood" % what)
+
+
+def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True, pnoise=None):
     """Assemble Khat (+ rhs / cross-covariance columns) and run the blocked Cholesky.
     rhs: (q, nrhs, n) or None.  Returns nothing; results live in ws (A, Vd, logdet, info).
     eig_lo=False: `noise` is no eigenvalue bound to scale by (a jitter on a noise-free prior, sample_lazy): the fp32 sweep gets
-    eig_lo = NULL and takes the three-plane scheme, which needs none (include/plmc.h, plmc_potrf_ex_*)."""
+    eig_lo = NULL and takes the three-plane scheme, which needs none (include/plmc.h, plmc_potrf_ex_*).
+    pnoise (point_noise()'s result) | None: per-point noise, through the *_pn form of the same entry points."""
     L = _hip.lib()
     dt, dev = ws.dtype, ws.device
     st = _hip.stream_ptr(dev)
@@ -220,8 +251,10 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
     # round 4: assembly and sweep as ONE library call (plmc_factorize_ex_*): the sweep writes the rows of its first group itself and
     # queues the others beside that group's chain (same kernels, same data: bit-identical; PLMC_FUSED_ASSEMBLE=0: two calls)
     fused = os.environ.get("PLMC_FUSED_ASSEMBLE", "1") != "0"
+    pn = () if pnoise is None else _pn_args(pnoise)
+    assemble, fact = ("plmc_assemble", "plmc_factorize_ex") if pnoise is None else ("plmc_assemble_pn", "plmc_factorize_pn_ex")
     if not fused:
-        _kernel_call(L, "plmc_assemble", dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise),
+        _kernel_call(L, assemble, dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise), *pn,
                      _hip.ptr(ws.A), ws.lda, ws.strideA, q, st))
     nrhs = 0 if rhs is None else rhs.shape[1]
     if ws.naug_pad > 0:
@@ -232,19 +265,20 @@ def factorize(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
     # eig_lo = the noise variances: lambda_min(K + s2 I) >= s2 -- the bound the two-plane fp16 split of the bulk fp32 products
     # scales its operands with (include/plmc.h, plmc_potrf_ex_*); ignored by the fp64 entry point
     flags = (1 | (4 if ws.keep_planes else 0)) if ws.with_inverse else 0
-    bound = _hip.ptr(noise) if eig_lo else None
+    lo = noise_bound(noise, pnoise) if eig_lo else None           # (kept alive until the call is queued)
+    bound = _hip.ptr(lo)
     if fused:
-        _kernel_call(L, "plmc_factorize_ex", dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise), _hip.ptr(ws.A), ws.n_pad,
+        _kernel_call(L, fact, dt, (k, _hip.ptr(X), n, d), ell, (_hip.ptr(oscale), _hip.ptr(noise), *pn, _hip.ptr(ws.A), ws.n_pad,
                      ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd), _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, bound, st))
     else:
         L.call("plmc_potrf_ex", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.naug, ws.strideA, _hip.ptr(ws.Vd),
                _hip.ptr(ws.logdet), _hip.ptr(ws.info), flags, q, bound, st)
 
 
-def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True):
-    """factorize + the jitter ladder (_pivot.walk) with the check read at once: on a non-PD pivot retry with noise + jitter.
-    Returns the jitter that was added."""
-    factorize(kind, X, ell, oscale, noise, rhs, ws, Xs, eig_lo)
+def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True, pnoise=None):
+    """factorize + the jitter ladder (_pivot.walk) with the check read at once: on a non-PD pivot retry with noise + jitter (the scalar
+    part takes it, with or without a per-point vector).  Returns the jitter that was added."""
+    factorize(kind, X, ell, oscale, noise, rhs, ws, Xs, eig_lo, pnoise)
     if not settings.check_cholesky.on():
         return 0.0
     check = PivotCheck.eager(ws)
@@ -252,7 +286,7 @@ def factorize_checked(kind, X, ell, oscale, noise, rhs, ws, Xs=None, eig_lo=True
         return 0.0
 
     def attempt(jit):
-        factorize(kind, X, ell, oscale, noise + jit, rhs, ws, Xs, eig_lo)
+        factorize(kind, X, ell, oscale, noise + jit, rhs, ws, Xs, eig_lo, pnoise)
         return PivotCheck.eager(ws), None
 
     return walk(ws.dtype, check, attempt)[0]
@@ -267,11 +301,15 @@ class ExactLatentLogProb(torch.autograd.Function):
     forward(..., kind, table) with table (q, grad_table_width(ell)) float64: the hyper-parameter gradients are written into `table` and
     NOT returned by this node's backward -- the two-node form exact_latent_log_prob builds when a gradient stream
     exists (see _HyperGrad).
+    forward(..., kind, table | None, pnoise) with pnoise (n) | (q, n): per-point noise on the diagonal beside `noise`.  Where it requires a
+    gradient, d logp / d pnoise_i = 1/2 (alpha_i^2 - (Khat^-1)_ii) is returned by this node (both forms), from alpha and the `kinv_diag`
+    output of the K^-1 + gradient kernel -- a buffer that exists only then; the table's d/d noise stays the gradient of the scalar part.
     """
 
     @staticmethod
-    def forward(ctx, X, ell, oscale, noise, y, kind, table=None):
+    def forward(ctx, X, ell, oscale, noise, y, kind, table=None, pnoise=None):
         x_grad = ctx.needs_input_grad[0]
+        pn_grad = pnoise is not None and ctx.needs_input_grad[7]
         if x_grad:
             require_input_grad_kind(kind)
         _hip.require_device(X, ell, noise, y)
@@ -282,8 +320,9 @@ class ExactLatentLogProb(torch.autograd.Function):
         q, n = y.shape
         d = X.shape[1]
         _check_kernel_shape(L, ell, kind)
-        need_grad = any(ctx.needs_input_grad[1:5]) or table is not None or x_grad
+        need_grad = any(ctx.needs_input_grad[1:5]) or table is not None or x_grad or pn_grad
         Xc, ellc, osc, nzc, yc = (_contig(t, dt) for t in (X, ell, oscale, noise, y))
+        pnc = point_noise(pnoise, q, n, dt)
         ws = _table_workspace(n, q, 1, dt, dev, need_grad, ell, kind)
         st = _hip.stream_ptr(dev)
         grad = table if table is not None else (torch.empty(q, grad_table_width(ell, kind), dtype=torch.float64, device=dev) if need_grad else None)
@@ -291,10 +330,11 @@ class ExactLatentLogProb(torch.autograd.Function):
         # d logp / dX, one (n, d) table per latent: the K^-1 + gradient kernel also writes K^-1, plmc_input_grad pulls alpha alpha^T - K^-1
         # back through the kernel's input derivative.  Nothing of this exists when X requires no gradient.
         gX = torch.empty(q, n, d, dtype=torch.float64, device=dev) if x_grad else None
+        kd = torch.empty(q, ws.n_pad, dtype=dt, device=dev) if pn_grad else None       # diag(Khat^-1): only for d logp / d pnoise
 
         def enqueue(noise_eff):
             """factorisation + everything that consumes it; returns (deferred pivot check, logp)."""
-            factorize(kind, Xc, ellc, osc, noise_eff, yc.reshape(q, 1, n), ws)
+            factorize(kind, Xc, ellc, osc, noise_eff, yc.reshape(q, 1, n), ws, pnoise=pnc)
             # (the copy of `info` stays right behind the sweep: the late pivot check of a training step waits for it, and with one
             # latent per rank the host, which then still has the optimiser step and the next projection to queue, is nearly critical)
             info = PivotCheck(ws) if check else None
@@ -303,19 +343,20 @@ class ExactLatentLogProb(torch.autograd.Function):
             if need_grad:
                 L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z),
                        _hip.ptr(ws.alpha), q, st)
+                lo = noise_bound(noise_eff, pnc)          # the gradient call's eig_lo (queued in front of the gradient stream's wait)
                 gs = grad_stream(dev)
                 gst = st
                 if gs is not None:
                     gs.wait_stream(torch.cuda.current_stream(dev))
                     gst = _hip.stream_handle(gs, dev)
-                    for t in (grad, Xc, ellc, osc, noise_eff, gX):
+                    for t in (grad, Xc, ellc, osc, noise_eff, gX, lo, kd):
                         if t is not None:
                             t.record_stream(gs)
                 Kinv = _kinv_buffer(ws) if x_grad else None
                 ldk = Kinv.shape[2] if x_grad else 0
                 _kernel_call(L, "plmc_kinv_grad_vd", dt, (kind_code(kind), _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW,
                              _hip.ptr(ws.alpha), _hip.ptr(Xc), n, d), ellc, (_hip.ptr(osc), _hip.ptr(grad),
-                             _hip.ptr(Kinv), ldk, ws.n_pad * ldk, None, _hip.ptr(ws.partials), q, _hip.ptr(noise_eff), _hip.ptr(ws.Vd), gst),
+                             _hip.ptr(Kinv), ldk, ws.n_pad * ldk, _hip.ptr(kd), _hip.ptr(ws.partials), q, _hip.ptr(lo), _hip.ptr(ws.Vd), gst),
                              stream=gs)
                 if x_grad:
                     _kernel_call(L, "plmc_input_grad", dt, (kind_code(kind), _hip.ptr(Kinv), ws.n_pad, ldk, ws.n_pad * ldk,
@@ -342,8 +383,9 @@ class ExactLatentLogProb(torch.autograd.Function):
 
                 logp = walk(dt, info, attempt)[1]
         if need_grad:
-            ctx.save_for_backward(grad, ws.alpha[:, :n].clone(), gX)
+            ctx.save_for_backward(grad, ws.alpha[:, :n].clone(), gX, kd)
         ctx.x_dtype = X.dtype
+        ctx.pn_meta = (pnoise.dim(), pnoise.dtype) if pn_grad else None
         ctx.grad_ready = getattr(ws, "pending", None) if need_grad else None
         ctx.ell_shape = ell.shape
         ctx.os_shape = None if oscale is None else oscale.shape
@@ -352,20 +394,26 @@ class ExactLatentLogProb(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        grad, alpha, gX = ctx.saved_tensors
+        grad, alpha, gX, kd = ctx.saved_tensors
         dt = alpha.dtype
-        g_X = None
+        g_X = g_pn = None
+        if kd is not None:                 # d logp / d pnoise_i = 1/2 (alpha_i^2 - (Khat^-1)_ii); a shared vector sums the latents
+            if ctx.grad_ready is not None:
+                torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
+            a = alpha.to(torch.float64)
+            g_pn = gout.to(torch.float64)[:, None] * (0.5 * (a * a - kd[:, :alpha.shape[1]].to(torch.float64)))
+            g_pn = (g_pn.sum(0) if ctx.pn_meta[0] == 1 else g_pn).to(ctx.pn_meta[1])
         if gX is not None:                 # X is shared by the latents: their tables, weighted, summed in fp64
             if ctx.grad_ready is not None:
                 torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
             g_X = (gout.to(torch.float64)[:, None, None] * gX).sum(0).to(ctx.x_dtype)
         if ctx.table_out:                  # the hyper-parameter gradients flow through _HyperGrad
-            return g_X, None, None, None, -(gout[:, None].to(dt) * alpha), None, None
+            return g_X, None, None, None, -(gout[:, None].to(dt) * alpha), None, None, g_pn
         if ctx.grad_ready is not None:
             torch.cuda.current_stream(alpha.device).wait_event(ctx.grad_ready)
         g_ell, g_noise, g_os = _split_grad_table(gout.to(torch.float64)[:, None] * grad, ctx.ell_shape, ctx.os_shape)
         g_y = -(gout[:, None].to(dt) * alpha)
-        return g_X, g_ell, g_os, g_noise, g_y, None, None
+        return g_X, g_ell, g_os, g_noise, g_y, None, None, g_pn
 
 
 class _HyperGrad(torch.autograd.Function):
@@ -421,13 +469,14 @@ def prepare_hyper_grad(ell, oscale, noise, kind=None):
     return h
 
 
-def exact_latent_log_prob(kind, X, ell, oscale, noise, y, hyper=None):
+def exact_latent_log_prob(kind, X, ell, oscale, noise, y, hyper=None, pnoise=None):
+    """pnoise (n) | (q, n) | None: per-point noise beside `noise`; it keeps its graph (ExactLatentLogProb)."""
     if hyper is None:
         hyper = prepare_hyper_grad(ell, oscale, noise, kind)
     if hyper is None:
-        return ExactLatentLogProb.apply(X, ell, oscale, noise, y, kind)
+        return ExactLatentLogProb.apply(X, ell, oscale, noise, y, kind, None, pnoise)
     det = lambda t: None if t is None else t.detach()
-    lp = ExactLatentLogProb.apply(X, det(ell), det(oscale), det(noise), y, kind, hyper.table)
+    lp = ExactLatentLogProb.apply(X, det(ell), det(oscale), det(noise), y, kind, hyper.table, pnoise)
     return lp + hyper.hz
 
 
@@ -613,7 +662,7 @@ def model_state_key(module, *tensors):
     return tuple(items)
 
 
-def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None):
+def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, pnoise=None):
     """Posterior of q zero-mean GPs at Xs from ONE augmented factorization [Khat | y | K*^T]:
     with v = U^-T k*, z = U^-T y:  mean = v^T z,  cov = K** - v^T v.
     (ExactGPModel.__call__ in eval mode -> gpytorch DefaultPredictionStrategy; reached from
@@ -625,7 +674,11 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
     every later call then reuses -- a one-shot prediction neither slows down nor holds that memory.  "eager" builds it
     on the first call, "off" never.
     Xs.requires_grad (with gradients enabled): the moments come from the autograd node PosteriorMoments, which carries d mean / dXs and
-    d var / dXs; hyper-parameters, noise and training data stay constants.  Without it nothing below changes."""
+    d var / dXs; hyper-parameters, noise and training data stay constants.  Without it nothing below changes.
+    pnoise (n) | (q, n) | None: per-point noise of the training points (a constant of the prediction); settings.posterior_hyper_grad
+    does not serve it."""
+    if pnoise is not None and settings.posterior_hyper_grad.on() and torch.is_grad_enabled():
+        refuse_point_noise("settings.posterior_hyper_grad (predictions differentiable in hyper-parameters, noise and targets)")
     if settings.posterior_hyper_grad.on() and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (ell, oscale, noise, y)):
         # hyper-parameters, noise or targets carry a graph: the node that differentiates the moments in them (and in Xs, if it asks)
         if full_cov:
@@ -640,11 +693,11 @@ def exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=No
                                       "(mean, variance) are differentiable with respect to the test inputs -- detach them, or "
                                       "predict with full_cov=False")
         require_input_grad_kind(kind)
-        return PosteriorMoments.apply(Xs, kind, X, ell, oscale, noise, y, cache, key)
-    return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov, cache, key)
+        return PosteriorMoments.apply(Xs, kind, X, ell, oscale, noise, y, cache, key, pnoise)
+    return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov, cache, key, **({} if pnoise is None else {"pnoise": pnoise}))
 
 
-def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, dx=None, keep=None):
+def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=None, key=None, dx=None, keep=None, pnoise=None):
     """exact_posterior's work.  dx = "mean" | "both": also the Jacobians of the marginal moments with respect to Xs, -> (mean, var, Jm,
     Jv | None) (_posterior_jacobians); they need the inverse factor, so a miss builds the cache at once where there is one (a caller
     who differentiates predictions will call again) and takes a pooled workspace WITH the inverse factor where there is none.
@@ -655,6 +708,7 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
     q, n = y.shape
     ns = Xs.shape[0]
     Xc, Xsc, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xs, ell, oscale, noise))
+    pnc = point_noise(pnoise, q, n, dt)
     _check_kernel_shape(L, ellc, kind)
     yc = _contig(y).reshape(q, 1, n)
     st = _hip.stream_ptr(dev)
@@ -676,7 +730,7 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
             cache.seen = key
             cache.misses += 1
         ws = get_workspace(n, q, 1 + ns, dt, dev, dx is not None or keep is not None)
-        factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)
+        factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc, pnoise=pnc)
     else:
         if hit:
             # new right-hand sides into the factorised buffer: y (column 0 shares its tile with the first test points, so it
@@ -688,14 +742,14 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
                          _hip.ptr(ws.A), ws.lda, ws.strideA, ws.n_pad + 1, ws.n_pad, q, st))
             if ws.keep_planes:
                 L.call("plmc_potrs_aug_kept", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, 1 + ns, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q,
-                       _hip.ptr(nzc), st)
+                       _hip.ptr(noise_bound(nzc, pnc)), st)
             else:
                 L.call("plmc_potrs_aug", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, 1 + ns, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q, st)
         else:
             cache.misses += 1
             cache.drop()
             ws = Workspace(n, q, 1 + ns, dt, dev, with_inverse=True, keep_planes=True)
-            ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc)      # (extend_cached_factor: the new diagonal carries it too)
+            ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, yc, ws, Xs=Xsc, pnoise=pnc)      # (extend_cached_factor: the new diagonal carries it too)
             cache.key, cache.ws = key, ws
     # mean = V^T z and |v|^2 per test point: one pass over the augmented columns (plmc_posterior_moments)
     mean = torch.empty(q, ns, dtype=dt, device=dev)
@@ -716,12 +770,12 @@ def _exact_posterior(kind, X, ell, oscale, noise, y, Xs, full_cov=False, cache=N
     return mean, var
 
 
-def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False):
+def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False, pnc=None):
     """A factorised workspace WITH the inverse factor whose first augmented columns hold U^-T rhs, rhs (q, P, n): the model's cached one
     where its key matches and it has room for P columns (the new columns are written and forward-substituted, plmc_write_rhs +
     plmc_potrs_aug[_kept]); else a new one, kept in `cache` by the rule of exact_posterior (settings.prediction_cache: eager, the second
     call with one key in lazy mode, or a cached state that is the same and only short of columns; always=True: unless the mode is "off")
-    and otherwise taken from the shared pool."""
+    and otherwise taken from the shared pool.  pnc: per-point noise as point_noise() returns it."""
     L = _hip.lib()
     dt, dev = rhs.dtype, rhs.device
     q, P, n = rhs.shape
@@ -735,7 +789,8 @@ def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False):
         cache.hits += 1
         L.call("plmc_write_rhs", dt, _hip.ptr(rhs), P, n, _hip.ptr(ws.A), ws.lda, ws.strideA, 0, ws.naug_pad, q, st)
         if ws.keep_planes:
-            L.call("plmc_potrs_aug_kept", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, P, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q, _hip.ptr(nzc), st)
+            L.call("plmc_potrs_aug_kept", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, P, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q,
+                   _hip.ptr(noise_bound(nzc, pnc)), st)
         else:
             L.call("plmc_potrs_aug", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, P, ws.wcol0, ws.strideA, _hip.ptr(ws.Vd), q, st)
         ws.alpha_key = None
@@ -750,14 +805,14 @@ def _cached_factor(kind, Xc, ellc, osc, nzc, rhs, cache, key, always=False):
         if cache is not None and mode != "off":
             cache.seen = key
         ws = get_workspace(n, q, P, dt, dev, True)
-    ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, rhs, ws)
+    ws.jitter = factorize_checked(kind, Xc, ellc, osc, nzc, rhs, ws, pnoise=pnc)
     ws.alpha_key = None
     if build:
         cache.key, cache.ws = key, ws
     return ws
 
 
-def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
+def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key, pnoise=None, pnoise_new=None):
     """The cached factorisation of a model on X (n, d) conditioned on m new inputs Xnew (m, d) without a new sweep: a NEW
     workspace of n + m live rows that meets the sweep's post-condition with the inverse factor (plmc_factor_extend, O(n^2 m)), so that every
     eval-mode path works on it unchanged; the model's own cache (built first through _cached_factor if absent) is read, not changed --
@@ -765,7 +820,11 @@ def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
     rows: the first call copies base -> destination, the later ones extend the destination in place on its own augmented columns.  The new
     diagonal carries noise + the jitter the cached factor was built with.  The destination has the capacity (naug) of the base and keeps no
     planes of the split engine.  Returns the workspace, or None if a pivot of a Schur block was not positive (read once): the caller then
-    has no extended factor and its first prediction factorises through the usual ladder."""
+    has no extended factor and its first prediction factorises through the usual ladder.
+    pnoise (n) | (q, n) with pnoise_new (m) | (q, m): per-point noise of the training points and of the new ones -- the new diagonal carries
+    noise + jitter + pnoise_new."""
+    if (pnoise is None) != (pnoise_new is None):
+        raise ValueError("extend_cached_factor: per-point noise is given for the training points and for the new points, or for neither")
     _hip.require_device(X, ell, noise, y, Xnew)
     L = _hip.lib()
     dt, dev = y.dtype, y.device
@@ -774,7 +833,9 @@ def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
     with torch.no_grad():
         Xc, Xn, ellc, osc, nzc = (_contig(t, dt) for t in (X, Xnew, ell, oscale, noise))
         _check_kernel_shape(L, ellc, kind)
-        base = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key, always=True)
+        pnc, pnew = point_noise(pnoise, q, n, dt), point_noise(pnoise_new, q, m, dt)
+        lo = noise_bound(nzc, pnc)
+        base = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key, always=True, pnc=pnc)
         if cache is None or cache.ws is not base:
             return None                                    # (settings.prediction_cache "off": there is no cache to extend)
         base.alpha_key = None
@@ -798,11 +859,13 @@ def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
             _kernel_call(L, "plmc_assemble_cross", dt, (k, _hip.ptr(Xl), live, _hip.ptr(Xs), c, d), ellc, (_hip.ptr(osc), _hip.ptr(cur.A), cur.lda,
                          cur.strideA, cur.n_pad, cur.n_pad, q, st))
             if cur.keep_planes:
-                L.call("plmc_potrs_aug_kept", dt, _hip.ptr(cur.A), cur.n_pad, cur.lda, c, cur.wcol0, cur.strideA, _hip.ptr(cur.Vd), q, _hip.ptr(nzc), st)
+                L.call("plmc_potrs_aug_kept", dt, _hip.ptr(cur.A), cur.n_pad, cur.lda, c, cur.wcol0, cur.strideA, _hip.ptr(cur.Vd), q, _hip.ptr(lo), st)
             else:
                 L.call("plmc_potrs_aug", dt, _hip.ptr(cur.A), cur.n_pad, cur.lda, c, cur.wcol0, cur.strideA, _hip.ptr(cur.Vd), q, st)
             K22 = dense_cross(kind, Xs, Xs, ellc, osc)
             K22.diagonal(dim1=1, dim2=2).add_(diag[:, None])
+            if pnew is not None:
+                K22.diagonal(dim1=1, dim2=2).add_(pnew[..., live - n:live - n + c])
             L.call("plmc_factor_extend", dt, _hip.ptr(cur.A), live, cur.n_pad, cur.lda, cur.wcol0, cur.strideA, c, _hip.ptr(K22), _hip.ptr(dst.A),
                    dst.n_pad, dst.lda, dst.wcol0, dst.strideA, _hip.ptr(dst.logdet), _hip.ptr(dst.info), _hip.ptr(scratch), q, st)
             cur, live = dst, live + c
@@ -811,7 +874,7 @@ def extend_cached_factor(kind, X, ell, oscale, noise, y, Xnew, cache, key):
         return dst
 
 
-def exact_posterior_mean(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):
+def exact_posterior_mean(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None, pnoise=None):
     """Posterior mean of q zero-mean GPs at Xs, (q, ns), as K(Xs, X) alpha with alpha = Khat^-1 y from a factorisation of [Khat | y]
     (settings.skip_posterior_variances): no augmented columns for the test points, so ns is not bounded by a workspace, and K(Xs, X) is
     never written (cross_matvec).  alpha is kept with the model's cached workspace (_cached_factor) and reused while the key is unchanged."""
@@ -830,7 +893,7 @@ def exact_posterior_mean(kind, X, ell, oscale, noise, y, Xs, cache=None, key=Non
             cache.hits += 1
             alpha = ws.alpha_kept
         else:
-            ws = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key)
+            ws = _cached_factor(kind, Xc, ellc, osc, nzc, _contig(y).reshape(q, 1, n), cache, key, pnc=point_noise(pnoise, q, n, dt))
             st = _hip.stream_ptr(dev)
             L.call("plmc_extract_col", dt, _hip.ptr(ws.A), ws.n_pad, ws.lda, ws.strideA, 0, _hip.ptr(ws.z), _hip.ptr(ws.quad), q, st)
             L.call("plmc_wt_matvec", dt, _hip.ptr(ws.W), ws.n_pad, ws.ldw, ws.strideW, _hip.ptr(ws.z), _hip.ptr(ws.alpha), q, st)
@@ -1082,9 +1145,10 @@ class PosteriorMoments(torch.autograd.Function):
     and `var` carries no gradient.  Not twice differentiable."""
 
     @staticmethod
-    def forward(ctx, Xs, kind, X, ell, oscale, noise, y, cache, key):
+    def forward(ctx, Xs, kind, X, ell, oscale, noise, y, cache, key, pnoise=None):
         variance = settings.predictive_variance_grad.on()
-        mean, var, Jm, Jv = _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both" if variance else "mean")
+        pn = {} if pnoise is None else {"pnoise": pnoise}
+        mean, var, Jm, Jv = _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both" if variance else "mean", **pn)
         ctx.save_for_backward(Jm, Jv)
         ctx.x_dtype = Xs.dtype
         if not variance:
@@ -1098,7 +1162,7 @@ class PosteriorMoments(torch.autograd.Function):
         g = (gmean.to(torch.float64)[:, :, None] * Jm).sum(0)
         if Jv is not None and gvar is not None:
             g = g + (gvar.to(torch.float64)[:, :, None] * Jv).sum(0)
-        return (g.to(ctx.x_dtype),) + (None,) * 8
+        return (g.to(ctx.x_dtype),) + (None,) * 9
 
 
 def _grad_partials(L, n_pad, q, ell, kind, dtype, device):
@@ -1275,12 +1339,12 @@ class PosteriorHyperMoments(torch.autograd.Function):
         return g_Xs, g_ell, g_os, g_noise, g_y, None, None, None, None
 
 
-def posterior_jacobians(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None):
+def posterior_jacobians(kind, X, ell, oscale, noise, y, Xs, cache=None, key=None, pnoise=None):
     """(Jm, Jv), (q, ns, d) float64: d mean / dXs and d var / dXs of exact_posterior's marginal moments, read off the kernel's output --
     no autograd graph."""
     require_input_grad_kind(kind)
     with torch.no_grad():
-        return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both")[2:]
+        return _exact_posterior(kind, X, ell, oscale, noise, y, Xs, False, cache, key, dx="both", pnoise=pnoise)[2:]
 
 
 def trmm_ut(ws, n, Z, shift=None):

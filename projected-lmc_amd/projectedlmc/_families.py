@@ -198,6 +198,9 @@ def family_of(kind, ndim=2):
 # PLMC_FAMILY_ENTRIES a family's form drops the kind where it has none and puts its flat arguments where the plain form has `ell`.
 OPERATIONS = {
     "plmc_assemble": ("plmc_assemble%s", [_I, _P, _I, _I], [_P, _P, _P, _L, _L, _I, _P], FAMILIES),
+    # ... with a per-point noise vector behind the scalar noise: (pnoise, stride_pn) (include/plmc.h, "Per-point noise")
+    "plmc_assemble_pn": ("plmc_assemble%s_pn", [_I, _P, _I, _I], [_P, _P, _P, _L, _P, _L, _L, _I, _P], FAMILIES),
+    "plmc_factorize_pn_ex": ("plmc_factorize%s_pn_ex", [_I, _P, _I, _I], [_P, _P, _P, _L, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P], FAMILIES),
     "plmc_assemble_cross": ("plmc_assemble_cross%s", [_I, _P, _I, _P, _I, _I], [_P, _P, _L, _L, _L, _L, _I, _P], FAMILIES),
     "plmc_factorize_ex": ("plmc_factorize%s_ex", [_I, _P, _I, _I], [_P, _P, _P, _L, _L, _I, _L, _P, _P, _P, _I, _I, _P, _P], FAMILIES),
     "plmc_kinv_grad_vd": ("plmc_kinv_grad%s_vd", [_I, _P, _L, _L, _L, _P, _P, _I, _I], [_P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _P],

@@ -164,6 +164,8 @@ class MultivariateNormal:
             from . import _engine
             if not c.is_square:
                 raise NotImplementedError("draws need a square kernel matrix k(X, X)")
+            if getattr(c, "pnoise", None) is not None:
+                _engine.refuse_point_noise("rsample / sample of a kernel prior")
             q = c.ell.shape[0]
             Zk = Z.reshape(S, q, n).permute(1, 2, 0)                   # K-major (q, n, S)
             Y, jit = _engine.sample_lazy(c.kind, c.x1, c.ell, c.oscale, None if c.noise is None else c.noise.reshape(-1), Zk,
@@ -221,7 +223,7 @@ class MultivariateNormal:
                 raise RuntimeError("log_prob of a noise-free kernel prior: apply the likelihood first")
             q = c.ell.shape[0]
             y = diff.reshape(q, -1)
-            lp = _engine.exact_latent_log_prob(c.kind, c.x1, c.ell, c.oscale, c.noise.reshape(-1), y)
+            lp = _engine.exact_latent_log_prob(c.kind, c.x1, c.ell, c.oscale, c.noise.reshape(-1), y, pnoise=c.pnoise)
             return lp.reshape(self.batch_shape)
         if torch.is_tensor(c):          # a dense predictive covariance (n* x n*, usually diagonal): plain torch, differentiable
             Lc = torch.linalg.cholesky(c)

@@ -461,10 +461,11 @@ class LazyKernel:
     lengthscales, the periods and the RBF lengthscales, oscale (q) | None.  kind "sum(<member>,...)": a sum of different families
     (additive.py); the member kinds travel in the kind string (so through add_noise and into the prediction cache's key), ell
     (q, G, 3 d + 1) holds one record [lengthscales | periods | RBF lengthscales | alpha] per member, oscale (q, G).  kind "linear" /
-    "poly<P>": ell (q, d + 1) holds the variances and, in its last column, the offset of a dot-product kernel; oscale (q) | None."""
+    "poly<P>": ell (q, d + 1) holds the variances and, in its last column, the offset of a dot-product kernel; oscale (q) | None.
+    pnoise (n) | (q, n) | None: per-point noise on the diagonal beside `noise` (FixedNoiseGaussianLikelihood): + diag(pnoise)."""
 
-    def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None):
-        self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise = kind, x1, x2, ell, oscale, noise
+    def __init__(self, kind, x1, x2, ell, oscale, batch_shape, noise=None, pnoise=None):
+        self.kind, self.x1, self.x2, self.ell, self.oscale, self.noise, self.pnoise = kind, x1, x2, ell, oscale, noise, pnoise
         self.batch_shape = torch.Size(batch_shape)
         self.is_square = x1 is x2
 
@@ -494,13 +495,23 @@ class LazyKernel:
 
     def add_noise(self, noise):
         return LazyKernel(self.kind, self.x1, self.x2, self.ell, self.oscale, self.batch_shape,
-                          noise if self.noise is None else self.noise + noise)
+                          noise if self.noise is None else self.noise + noise, self.pnoise)
+
+    def add_point_noise(self, pnoise):
+        """+ diag(pnoise), pnoise (n) or (q, n); the scalar noise stays what it is."""
+        n, q = self.x1.shape[-2], self.ell.shape[0]
+        if not self.is_square or pnoise.dim() not in (1, 2) or pnoise.shape[-1] != n or (pnoise.dim() == 2 and pnoise.shape[0] != q):
+            raise ValueError("per-point noise is (n) = (%d) or (q, n) = (%d, %d) on a square kernel matrix, got %s" % (n, q, n, tuple(pnoise.shape)))
+        return LazyKernel(self.kind, self.x1, self.x2, self.ell, self.oscale, self.batch_shape, self.noise,
+                          pnoise if self.pnoise is None else self.pnoise + pnoise)
 
     def diagonal(self, *args, **kwargs):
         q = self.ell.shape[0]
         dg = prior_diagonal(self.kind, self.x1.to(self.ell.dtype), self.oscale, q, self.ell)
         if self.noise is not None:
             dg = dg + self.noise.reshape(-1, 1)
+        if self.pnoise is not None:
+            dg = dg + self.pnoise.to(dg.dtype)
         return dg.reshape(*self.batch_shape, -1)
 
     def evaluate(self):
@@ -509,6 +520,8 @@ class LazyKernel:
                                 None if self.oscale is None else self.oscale.detach())
         if self.noise is not None and self.is_square:
             K = K + self.noise.detach().reshape(-1, 1, 1) * torch.eye(K.shape[-1], dtype=K.dtype, device=K.device)
+        if self.pnoise is not None and self.is_square:
+            K = K + torch.diag_embed(self.pnoise.detach().to(K.dtype).expand(K.shape[0], -1))
         return K.reshape(*self.batch_shape, *K.shape[-2:])
 
     to_dense = evaluate

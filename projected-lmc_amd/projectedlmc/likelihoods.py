@@ -7,6 +7,7 @@ lazy covariance; the addition itself is fused into the HIP assembly kernel.
 [gpytorch-knowledge]: noise = softplus(raw_noise) + lower bound (default 1e-4), raw init 0;
 multitask rank 0: Sigma = diag(task_noises) + noise I; rank r > 0: Sigma = F F^T + noise I with
 F = task_noise_covar_factor (p x r, randn init); has_global_noise=False drops noise I.
+FixedNoiseGaussianLikelihood(noise, learn_additional_noise): a known noise variance per training point (+ a learned scalar).
 """
 import torch
 
@@ -69,6 +70,125 @@ class GaussianLikelihood(_GaussianLikelihoodBase):
         else:
             raise NotImplementedError("GaussianLikelihood on %s" % type(c).__name__)
         return MultivariateNormal(function_dist.mean, new)
+
+
+class FixedNoise(torch.nn.Module):
+    """The per-point noise vector of FixedNoiseGaussianLikelihood: a plain tensor (n) or (*batch_shape, n) -- no parameter, not in the
+    state_dict.  It may be the output of the user's own noise model and then carries its graph."""
+
+    def __init__(self, noise, batch_shape=torch.Size()):
+        super().__init__()
+        self.batch_shape = torch.Size(batch_shape)
+        self.noise = self._checked(noise)
+
+    def __deepcopy__(self, memo):          # (a vector that carries a graph has no deepcopy of its own: the copy holds its values)
+        new = memo[id(self)] = FixedNoise(self.noise.detach().clone(), self.batch_shape)
+        return new
+
+    def _checked(self, noise):
+        if not torch.is_tensor(noise):
+            noise = torch.as_tensor(noise, dtype=torch.get_default_dtype())
+        if noise.dim() == 0 or noise.dim() > 1 + len(self.batch_shape) or (noise.dim() > 1 and noise.shape[:-1] != self.batch_shape):
+            raise ValueError("FixedNoiseGaussianLikelihood: noise is (n) or (*batch_shape, n) with batch_shape %s, got %s"
+                             % (tuple(self.batch_shape), tuple(noise.shape)))
+        if not bool((noise.detach() > 0).all()):
+            raise ValueError("FixedNoiseGaussianLikelihood: noise has non-positive (or non-finite) values; every entry must be > 0")
+        return noise
+
+    def _apply(self, fn, *args, **kwargs):
+        self.noise = fn(self.noise) if not self.noise.requires_grad else self.noise
+        return super()._apply(fn, *args, **kwargs)
+
+
+class FixedNoiseGaussianLikelihood(_GaussianLikelihoodBase):
+    """Gaussian likelihood with a known (or modelled) noise variance per training point, gpytorch's names and meaning
+    [gpytorch-knowledge, unverified offline]: Khat = K + diag(noise) (+ second_noise I with learn_additional_noise=True).
+    `noise` (n) or (*batch_shape, n), every entry > 0: replicated runs averaged to sigma^2 / r_i, Monte-Carlo standard errors, the
+    output of a noise model sigma^2(x) = g_phi(x) (its graph is kept: the marginal likelihood differentiates into it), or a large value
+    that down-weights an observation.  `.noise` gets and sets the vector (`noise_covar.noise`); `.second_noise` is the learned
+    homoskedastic part (`second_noise_covar.raw_noise`, (*batch_shape, 1)).  The addition itself is fused into the HIP assembly kernels
+    (plmc_assemble*_pn_*, plmc_factorize*_pn_ex_*).
+    forward(function_dist, noise=None): the keyword's vector if given; else the stored one if its length is the distribution's; else a
+    UserWarning, and only the additional noise is added (zero without one) -- what evaluating the likelihood at test points without
+    telling it their noise means.
+    Served by ExactGPModel (training with ExactMarginalLogLikelihood, eval-mode predictions, get_fantasy_model(..., noise=)); every other
+    model and objective refuses it by name."""
+
+    def __init__(self, noise, learn_additional_noise=False, batch_shape=torch.Size(), noise_constraint=None, **kwargs):
+        super().__init__()
+        self.batch_shape = torch.Size(batch_shape)
+        self.noise_covar = FixedNoise(noise, self.batch_shape)
+        self.second_noise_covar = HomoskedasticNoise(noise_constraint, self.batch_shape) if learn_additional_noise else None
+
+    @property
+    def noise(self):
+        return self.noise_covar.noise
+
+    @noise.setter
+    def noise(self, value):
+        self.noise_covar.noise = self.noise_covar._checked(value)
+
+    @property
+    def second_noise(self):
+        if self.second_noise_covar is None:
+            return 0.0
+        return self.second_noise_covar.noise
+
+    @second_noise.setter
+    def second_noise(self, value):
+        if self.second_noise_covar is None:
+            raise RuntimeError("FixedNoiseGaussianLikelihood: set second_noise with learn_additional_noise=True only")
+        self.second_noise_covar.noise = value
+
+    def additional_noise(self, q, like):
+        """The homoskedastic part per latent, (q): second_noise, or zeros without one."""
+        if self.second_noise_covar is None:
+            return torch.zeros(q, dtype=like.dtype, device=like.device)
+        return self.second_noise.reshape(-1).to(like.dtype).expand(q)
+
+    def _vector(self, noise, n):
+        """The per-point vector for a distribution over n points: the keyword's, the stored one if it fits, or None with a warning."""
+        if noise is not None:
+            noise = self.noise_covar._checked(noise)
+            if noise.shape[-1] != n:
+                raise ValueError("FixedNoiseGaussianLikelihood: noise= has %d entries for a distribution over %d points" % (noise.shape[-1], n))
+            return noise
+        if self.noise.shape[-1] == n:
+            return self.noise
+        import warnings
+        warnings.warn("FixedNoiseGaussianLikelihood: the distribution has %d points and the stored noise %d, and no noise= was given: only "
+                      "the additional noise is added (pass noise= for the points' own)" % (n, self.noise.shape[-1]), UserWarning)
+        return None
+
+    def forward(self, function_dist, *params, noise=None, **kwargs):
+        c = function_dist.lazy_covariance_matrix
+        if hasattr(c, "log_prob_batch"):
+            raise NotImplementedError("FixedNoiseGaussianLikelihood on the inducing-point (SGPR) covariance of ExactGPModel(n_inducing_points=...) "
+                                      "is not implemented: per-point noise runs on the exact engine only")
+        if isinstance(c, LazyKernel):
+            if not c.is_square:
+                raise NotImplementedError("FixedNoiseGaussianLikelihood on a cross-covariance k(X1, X2)")
+            q = c.ell.shape[0]
+            v = self._vector(noise, c.x1.shape[-2])
+            new = c.add_noise(self.additional_noise(q, c.ell))
+            if v is not None:
+                new = new.add_point_noise(v.to(device=c.ell.device))
+            return MultivariateNormal(function_dist.mean, new)
+        if torch.is_tensor(c):
+            v = self._vector(noise, c.shape[-1])
+            extra = self.second_noise if self.second_noise_covar is None else self.second_noise.reshape(*self.batch_shape, 1).to(c.dtype)
+            dg = extra if v is None else v.to(c) + extra
+            if not torch.is_tensor(dg):
+                return MultivariateNormal(function_dist.mean, c)
+            return MultivariateNormal(function_dist.mean, c + torch.diag_embed(dg.expand(c.shape[:-1])))
+        raise NotImplementedError("FixedNoiseGaussianLikelihood on %s" % type(c).__name__)
+
+
+def refuse_fixed_noise(likelihood, what):
+    """What does not serve per-point noise says so by the likelihood's name instead of dropping the vector."""
+    if isinstance(likelihood, FixedNoiseGaussianLikelihood):
+        raise NotImplementedError("%s is not implemented for FixedNoiseGaussianLikelihood (per-point noise): it is served by ExactGPModel "
+                                  "without inducing points -- ExactMarginalLogLikelihood, eval-mode predictions, get_fantasy_model" % what)
 
 
 class MultitaskGaussianLikelihood(_GaussianLikelihoodBase):

@@ -55,6 +55,8 @@ class LeaveOneOutPseudoLikelihood(ExactMarginalLogLikelihood):
     Serves ExactGPModel without inducing points (a batch of independent tasks is summed, as log_prob does)."""
 
     def __init__(self, likelihood, model, train_x=None, train_y=None):
+        from .likelihoods import refuse_fixed_noise
+        refuse_fixed_noise(likelihood, "LeaveOneOutPseudoLikelihood")
         super().__init__(likelihood, model)
         self.train_x = train_x
         self.train_y = train_y

@@ -13,7 +13,7 @@ from . import settings
 from . import kernels as _k
 from . import means as _m
 from .distributions import MultivariateNormal, MultitaskMultivariateNormal, ZeroCovariance
-from .likelihoods import GaussianLikelihood
+from .likelihoods import FixedNoiseGaussianLikelihood, GaussianLikelihood, refuse_fixed_noise
 
 # model -> (input tensor, version, training input, version) already compared equal (kept outside the module's
 # __dict__: weak references do not pickle)
@@ -311,7 +311,11 @@ class ExactGPModel(ExactGP):
         self.input_transform = input_transform
         self.dim = self._features(self.train_inputs[0][:2].detach(), grad=False).shape[-1]
         self.n_tasks = n_tasks
-        self.batch_lik = isinstance(likelihood, GaussianLikelihood)
+        self.batch_lik = isinstance(likelihood, (GaussianLikelihood, FixedNoiseGaussianLikelihood))
+        # per-point noise (FixedNoiseGaussianLikelihood): the vector rides beside the scalar noise through the engine
+        self.fixed_noise = isinstance(likelihood, FixedNoiseGaussianLikelihood)
+        if n_inducing_points is not None:
+            refuse_fixed_noise(likelihood, "ExactGPModel(n_inducing_points=...) (SGPR)")
         self.mean_module = mean_type(input_size=self.dim, batch_shape=torch.Size([n_tasks]))
         self.covar_module = handle_covar_(kernel_type, dim=self.dim, decomp=decomp, prior_scales=prior_scales,
                                           prior_width=prior_width, outputscales=outputscales, n_funcs=n_tasks,
@@ -370,23 +374,20 @@ class ExactGPModel(ExactGP):
         raw_tx = self.train_inputs[0]
         tx, x = self._features(raw_tx, grad=False), self._test_features(x)
         lazy = self.covar_module(tx)
-        lik = self.likelihood
-        if self.batch_lik:
-            noise = lik.noise.reshape(-1)
-        else:
-            noise = torch.diagonal(lik.task_noise_matrix()).reshape(-1)
+        noise, pnoise = self._latent_noise(), self._point_noise()
         prior_mean = self.mean_module(tx).reshape(self.n_tasks, -1)
         resid = self._latent_targets() - prior_mean
         xs = self.covar_module.select(x)
         # settings.posterior_hyper_grad: the posterior keeps the graph of the kernel's table, the noise and y - m(X)
         hyper = settings.posterior_hyper_grad.on() and torch.is_grad_enabled()
         if hyper:
+            refuse_fixed_noise(self.likelihood, "settings.posterior_hyper_grad")
             refuse_hyper_grad(full_cov, "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None, self.input_transform)
         if settings.skip_posterior_variances.on():             # the mean alone, K(x*, X) alpha without K(x*, X)
             refuse_skip_variances(x, full_cov, "an inducing-point (SGPR) model" if hasattr(lazy, "log_prob_batch") else None)
             mean = _engine.exact_posterior_mean(lazy.kind, lazy.x1, lazy.ell.detach(), None if lazy.oscale is None else lazy.oscale.detach(),
                                                 noise.detach().to(lazy.ell.dtype), resid.detach(), xs, cache=self._prediction_cache(),
-                                                key=_engine.model_state_key(self, raw_tx, self.train_targets))
+                                                key=_engine.model_state_key(self, *self._cache_key_tensors()), pnoise=pnoise)
             with torch.no_grad():
                 mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
             return self._wrap_posterior(mean, ZeroCovariance(mean))
@@ -398,20 +399,23 @@ class ExactGPModel(ExactGP):
         mean, v = _engine.exact_posterior(lazy.kind, lazy.x1, keep(lazy.ell),
                                           None if lazy.oscale is None else keep(lazy.oscale),
                                           keep(noise).to(lazy.ell.dtype), keep(resid), xs, full_cov=full_cov,
-                                          cache=self._prediction_cache(), key=_engine.model_state_key(self, raw_tx, self.train_targets))
+                                          cache=self._prediction_cache(), key=_engine.model_state_key(self, *self._cache_key_tensors()),
+                                          pnoise=pnoise)
         mean = mean + self.mean_module(x).reshape(self.n_tasks, -1)
         return self._wrap_posterior(mean, v if full_cov else torch.diag_embed(v))
 
     def sample_paths(self, num_paths, num_features=1024, generator=None):
         """num_paths draws of the posterior AS FUNCTIONS (pathwise conditioning, paths.PosteriorPaths): evaluable at any number of points
         chosen later, consistent across calls, linear in n*.  Eval mode; the stationary kinds and their additive table."""
+        refuse_fixed_noise(self.likelihood, "sample_paths")
         from .paths import sample_paths
         return sample_paths(self, num_paths, num_features, generator)
 
     # -- fantasy models: condition on new observations through a bordered update of the cached factorisation (DESIGN.md 7.15)
     def _cache_key_tensors(self):
-        """the training tensors the model's cache key is made of beside its parameters and buffers (_posterior)"""
-        return self.train_inputs[0], self.train_targets
+        """the training tensors the model's cache key is made of beside its parameters and buffers (_posterior); with per-point noise
+        the vector is one of them -- a replaced or in-place-edited vector is a new key"""
+        return self.train_inputs[0], self.train_targets, (self.likelihood.noise if getattr(self, "fixed_noise", False) else None)
 
     def _engine_targets(self):
         """the latent targets y (q, n) the engine is given (_posterior)"""
@@ -419,8 +423,21 @@ class ExactGPModel(ExactGP):
         return self._latent_targets() - self.mean_module(tx).reshape(self.n_tasks, -1)
 
     def _latent_noise(self):
+        """the scalar noise per latent, (n_tasks); with per-point noise its homoskedastic part (zeros without an additional noise)"""
         lik = self.likelihood
+        if getattr(self, "fixed_noise", False):
+            return lik.additional_noise(self.n_tasks, self.train_inputs[0])
         return lik.noise.reshape(-1) if self.batch_lik else torch.diagonal(lik.task_noise_matrix()).reshape(-1)
+
+    def _point_noise(self):
+        """the per-point noise of the training points, (n) or (n_tasks, n), detached | None"""
+        if not getattr(self, "fixed_noise", False):
+            return None
+        v, n = self.likelihood.noise, self.train_inputs[0].shape[0]
+        if v.shape[-1] != n or (v.dim() == 2 and v.shape[0] != self.n_tasks):
+            raise ValueError("FixedNoiseGaussianLikelihood: noise of shape %s does not fit %d training points (and %d tasks)"
+                             % (tuple(v.shape), n, self.n_tasks))
+        return v.detach()
 
     def _append_train_data(self, inputs, targets):
         """[X; X_new] and the targets in the layout of train_targets: (n,), (n_tasks, n) or (n, n_tasks) (_latent_targets)"""
@@ -434,8 +451,10 @@ class ExactGPModel(ExactGP):
         self.train_inputs = (torch.cat([tx, inputs.to(tx)]),)
         self.train_targets = torch.cat([y, targets], dim=along)
 
-    def get_fantasy_model(self, inputs, targets):
-        """A new eval-mode model on [X; inputs] / [y; targets] whose cached factorisation was extended by the m new rows in O(n^2 m)
+    def get_fantasy_model(self, inputs, targets, noise=None):
+        """noise (m) | (n_tasks, m): the new points' noise variances, required with a FixedNoiseGaussianLikelihood (the copy's likelihood
+        holds the concatenated vector; the new diagonal carries additional noise + jitter + these values) and refused without one.
+        A new eval-mode model on [X; inputs] / [y; targets] whose cached factorisation was extended by the m new rows in O(n^2 m)
         (plmc_factor_extend) instead of factorised again: gpytorch's get_fantasy_model [gpytorch-knowledge, unverified offline], the step
         a Bayesian-optimisation or active-learning loop takes after choosing a point.  The model itself, its cache and its predictions
         are unchanged; the copy shares no parameter with it.  Every eval-mode path works on the copy; a fantasy model of a fantasy model
@@ -450,6 +469,18 @@ class ExactGPModel(ExactGP):
             refuse_fantasy('settings.prediction_cache("off") (there is no cached factorisation to extend)')
         if inputs.ndimension() == 1:
             inputs = inputs.unsqueeze(-1)
+        pnoise = self._point_noise()
+        if pnoise is None and noise is not None:
+            raise ValueError("get_fantasy_model: noise= is the new points' per-point noise of a FixedNoiseGaussianLikelihood; this model's "
+                             "likelihood is homoskedastic")
+        if pnoise is not None:
+            if noise is None:
+                raise ValueError("get_fantasy_model: a model with a FixedNoiseGaussianLikelihood needs noise=, the new points' noise "
+                                 "variances (m) or (n_tasks, m)")
+            noise = self.likelihood.noise_covar._checked(torch.as_tensor(noise).detach().to(pnoise))
+            if noise.shape[-1] != inputs.shape[0] or noise.dim() != pnoise.dim():
+                raise ValueError("get_fantasy_model: noise= of shape %s does not continue the likelihood's noise of shape %s for %d new inputs"
+                                 % (tuple(noise.shape), tuple(pnoise.shape), inputs.shape[0]))
         import copy
         from torch.nn.utils import parametrize
         with torch.no_grad(), parametrize.cached():
@@ -459,10 +490,12 @@ class ExactGPModel(ExactGP):
             xnew = self.covar_module.select(self._features(inputs, grad=False))
             ws = _engine.extend_cached_factor(lazy.kind, lazy.x1, lazy.ell, lazy.oscale, self._latent_noise().to(lazy.ell.dtype),
                                               self._engine_targets(), xnew, self._prediction_cache(),
-                                              _engine.model_state_key(self, *self._cache_key_tensors()))
+                                              _engine.model_state_key(self, *self._cache_key_tensors()), pnoise=pnoise, pnoise_new=noise)
         new = copy.deepcopy(self)
         with torch.no_grad():
             new._append_train_data(inputs, targets.detach())
+            if pnoise is not None:
+                new.likelihood.noise = torch.cat([pnoise, noise], dim=-1)
         if ws is not None:
             cache = new._prediction_cache()
             key = _engine.model_state_key(new, *new._cache_key_tensors())
@@ -492,12 +525,11 @@ class ExactGPModel(ExactGP):
         x = self._plain_test_inputs(x, "predictive_gradients")
         raw_tx = self.train_inputs[0]
         lazy = self.covar_module(raw_tx)
-        lik = self.likelihood
-        noise = lik.noise.reshape(-1) if self.batch_lik else torch.diagonal(lik.task_noise_matrix()).reshape(-1)
+        noise = self._latent_noise()
         resid = self._latent_targets() - self.mean_module(raw_tx).reshape(self.n_tasks, -1)
         Jm, Jv = _engine.posterior_jacobians(lazy.kind, lazy.x1, lazy.ell.detach(), None if lazy.oscale is None else lazy.oscale.detach(),
                                              noise.detach().to(lazy.ell.dtype), resid.detach(), x, cache=self._prediction_cache(),
-                                             key=_engine.model_state_key(self, raw_tx, self.train_targets))
+                                             key=_engine.model_state_key(self, *self._cache_key_tensors()), pnoise=self._point_noise())
         Jm, Jv = Jm.to(x.dtype), Jv.to(x.dtype)
         if self.n_tasks == 1 and self.train_targets.dim() == 1:
             return Jm[0], Jv[0]
@@ -517,6 +549,7 @@ class ExactGPModel(ExactGP):
         means) is not supported."""
         if complex_mean:
             raise ValueError("A complex mean treatment was required, but the model mean function doesn't allow it !")
+        refuse_fixed_noise(self.likelihood, "compute_loo")
         tx = self._features(self.train_inputs[0], grad=False)
         lazy = self.covar_module(tx)
         lik = self.likelihood

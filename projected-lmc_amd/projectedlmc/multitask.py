@@ -24,6 +24,8 @@ from .projected import _DiagonalTaskCovariance
 class MultitaskGPModel(ExactGPModel):
     def __init__(self, train_x, train_y, likelihood, n_tasks, n_latents, model_type='ICM', init_lmc_coeffs=True,
                  fix_diagonal=False, **kwargs):
+        from .likelihoods import refuse_fixed_noise
+        refuse_fixed_noise(likelihood, "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_sm(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_periodic(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")
         _k.refuse_rq(kwargs.get("kernel_type"), "MultitaskGPModel (dense LMC / ICM)")

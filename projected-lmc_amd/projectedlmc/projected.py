@@ -122,6 +122,8 @@ class ProjectedGPModel(ExactGPModel):
                  diagonal_B=False, scalar_B=False, diagonal_R=False, mean_type=_m.ConstantMean,
                  ortho_param='matrix_exp', bulk=True, noise_thresh=-9., noise_init=1e-2, outputscales=False,
                  eps=1e-3, latent_shard=None, **kwargs):
+        from .likelihoods import refuse_fixed_noise
+        refuse_fixed_noise(proj_likelihood, "ProjectedGPModel")
         if proj_likelihood is None or proj_likelihood.noise.shape[0] != n_latents:
             warnings.warn("In projected GP model the dimension of the likelihood is the number of latent processes. "
                           "Provided likelihood was the wrong shape or None, so it was replaced by a fresh one")

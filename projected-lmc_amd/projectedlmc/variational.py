@@ -298,6 +298,8 @@ class VariationalELBO(torch.nn.Module):
 
     def __init__(self, likelihood, model, num_data, beta=1.0, combine_terms=True):
         super().__init__()
+        from .likelihoods import refuse_fixed_noise
+        refuse_fixed_noise(likelihood, "VariationalELBO / VariationalMultitaskGPModel")
         self.likelihood, self.model, self.num_data, self.beta = likelihood, model, num_data, beta
 
     def forward(self, variational_dist_f, target, **kwargs):
