@@ -393,8 +393,8 @@ class ExactGPModel(ExactGP):
             return self._wrap_posterior(mean, ZeroCovariance(mean))
         if hasattr(lazy, "log_prob_batch"):                    # SGPR predictive moments (sgpr.py)
             with torch.no_grad():
-                mean, v = lazy.add_noise(noise.detach().to(lazy.ell.dtype)).posterior(resid.detach(), xs)
-            return self._wrap_posterior(mean + self.mean_module(x).reshape(self.n_tasks, -1), torch.diag_embed(v))
+                mean, v = lazy.add_noise(noise.detach().to(lazy.ell.dtype)).posterior(resid.detach(), xs, full_cov=full_cov)
+            return self._wrap_posterior(mean + self.mean_module(x).reshape(self.n_tasks, -1), v if full_cov else torch.diag_embed(v))
         keep = (lambda t: t) if hyper else (lambda t: t.detach())
         mean, v = _engine.exact_posterior(lazy.kind, lazy.x1, keep(lazy.ell),
                                           None if lazy.oscale is None else keep(lazy.oscale),
